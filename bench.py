@@ -15,8 +15,8 @@ What one run does, per GPU (one rank per GPU, RCCL for the rank barrier):
    gets the device plugin's allocation env: ``NOS_AMD_POD_SERVER`` (the
    GPU's server socket) + ``NOS_AMD_MEMORY_LIMIT_GB`` in server mode,
    otherwise ``HIP_VISIBLE_DEVICES``, ``NOS_AMD_MEMORY_LIMIT_GB`` and, for
-   ``--mode cumask``, ``ROC_GLOBAL_CU_MASK``.  The node's schedulable capacity
-   for the slice size is also counted by the simulator
+   ``--mode cumask``, ``ROC_GLOBAL_CU_MASK``.  With ``--full`` the node's
+   schedulable capacity for the slice size is also counted by the simulator
    (``schedulable_fractional_pods_per_node_sim``);
 2. data plane: in server mode one pod server per rank (its GPU,
    ``--server-lanes`` streams); each pod is started as its own process with
@@ -46,10 +46,17 @@ A100-80GB (MPS).  gpu_util_pct is the mean amd-smi gfx activity ove
 aggregate_inf_per_s (fp32) is compared with 21.89 inf/s per GPU (the
 reference's best aggregate, 7 MPS pods on one A100).
 
-Also in the JSON: one whole-GPU pod's rate (``--ref-pod-s``), a bf16 fleet on
+A plain run does only that: control plane, pods, warm-up, the timed steps, the
+result line (``ms_per_step`` = the window / ``--steps``).  ``--dump-outputs DIR``
+also writes what every pod of the timed fleet received from its last inference
+(``DIR/gpu<G>_pod<SLOT>_out<K>.npy``, float32: logits and boxes; the pods'
+weights and inputs are seeded, so two builds can be compared output for output).
+
+With ``--full`` also in the JSON: the node's simulated schedulable capacity
+(cumask and hybrid), one whole-GPU pod's rate (``--ref-pod-s``), a bf16 fleet on
 the gfx950 kernels (``--extra-bf16-s``), the reference demo's latency table
 (1/3/5/7 pods: pod-server, shared and CU-mask slices; default on single-GPU runs,
-``--table``), and with WORLD_SIZE > 1 a data-parallel trainer pod per GPU
+``--table``).  With WORLD_SIZE > 1 a data-parallel trainer pod per GPU
 (slot 0: its own pod process with its device-plugin env, CU mask included,
 nos_amd/models/trainer_pod.py -- bf16 MLP forward + backward with bucketed
 RCCL all-reduces over xGMI launched from the gradient hooks, the trainer pods
@@ -91,10 +98,18 @@ def parse_args(argv=None):
                          "(profiles/r04_h3_lanes_ab.json)")
     ap.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--no-graphs", action="store_true")
-    ap.add_argument("--ref-pod-s", type=float, default=4.0,
-                    help="window of the single full-GPU pod reference run (0 = skip)")
-    ap.add_argument("--extra-bf16-s", type=float, default=4.0,
-                    help="window of an extra bf16 (gfx950 kernels) fleet run (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the whole-GPU reference pod (--ref-pod-s), "
+                         "the bf16 fleet (--extra-bf16-s), the latency table (--table) and the simulated capacity "
+                         "probes; without it a run sets up, warms up, times its steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what every pod of the timed fleet received from its last "
+                         "inference as DIR/gpu<G>_pod<SLOT>_out<K>.npy (float32); the pods' weights and inputs are "
+                         "seeded, so two runs with the same arguments are comparable output for output")
+    ap.add_argument("--ref-pod-s", type=float, default=None,
+                    help="--full: window of the single full-GPU pod reference run (default 4, 0 = skip)")
+    ap.add_argument("--extra-bf16-s", type=float, default=None,
+                    help="--full: window of an extra bf16 (gfx950 kernels) fleet run (default 4, 0 = skip)")
     ap.add_argument("--hw-queues", type=int, default=0, help="GPU_MAX_HW_QUEUES per pod (0 = HIP default)")
     ap.add_argument("--bursty", default="", metavar="ON_S:OFF_S",
                     help="bursty tenants: every pod infers for ON_S seconds then idles OFF_S, out of phase "
@@ -106,8 +121,8 @@ def parse_args(argv=None):
     ap.add_argument("--coll-bucket-mb", type=int, default=64)
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda",
                     help="cpu: rehearsal of the whole launch path without a GPU (tiny pods, gloo)")
-    ap.add_argument("--table", default="auto",
-                    help="also measure the reference demo's latency table: comma list of pod counts per GPU "
+    ap.add_argument("--table", default=None,
+                    help="--full: also measure the reference demo's latency table: comma list of pod counts per GPU "
                          "(e.g. 1,3,5,7), one aligned window per (mode, count), reported as latency_table; "
                          "auto = 1,3,5,7 on single-GPU runs, none on multi-GPU runs; '' = none")
     ap.add_argument("--table-modes", default="shared,cumask")
@@ -126,7 +141,19 @@ def parse_args(argv=None):
                     help="BASELINE config 5 instead of the headline: two namespaces' ElasticQuotas on the GPU's "
                          "pod-server slices, borrowing then fair-share preemption acting on running tenants "
                          "(nos_amd/quotabench.py); prints its own JSON line")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.full:
+        args.ref_pod_s = 4.0 if args.ref_pod_s is None else args.ref_pod_s
+        args.extra_bf16_s = 4.0 if args.extra_bf16_s is None else args.extra_bf16_s
+        args.table = "auto" if args.table is None else args.table
+    else:
+        # asking for an extra measurement without --full is an error, never a silent skip
+        asked = [k for k, v in (("--ref-pod-s", args.ref_pod_s), ("--extra-bf16-s", args.extra_bf16_s),
+                                ("--table", args.table)) if v]
+        if asked:
+            ap.error(f"{', '.join(asked)}: the extra measurements run only with --full")
+        args.ref_pod_s, args.extra_bf16_s, args.table = 0.0, 0.0, ""
+    return args
 
 
 def log(rank: int, msg: str) -> None:
@@ -135,13 +162,17 @@ def log(rank: int, msg: str) -> None:
 
 
 POD_SERVER_TENANTS = 48  # per GPU, MPS's client limit; memory bounds it first (28 x 10 GB)
+DUMP_MAX_BYTES = 60 * 10 ** 6  # --dump-outputs: all files together, shared evenly among the pods
 
 
-def plan(args, world: int, local: int, slice_gb: int, pods: int, mode: str) -> tuple[list[dict], dict]:
+def plan(args, world: int, local: int, slice_gb: int, pods: int, mode: str,
+         probe: bool = True) -> tuple[list[dict], dict]:
+    """``probe``: also count the node's schedulable capacity for the slice size
+    (a simulation of its own; main() asks for it only with --full)."""
     from nos_amd.bench_support import control_plane_plan
 
     _, info = control_plane_plan(n_gpus=world, pods_per_gpu=pods, slice_gb=slice_gb, num_cus=256, local_gpu=local,
-                                 cu_policy="proportional" if mode == "cumask" else "shared", capacity_probe=True,
+                                 cu_policy="proportional" if mode == "cumask" else "shared", capacity_probe=probe,
                                  pod_server_tenants=POD_SERVER_TENANTS if mode == "server" else 0,
                                  pod_server_dir=getattr(args, "pod_server_dir", "/tmp/nos_ps"))
     envs = info.pop("envs")
@@ -663,20 +694,28 @@ def main(argv=None) -> int:
     if world != args.gpus:
         log(rank, f"note: --gpus {args.gpus} but WORLD_SIZE {world}; using {world}")
     # control plane first (CPU only): the GPU is initialised by the pods, then by this rank
-    envs, cp = plan(args, world, local, args.slice_gb, args.pods_per_gpu, args.mode)
+    envs, cp = plan(args, world, local, args.slice_gb, args.pods_per_gpu, args.mode, probe=args.full)
     from nos_amd.api import constants as C
     from nos_amd.bench_support import schedulable_pods
 
-    cp10 = {}
-    if args.slice_gb != 10:
-        cp10 = schedulable_pods(world, 10)
-    # hybrid partitioning (modes + memory slices per partition): simulated only --
-    # the pool cannot switch compute/memory modes (needs root), parity unpinned
-    hyb10 = schedulable_pods(world, 10, kind=C.PARTITIONING_HYBRID)
+    cp10, hyb10 = {}, {}
+    if args.full:  # capacity probes: simulations of their own, not needed to place this run's pods
+        if args.slice_gb != 10:
+            cp10 = schedulable_pods(world, 10)
+        # hybrid partitioning (modes + memory slices per partition): simulated only --
+        # the pool cannot switch compute/memory modes (needs root), parity unpinned
+        hyb10 = schedulable_pods(world, 10, kind=C.PARTITIONING_HYBRID)
     extra_env = {"GPU_MAX_HW_QUEUES": str(args.hw_queues)} if args.hw_queues else {}
     if args.device == "cpu":
         extra_env["OMP_NUM_THREADS"] = "1"
     fleet_env = {**extra_env, **({"NOS_AMD_POD_DUTY": args.bursty} if args.bursty else {})}
+    if args.dump_outputs:  # the timed fleet's pods write their last outputs themselves (models/pod.py)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for f in os.listdir(args.dump_outputs):  # an earlier run's files of this GPU
+            if f.startswith(f"gpu{local}_") and f.endswith(".npy"):
+                os.unlink(os.path.join(args.dump_outputs, f))
+        fleet_env["NOS_AMD_POD_DUMP_OUTPUTS"] = os.path.join(os.path.abspath(args.dump_outputs), f"gpu{local}_")
+        fleet_env["NOS_AMD_POD_DUMP_MAX_BYTES"] = str(DUMP_MAX_BYTES // (world * len(envs)))
     log(rank, f"control plane placed {cp.get('placed_pods')} pods; local envs {envs[:2]}...")
     if args.table == "auto":
         args.table = "1,3,5,7" if world == 1 and args.device == "cuda" else ""
@@ -728,6 +767,11 @@ def main(argv=None) -> int:
                                                  fleet_env, args.warmup, args.steps, args.step_s, sampler,
                                                  device=args.device, server_alive=srv)
     mix = mix_stats(w, families) if families else None
+    dumped = None
+    if args.dump_outputs:  # written by the pods as they stopped (fleet.stop() waited for them)
+        dumped = sorted(f for f in os.listdir(args.dump_outputs) if f.startswith(f"gpu{local}_") and f.endswith(".npy"))
+        if not dumped:
+            raise RuntimeError(f"--dump-outputs: no pod of GPU {local} wrote its outputs to {args.dump_outputs}")
     bf = None
     if args.extra_bf16_s > 0 and args.dtype != "bf16" and d.cuda and not families:
         wb, ub, _, _, _ = run_fleet(d, launcher, fleet_envs(pod_envs), "bf16", not args.no_graphs, extra_env, 2, 1,
@@ -786,6 +830,7 @@ def main(argv=None) -> int:
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(elapsed / args.steps * 1e3, 3),
         "higher_is_better": True,
         "scaling": "weak",
@@ -827,7 +872,7 @@ def main(argv=None) -> int:
         # the same 10 GB pods on a simulated HYBRID node of this many MI355X (the
         # partitioner picks each GPU's compute/memory mode; 8 HWS process slots per
         # partition): simulation, not hardware -- the pool cannot switch modes
-        "schedulable_10gb_pods_per_node_hybrid_sim": hyb10["schedulable_fractional_pods_per_node"],
+        "schedulable_10gb_pods_per_node_hybrid_sim": hyb10.get("schedulable_fractional_pods_per_node"),
         "hybrid_sim_modes": hyb10.get("modes"),
         "aggregate_inf_per_s": round(agg, 3),
         "aggregate_inf_per_s_vs_baseline": round(agg / (BASELINE_INF_PER_S_PER_GPU * world), 2),
@@ -872,6 +917,7 @@ def main(argv=None) -> int:
         "tenant_mix": mix,
         "rank0_ref_pod": ref,
         "pods_ready_s": round(ready_s, 1),
+        "rank0_dumped_outputs": dumped,
         "control_plane": cp,
     }
     if sampler and sampler.err:

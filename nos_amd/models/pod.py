@@ -202,11 +202,14 @@ class _ServerTenant:
     """A pod on a pod-server slice: its inferences run in the GPU's pod server
     (nos_amd/podserver); this process never opens the GPU."""
 
-    def __init__(self, client):
-        self.client = client
+    def __init__(self, client, keep_outputs: bool = False):
+        self.client, self.keep_outputs, self.outputs = client, keep_outputs, ()
 
     def launch(self) -> None:
-        self.client.infer()
+        if self.keep_outputs:  # every reply carries the outputs; the last one is what gets dumped
+            self.outputs = self.client.infer(outputs=True)[0]
+        else:
+            self.client.infer()
 
     def synchronize(self) -> None:  # infer() returns when the server's replay has finished
         pass
@@ -214,13 +217,35 @@ class _ServerTenant:
 
 class _CpuTenant:
     def __init__(self, model, x):
-        self.model, self.x = model, x
+        self.model, self.x, self.outputs = model, x, ()
 
     def launch(self) -> None:
-        self.model(self.x)
+        self.outputs = self.model(self.x)
 
     def synchronize(self) -> None:
         pass
+
+
+ENV_DUMP_OUTPUTS = "NOS_AMD_POD_DUMP_OUTPUTS"      # path prefix of the pod's output files (bench.py --dump-outputs)
+ENV_DUMP_MAX_BYTES = "NOS_AMD_POD_DUMP_MAX_BYTES"  # this pod's share of the dump's size bound
+
+
+def dump_outputs(prefix: str, slot: int, outputs, max_bytes: int = 0) -> list[str]:
+    """What the pod's last inference returned, one float32
+    ``<prefix>pod<slot>_out<k>.npy`` per output.  An output over its share of
+    ``max_bytes`` is stored as a fixed sample of its flattened values (indices
+    drawn once with seed 0, ascending), the same in every run."""
+    outputs = outputs if isinstance(outputs, (tuple, list)) else (outputs,)
+    paths = []
+    for k, o in enumerate(outputs):
+        a = o if isinstance(o, np.ndarray) else o.detach().float().cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        keep = max_bytes // (4 * len(outputs)) if max_bytes else a.size
+        if a.size > keep:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        paths.append(f"{prefix}pod{slot:02d}_out{k}.npy")
+        np.save(paths[-1], a)
+    return paths
 
 
 def run_pod(status: str, slot: int, out: str, dtype: str = "fp32", graphs: bool = True, seed: int = 0,
@@ -251,7 +276,7 @@ def run_pod(status: str, slot: int, out: str, dtype: str = "fp32", graphs: bool 
                 program, weights = demo_tenant(dtype, seed, small=device == "cuda")
             client = PodClient.from_env(reconnect_s=float(os.environ.get("NOS_AMD_POD_RECONNECT_S", "0")))
             rep = client.register(os.environ.get("NOS_AMD_POD_NAME") or f"pod-{slot}", program, weights)
-            s = t = _ServerTenant(client)
+            s = t = _ServerTenant(client, keep_outputs=bool(os.environ.get(ENV_DUMP_OUTPUTS)))
             for _ in range(warmup):
                 t.launch()
             srv = rep.get("server") or {}
@@ -356,6 +381,9 @@ def _loop(board: StatusBoard, row, slot: int, out: str, t, s, info: dict, orphan
 
         info["max_allocated_gb"] = round(torch.cuda.max_memory_allocated(0) / 2 ** 30, 3)
     info["times"] = times
+    if os.environ.get(ENV_DUMP_OUTPUTS) and times:
+        info["dumped_outputs"] = dump_outputs(os.environ[ENV_DUMP_OUTPUTS], slot, t.outputs,
+                                              int(os.environ.get(ENV_DUMP_MAX_BYTES) or 0))
     Path(out, f"pod-{slot}.json").write_text(json.dumps(info))
     row[0] = STATE_DONE
     return 0

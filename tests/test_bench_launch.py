@@ -55,8 +55,8 @@ def test_trainer_job_that_cannot_form_falls_back_on_every_rank():
 
 @pytest.mark.timeout(600)
 def test_latency_table_rows_are_self_consistent():
-    """bench.py --table: one aligned window per (mode, pods); pods / mean latency == throughput in every row."""
-    cmd = [sys.executable, "bench.py", "--device", "cpu", "--steps", "2", "--warmup", "1", "--step-s", "0.3",
+    """bench.py --full --table: one aligned window per (mode, pods); pods / mean latency == throughput in every row."""
+    cmd = [sys.executable, "bench.py", "--full", "--device", "cpu", "--steps", "2", "--warmup", "1", "--step-s", "0.3",
            "--ref-pod-s", "0", "--extra-bf16-s", "0", "--pods-per-gpu", "2", "--table", "1,3",
            "--table-window-s", "2"]
     r = subprocess.run(cmd, cwd=REPO, env={**os.environ, "OMP_NUM_THREADS": "1"}, capture_output=True, text=True,
@@ -70,6 +70,66 @@ def test_latency_table_rows_are_self_consistent():
     for t in rows:
         assert t["concurrent"] == t["pods"]
         assert t["pods_over_latency"] == pytest.approx(t["inf_per_s"], rel=1e-3)
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_times_the_headline_fleet_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full: no reference pod, bf16 fleet, table or capacity probe;
+    --dump-outputs writes what each pod's last inference returned (here: the
+    tiny CPU tenants on the server's resident all-zero input, checked against
+    the programs' own eager reference).  An extra asked for without --full is
+    refused, not skipped."""
+    import numpy as np
+    import torch
+
+    from nos_amd.models.yolos_program import demo_tenant
+    from nos_amd.podserver import program as PG
+
+    env = {**os.environ, "OMP_NUM_THREADS": "1"}
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--device", "cpu", "--steps", "3", "--warmup", "1", "--step-s",
+           "0.3", "--pods-per-gpu", "2"]
+    r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / "out")], cwd=REPO, env=env, capture_output=True,
+                       text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert d["value"] == 2 and d["steps"] == 3 and d["full"] is False
+    assert d["ms_per_step"] == pytest.approx(300, rel=0.2) and d["window_s"] == pytest.approx(0.9, rel=0.2)
+    for k in ("latency_table", "rank0_ref_pod", "single_pod_inf_per_s", "bf16_gfx950_kernels",
+              "schedulable_fractional_pods_per_node_sim", "schedulable_10gb_pods_per_node_hybrid_sim"):
+        assert d[k] is None, k
+    files = sorted(p.name for p in (tmp_path / "out").iterdir())
+    assert files == d["rank0_dumped_outputs"] == [f"gpu0_pod{s:02d}_out{k}.npy" for s in (0, 1) for k in (0, 1)]
+    for slot in (0, 1):  # pod slot s runs the seed-s tenant
+        prog = PG.parse(*demo_tenant("fp32", slot, small=False))
+        ref = prog.reference(torch.zeros(prog.inputs[0].shape))
+        for k, e in enumerate(ref):
+            a = np.load(tmp_path / "out" / f"gpu0_pod{slot:02d}_out{k}.npy")
+            assert a.dtype == np.float32 and a.shape == tuple(e.shape)
+            np.testing.assert_allclose(a, e.numpy(), rtol=1e-4, atol=1e-6)
+    r = subprocess.run(cmd + ["--table", "1,3"], cwd=REPO, env=env, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
+def test_dumped_outputs_over_their_share_are_a_fixed_sample(tmp_path):
+    """A pod's dump is float32 whatever the model's precision, and an output
+    larger than its share of the size bound is stored as the same sample of
+    its values in every run."""
+    import numpy as np
+    import torch
+
+    from nos_amd.models.pod import dump_outputs
+
+    big = torch.arange(5000, dtype=torch.float32).reshape(50, 100).to(torch.bfloat16)
+    small = np.arange(6, dtype=np.float64).reshape(2, 3)
+    a = [np.load(p) for p in dump_outputs(str(tmp_path / "a_"), 3, (big, small), max_bytes=8 * 1000)]
+    b = [np.load(p) for p in dump_outputs(str(tmp_path / "b_"), 3, (big, small), max_bytes=8 * 1000)]
+    assert (tmp_path / "a_pod03_out0.npy").exists() and (tmp_path / "a_pod03_out1.npy").exists()
+    assert all(x.dtype == np.float32 for x in a) and a[0].shape == (1000,) and a[1].shape == (2, 3)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], small)
+    flat = big.float().numpy().reshape(-1)
+    assert np.isin(a[0], flat).all() and (np.diff(a[0]) >= 0).all()  # the output's own values, in their order
+    whole = np.load(dump_outputs(str(tmp_path / "c_"), 0, big)[0])
+    assert whole.shape == (50, 100) and np.array_equal(whole, big.float().numpy())
 
 
 def test_fold_gpus_maps_every_rank_onto_the_visible_gpus(monkeypatch):

@@ -18,5 +18,5 @@ cd $R
 python3 tools/pmc_summary.py $O --out $O/summary.json > $O/summary.log 2>&1 || { tail -5 $O/summary.log; }
 rm -rf $O/pass1 $O/pass2 $O/pass3
 timeout -k 10 150 python3 tools/pod_once.py --memory-fraction 0.125 --cu-mask 0xffffffff --iters 30 > $O/solo_masked.log 2>&1; tail -1 $O/solo_masked.log
-timeout -k 10 600 python bench.py --steps 10 --warmup 3 --table-modes cumask,shared --extra-bf16-s 0 --json-out $O/bench.json > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
+timeout -k 10 600 python bench.py --full --steps 10 --warmup 3 --table-modes cumask,shared --extra-bf16-s 0 --json-out $O/bench.json > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
 python3 -c "import json;d=json.load(open('$O/bench.json'));print([(r['mode'],r['pods'],r['inf_per_s'],r.get('latency_vs_solo_at_solo_clock'),r.get('umc_util_pct')) for r in d['latency_table']])"
