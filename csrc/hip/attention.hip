@@ -30,6 +30,7 @@
 //  * XCD-aware workgroup -> (batch, head, q-block) map: q-blocks of one
 //    head share an XCD's L2 (K/V of one head = 870 KB at S = 3401).
 #include "common.h"
+#include "lds_pipe.h"
 
 namespace {
 
@@ -48,10 +49,6 @@ __device__ __forceinline__ int vswz(int row) { return ((row >> 1) & 1) << 2; }
 __device__ __forceinline__ float xor32_max(float v) {
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
 __global__ __launch_bounds__(NT, 4) void attn_fwd_d64_kernel(
@@ -104,7 +101,7 @@ __global__ __launch_bounds__(NT, 4) void attn_fwd_d64_kernel(
       kv = kv < Skv ? kv : Skv - 1;
       const unsigned short* src = (is_v ? vb_ptr : kb_ptr) + (long long)kv * ld_in + lc * 8;
       unsigned char* dst = smem + buf * PAIR_BYTES + g * 2 * TILE_BYTES + is_v * TILE_BYTES + (R & 63) * 128;
-      glds16(src, dst);
+      nos::glds16_builtin(src, dst);
     }
   };
 

@@ -29,6 +29,7 @@
 //    exceeds it by more than 8 (log2 units), so O and l are rescaled rarely;
 //  * XCD-aware workgroup order: the q-blocks of one head share an XCD's L2.
 #include "common.h"
+#include "lds_pipe.h"
 
 namespace {
 
@@ -49,22 +50,8 @@ __device__ __forceinline__ float xor32_sum(float v) {
 __device__ __forceinline__ int kswz(int row) { return row & 15; }
 __device__ __forceinline__ int vswz(int row) { return ((row >> 2) & 1) << 3; }
 
-// LDS-DMA as inline asm + explicit vmcnt(0) before the publishing barrier:
-// with the builtin, hipcc drained the next stage's DMA before this stage's
-// LDS reads (attention.hip: glds16)
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-  const unsigned lds = __builtin_amdgcn_readfirstlane(
-      (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds_wave_base);
-  // m0 is an operand ("{m0}"), so the compiler writes it and knows it is live
-  // (a clobbered m0 is undefined behaviour: m0 is a reserved register); the
-  // s_nop is the SALU-write-m0 -> LDS-DMA wait state the compiler cannot see
-  asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "{m0}"(lds) : "memory");
-}
-
-__device__ __forceinline__ void dma_wait_publish() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-}
+using nos::dma_wait_publish;
+using nos::glds16;  // the asm form: the next stage stays in flight under this stage's LDS reads
 
 // G = 2: two groups of W waves walk interleaved key tiles of the same
 // (batch, head, q-block) and merge (m, l, O) through LDS at the end -- two

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lds_pipe.h"
 #include "split_bf16.h"
 #include "split_f16.h"
 
@@ -61,36 +62,14 @@ __device__ __forceinline__ float xor32_sum(float v) {
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-// LDS-DMA of 16 bytes per lane issued as inline asm: with the builtin, hipcc
-// assumes every ds_read may alias an in-flight LDS-DMA and inserts
-// s_waitcnt vmcnt(0) before the first LDS read after the issue -- draining
-// the NEXT tile's loads before the CURRENT tile's math (seen in the ISA: one
-// L2/HBM round trip per tile).  The ring is ordered by the explicit
-// vmcnt(0) + barrier that ends each tile (dma_wait_publish).
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-  const unsigned lds = __builtin_amdgcn_readfirstlane(
-      (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds_wave_base);
-  // m0 is an operand ("{m0}"), so the compiler writes it and knows it is live
-  // (a clobbered m0 is undefined behaviour: m0 is a reserved register); the
-  // s_nop is the SALU-write-m0 -> LDS-DMA wait state the compiler cannot see
-  asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "{m0}"(lds) : "memory");
-}
+// the asm LDS-DMA: the next tile's loads stay in flight under the current
+// tile's math; the ring is ordered by the vmcnt(0) + barrier that ends each
+// tile (dma_wait_publish)
+using nos::dma_wait_publish;
+using nos::glds16;
+using nos::glds16_s;
 
-// LDS-DMA from a wave-uniform tile base (SGPR pair) plus a per-lane 32-bit byte
-// offset: the steady-state tiles need no 64-bit VALU address arithmetic
-__device__ __forceinline__ void glds16_s(const void* sbase, unsigned voff, unsigned char* lds_wave_base) {
-  const unsigned lds = __builtin_amdgcn_readfirstlane(
-      (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds_wave_base);
-  asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "{m0}"(lds) : "memory");
-}
-
-// every DMA this wave issued has landed, then the workgroup barrier publishes them
-__device__ __forceinline__ void dma_wait_publish() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-
-// the same with the newest N DMAs left in flight (a deeper ring): a counted
+// dma_wait_publish with the newest N DMAs left in flight (a deeper ring): a counted
 // vmcnt and a raw barrier -- __syncthreads() would drain them (vmcnt(0))
 template <int N>
 __device__ __forceinline__ void dma_wait_publish_keep(bool keep) {

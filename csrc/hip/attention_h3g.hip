@@ -36,6 +36,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "lds_pipe.h"
 #include "split_f16.h"
 
 namespace {
@@ -61,26 +62,9 @@ __device__ __forceinline__ float xor32_sum(float v) {
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-// LDS-DMA of 16 bytes per lane as inline asm (see attention_f32x.hip: the
-// builtin makes hipcc drain in-flight tiles before every LDS read)
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-  const unsigned lds = __builtin_amdgcn_readfirstlane(
-      (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds_wave_base);
-  asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "{m0}"(lds) : "memory");
-}
-
-// LDS-DMA from a wave-uniform tile base (SGPR pair) plus a per-lane 32-bit byte
-// offset: the steady-state tiles need no 64-bit VALU address arithmetic
-__device__ __forceinline__ void glds16_s(const void* sbase, unsigned voff, unsigned char* lds_wave_base) {
-  const unsigned lds = __builtin_amdgcn_readfirstlane(
-      (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds_wave_base);
-  asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "{m0}"(lds) : "memory");
-}
-
-__device__ __forceinline__ void dma_wait_publish() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-}
+using nos::dma_wait_publish;
+using nos::glds16;  // the asm form: in-flight tiles are not drained before every LDS read
+using nos::glds16_s;
 
 // ---------------------------------------------------------------- 1. absmax
 // part[(bh * nchunk + chunk) * 2 + (0: K, 1: V)] = max |x| over the chunk's rows

@@ -29,12 +29,11 @@
 #include <math.h>
 
 #include "common.h"
+#include "epilogue.h"
 
 namespace {
 
-enum : int { EPI_BIAS = 1, EPI_GELU = 2, EPI_RESID = 4, EPI_RELU = 8, EPI_SILU = 64, EPI_GLU = 256 };
-// EPI_GLU (GEMV): W = [gate; up] (2 Nh rows), y [M, Nh] = silu(x . gate_n) * (x . up_n) -- SwiGLU
-// in the merged gate-up GEMV's epilogue, each wave's two columns being n and n + Nh
+// EPI_GLU (epilogue.h): SwiGLU in the merged gate-up GEMV's epilogue, each wave's two columns being n and n + Nh
 
 __device__ __forceinline__ float ldf(const void* p, long long i, int bf) {
   return bf ? nos::bf16_to_f32(static_cast<const unsigned short*>(p)[i]) : static_cast<const float*>(p)[i];

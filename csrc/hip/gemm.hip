@@ -35,7 +35,9 @@
 //    XCD-aware tile order so tiles sharing the larger operand panel share an
 //    XCD's L2.
 #include "common.h"
+#include "epilogue.h"
 #include "gemm_tiles.h"
+#include "lds_pipe.h"
 
 namespace {
 
@@ -78,7 +80,6 @@ using CfgNarrow = Cfg<128, 64, 2, 2>;
 using CfgBig = Cfg<256, 256, 2, 4>;
 using CfgWide = Cfg<256, 192, 4, 2>;  // N = 384 in two tiles, 256-row panels: one round on 256 CUs
 
-enum : int { EPI_BIAS = 1, EPI_GELU = 2, EPI_RESID = 4, EPI_RELU = 8 };
 // Tile policy (process-wide, nos_gemm_set_policy), see pick_tile():
 //  * 0 = throughput (default): least padded work over 128x128 / 256x192 /
 //    256x256 tiles -- what fractional pods sharing a GPU want (8 co-running
@@ -94,10 +95,6 @@ int g_persist = 0;
 
 int num_cus() { return nos_effective_cus(); }  // a CU-slice tenant plans for its budget
 
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 // Stage a [ROWS][BK] bf16 K-slice: ROWS/RPI wave-instructions, spread over NW waves.
 template <int ROWS, int NW, int BK>
 __device__ __forceinline__ void stage_tile(const unsigned short* __restrict__ src, int ld, int row0,
@@ -112,40 +109,13 @@ __device__ __forceinline__ void stage_tile(const unsigned short* __restrict__ sr
     const int lc = pc ^ L::swz(row);
     int grow = row0 + row;
     grow = grow < nrows ? grow : nrows - 1;
-    glds16(src + (long long)grow * ld + k0 + lc * 8, tile + R * L::RB);
+    nos::glds16_builtin(src + (long long)grow * ld + k0 + lc * 8, tile + R * L::RB);
   }
 }
 
-// s_waitcnt vmcnt(n * LPS) for a runtime n in [0, 3]: the immediate must be a constant
-template <int LPS>
-__device__ __forceinline__ void wait_stages(int n) {
-  if (n <= 0)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if (n == 1)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");
-  else if (n == 2)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPS) : "memory");
-  else
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * LPS) : "memory");
-}
+using nos::wait_stages;
 
-// erf(x) for GELU: Abramowitz & Stegun 7.1.26 (|err| <= 1.5e-7, far below
-// bf16 output precision) -- one exp + one rcp instead of the libm erff.
-__device__ __forceinline__ float erf_fast(float x) {
-  const float ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.f));
-  float p = fmaf(1.061405429f, t, -1.453152027f);
-  p = fmaf(p, t, 1.421413741f);
-  p = fmaf(p, t, -0.284496736f);
-  p = fmaf(p, t, 0.254829592f);
-  const float e = __builtin_amdgcn_exp2f(-ax * ax * 1.4426950408889634f);
-  const float r = fmaf(-p * t, e, 1.f);
-  return copysignf(r, x);
-}
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erf_fast(x * 0.70710678118654752f)); }
-
-// the same GELU on a register pair: the polynomial runs as packed-f32 FMAs
+// nos::gelu_erf (epilogue.h) on a register pair: the polynomial runs as packed-f32 FMAs
 // (v_pk_fma_f32 / v_pk_mul_f32, two columns per VALU op); rcp and exp stay
 // per element on the transcendental unit
 __device__ __forceinline__ f32x2_t gelu_erf2(f32x2_t x) {

@@ -24,19 +24,16 @@
 //    per register; LayerNorm row statistics are accumulated from the A tiles
 //    already in LDS (no second pass over A).
 #include "common.h"
+#include "epilogue.h"
+#include "lds_pipe.h"
 
 namespace {
 
 constexpr int BK = 32;              // fp32 per stage row chunk = 128 B
 constexpr int NT = 256;
 constexpr int ROWB = BK * 4;        // 128 B per staged row
-enum : int { EPI_BIAS = 1, EPI_GELU = 2, EPI_RESID = 4, EPI_RELU = 8 };
 
 __device__ __forceinline__ int swz(int row) { return row & 7; }
-
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 // [ROWS][32 k] fp32 tile: ROWS/8 wave-instructions spread over the 4 waves
 template <int ROWS>
@@ -50,19 +47,8 @@ __device__ __forceinline__ void stage_tile(const float* __restrict__ src, int ld
     const int lc = (lane & 7) ^ swz(row);
     int grow = row0 + row;
     grow = grow < nrows ? grow : nrows - 1;
-    glds16(src + (long long)grow * ld + k0 + lc * 4, tile + R * ROWB);
+    nos::glds16_builtin(src + (long long)grow * ld + k0 + lc * 4, tile + R * ROWB);
   }
-}
-
-__device__ __forceinline__ float erf_fast(float x) {  // Abramowitz-Stegun 7.1.26, |err| <= 1.5e-7
-  const float ax = fabsf(x);
-  const float t = 1.f / fmaf(0.3275911f, ax, 1.f);
-  float p = fmaf(1.061405429f, t, -1.453152027f);
-  p = fmaf(p, t, 1.421413741f);
-  p = fmaf(p, t, -0.284496736f);
-  p = fmaf(p, t, 0.254829592f);
-  const float r = fmaf(-p * t, expf(-ax * ax), 1.f);
-  return copysignf(r, x);
 }
 
 // PERSIST: the slice-sized-grid instantiation (a chunk of tiles per
@@ -209,7 +195,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_f32_kernel(
         float v = acc[i][j][r];
         if constexpr (LN) v = fmaf(s_rstd[rl], v - s_mu[rl] * p1, p2);
         else v += p2;
-        if (epi & EPI_GELU) v = 0.5f * v * (1.f + erf_fast(v * 0.70710678118654752f));
+        if (epi & EPI_GELU) v = 0.5f * v * (1.f + nos::erf_ieee(v * 0.70710678118654752f));
         if (epi & EPI_RELU) v = fmaxf(v, 0.f);
         if (m < M && n < N) {
           if (epi & EPI_RESID) v += R[(long long)m * ldr + n];

@@ -26,19 +26,21 @@
 #include <type_traits>
 
 #include "common.h"
+#include "epilogue.h"
+#include "lds_pipe.h"
 #include "split_f16.h"
 
 namespace {
 
-enum : int { EPI_BIAS = 1, EPI_GELU = 2, EPI_RESID = 4, EPI_RELU = 8, EPI_BIAS_ROW = 16, EPI_RESID_PRE = 32,
-             EPI_WIDE = 128 };
+using nos::gelu_erf;
+using nos::glds16;  // the asm form: later stages stay in flight across the fragment reads
+using nos::wait_stages;
+
 // EPI_WIDE (set by the host, stripped on entry): interior tiles written as
 // fp16 planes go through LDS and leave as 16-byte row stores (8 per plane
 // row chunk) instead of one 2-byte store per element and plane
 template <int E>
 using EpiC = std::integral_constant<int, E>;
-// EPI_RESID adds R after the activation (transformer residuals); EPI_RESID_PRE
-// before it (ResNet: relu(conv + bn + identity))
 
 // batched GEMMs (nos_gemm_f32h3_batched): per-batch element strides of every
 // operand (0 = shared by the whole batch, e.g. a conv weight); the tile index
@@ -55,41 +57,6 @@ constexpr int BK = 32;  // K granule of the API (K % 32 == 0); stages are BKT = 
 // logical chunk of 16 consecutive rows hit 16 distinct 16-byte slots
 template <int CH>
 __device__ __forceinline__ int swz(int row) { return CH == 4 ? ((row >> 2) & 3) : ((row >> 3) & 1); }
-
-// s_waitcnt vmcnt(n * LPS) for a runtime n in [0, 3]
-template <int LPS>
-__device__ __forceinline__ void wait_stages(int n) {
-  if (n <= 0)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if (n == 1)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");
-  else if (n == 2)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPS) : "memory");
-  else
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * LPS) : "memory");
-}
-
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-  const unsigned lds = __builtin_amdgcn_readfirstlane(
-      (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds_wave_base);
-  asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "{m0}"(lds) : "memory");
-}
-
-// Abramowitz-Stegun 7.1.26, |err| <= 1.5e-7, on the hardware reciprocal and
-// exp2 (v_rcp_f32 / v_exp_f32, ~1 ulp each): an IEEE division and expf's
-// range reduction cost ~15 more VALU per element, and fc1's GELU epilogue is
-// the largest VALU block of the h3 GEMMs
-__device__ __forceinline__ float erf_fast(float x) {
-  const float ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.f));
-  float p = fmaf(1.061405429f, t, -1.453152027f);
-  p = fmaf(p, t, 1.421413741f);
-  p = fmaf(p, t, -0.284496736f);
-  p = fmaf(p, t, 0.254829592f);
-  const float e = __builtin_amdgcn_exp2f(-ax * ax * 1.4426950408889634f);  // exp(-x^2); 0 past |x| ~ 10
-  const float r = fmaf(-p * t, e, 1.f);
-  return copysignf(r, x);
-}
 
 // the K / V columns (>= qcols) of a fused QKV projection as the h3
 // attention's planes kvs[b][s][K hi, K lo, V hi, V lo][hd], each head on
@@ -461,7 +428,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
             for (int r = 0; r < 16; ++r) {
               const int rl = wm * (BM / WGM) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
               float v = fmaf(acc[i][j][r], rsv[i][r] * cs, p2);
-              if (has(EPI_GELU)) v = 0.5f * v * (1.f + erf_fast(v * 0.70710678118654752f));
+              if (has(EPI_GELU)) v = gelu_erf(v);
               if (has(EPI_RELU)) v = fmaxf(v, 0.f);
               T[rl * BN + cl] = v;
             }
@@ -561,7 +528,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
             for (int r = 0; r < 16; ++r) {
               const int rl = wm * (BM / WGM) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
               float v = fmaf(acc[i][j][r], rsv[i][r] * cs, p2 + rbv[i][r]);
-              if (has(EPI_GELU)) v = 0.5f * v * (1.f + erf_fast(v * 0.70710678118654752f));
+              if (has(EPI_GELU)) v = gelu_erf(v);
               if (has(EPI_RELU)) v = fmaxf(v, 0.f);
               const float x = v * osc;
               const _Float16 h0 = (_Float16)x;
@@ -609,7 +576,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
               const int rl = wm * (BM / WGM) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
               float v = fmaf(acc[i][j][r], rsv[i][r] * cs, p2 + rbv[i][r]);
               if (BATCHED && has(EPI_RESID_PRE)) v += Rt[(unsigned)(rl * ldr + cl)];
-              if (has(EPI_GELU)) v = 0.5f * v * (1.f + erf_fast(v * 0.70710678118654752f));
+              if (has(EPI_GELU)) v = gelu_erf(v);
               if (has(EPI_RELU)) v = fmaxf(v, 0.f);
               if (has(EPI_RESID)) v += Rt[(unsigned)(rl * ldr + cl)];
               Ct[(unsigned)(rl * ldc + cl)] = v;
@@ -655,7 +622,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
           const int m = m0 + wm * (BM / WGM) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
           float v = fmaf(acc[i][j][r], rsv[i][r] * cs, p2 + rbv[i][r]);
           if (BATCHED && (epi & EPI_RESID_PRE) && m < M && n < N) v += Rb[(long long)m * ldr + n];
-          if ((epi & EPI_GELU)) v = 0.5f * v * (1.f + erf_fast(v * 0.70710678118654752f));
+          if ((epi & EPI_GELU)) v = gelu_erf(v);
           if ((epi & EPI_RELU)) v = fmaxf(v, 0.f);
           if (m < M && n < N) {
             if ((epi & EPI_RESID)) v += Rb[(long long)m * ldr + n];
@@ -703,33 +670,53 @@ bool wide_planes_ok(const KvOut& kv, const PlaneOut& po) {
   return false;
 }
 
+// one GEMM as the host entry points hand it to launch_t: gemm_h3_kernel's
+// arguments by name (A is the planes a, or under MODE 1 the fp32 rows ln.x)
+struct H3Call {
+  const _Float16* a = nullptr;  // A planes [2][M][lda], plane stride aplane
+  int lda = 0;
+  long long aplane = 0;
+  const float* rinv = nullptr;  // row scales, or nullptr: rconst for every row
+  float rconst = 0.f;
+  const _Float16* w = nullptr;  // W planes [2][N][ldw], plane stride wplane
+  int ldw = 0;
+  long long wplane = 0;
+  const float* csc = nullptr;
+  const float* bias = nullptr;
+  const float* R = nullptr;
+  int ldr = 0;
+  float* C = nullptr;
+  int ldc = 0;
+  int M = 0, N = 0, K = 0, epi = 0;
+  KvOut kv;
+  PlaneOut po;
+  Batch bt;
+  LnIo ln;
+};
+
 template <int BM, int BN, int WGM, int WGN, int BKT = 32, int RS = 2, bool BATCHED = false, int MODE = 0>
-int launch_t(const _Float16* Ap, int lda, long long aplane, const float* rinv, float rconst, const _Float16* Wp,
-             int ldw, long long wplane, const float* csc, const float* bias, const float* R, int ldr, float* C, int ldc,
-             int M, int N, int K, int epi, KvOut kv, PlaneOut po, Batch bt, hipStream_t st, LnIo ln = LnIo{}) {
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const long long ntiles = (long long)tiles_m * tiles_n * bt.nb;
+int launch_t(const H3Call& c, hipStream_t st) {
+  const int tiles_m = (c.M + BM - 1) / BM, tiles_n = (c.N + BN - 1) / BN;
+  const long long ntiles = (long long)tiles_m * tiles_n * c.bt.nb;
   if (ntiles > (1LL << 30)) return (int)hipErrorInvalidValue;
   const size_t lds = RS * (size_t)(2 * BM * BKT * 2 + 2 * BN * BKT * 2);
   constexpr int NT = 64 * WGM * WGN;
-  if (!BATCHED && wide_planes_ok(kv, po)) epi |= EPI_WIDE;
+  const int epi = !BATCHED && wide_planes_ok(c.kv, c.po) ? c.epi | EPI_WIDE : c.epi;
+  auto launch = [&](auto* kernel, long long grid) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(NT), lds, st, c.a, c.lda, c.aplane, c.rinv, c.rconst, c.w,
+                       c.ldw, c.wplane, c.csc, c.bias, c.R, c.ldr, c.C, c.ldc, c.M, c.N, c.K, epi, tiles_m, tiles_n,
+                       c.kv, c.po, c.bt, c.ln);
+    return (int)hipGetLastError();
+  };
   // batched GEMMs always launch one workgroup per tile: their persistent
   // form (a CU slice's capped grid) needs 21 more VGPRs than 256 and spilled
   // to scratch; the CU mask bounds where the tiles run either way
   if constexpr (!BATCHED) {
-    const int grid =
-        nos_grid_for((const void*)gemm_h3_kernel<BM, BN, WGM, WGN, true, BKT, RS, MODE, BATCHED>, NT, lds, ntiles);
-    if (grid < ntiles) {
-      hipLaunchKernelGGL((gemm_h3_kernel<BM, BN, WGM, WGN, true, BKT, RS, MODE, BATCHED>), dim3((unsigned)grid),
-                         dim3(NT), lds, st, Ap, lda, aplane, rinv, rconst, Wp, ldw, wplane, csc, bias, R, ldr, C, ldc,
-                         M, N, K, epi, tiles_m, tiles_n, kv, po, bt, ln);
-      return (int)hipGetLastError();
-    }
+    auto* persistent = gemm_h3_kernel<BM, BN, WGM, WGN, true, BKT, RS, MODE, BATCHED>;
+    const int grid = nos_grid_for((const void*)persistent, NT, lds, ntiles);
+    if (grid < ntiles) return launch(persistent, grid);
   }
-  hipLaunchKernelGGL((gemm_h3_kernel<BM, BN, WGM, WGN, false, BKT, RS, MODE, BATCHED>), dim3((unsigned)ntiles),
-                     dim3(NT), lds, st, Ap, lda, aplane, rinv, rconst, Wp, ldw, wplane, csc, bias, R, ldr, C, ldc, M, N,
-                     K, epi, tiles_m, tiles_n, kv, po, bt, ln);
-  return (int)hipGetLastError();
+  return launch(gemm_h3_kernel<BM, BN, WGM, WGN, false, BKT, RS, MODE, BATCHED>, ntiles);
 }
 
 // nos_gemm_f32h3_set_layout: 0: 128x128, 4 x 1 waves; 1: 128x128, 2 x 2;
@@ -1043,51 +1030,103 @@ NOS_API int nos_split_cols_h3(const float* X, int ldx, long long bsx, int M, int
 
 namespace {
 
+// fp32 C alone, C and R in rows of float4: what MODE 2's epilogue stores and loads
+bool lds_epilogue_ok(const H3Call& c) {
+  return c.kv.kvs == nullptr && c.po.p == nullptr && c.C != nullptr && !(c.N % 4) && !(c.ldc % 4) &&
+         !(((uintptr_t)c.C) & 15) && (!(c.epi & EPI_RESID) || (!(c.ldr % 4) && !(((uintptr_t)c.R) & 15)));
+}
+
+// the LDS-epilogue / row-statistics GEMMs (MODE 2) on the tile and ring of
+// nos_gemm_f32h3_set_hot_bn / nos_gemm_f32h3_set_hot_ring
+int launch_hot(const H3Call& c, hipStream_t st) {
+  if (g_hot_bn == 64) return launch_t<128, 64, 2, 2, 32, 2, false, 2>(c, st);
+  if (g_hot_ring == 3) return launch_t<128, 128, 2, 2, 32, 3, false, 2>(c, st);
+  return launch_t<128, 128, 2, 2, 32, 2, false, 2>(c, st);
+}
+
 // batched: the BATCHED instantiation (batch strides, per-row bias, residual
 // before the activation -- kept out of the one-GEMM kernels' registers)
-int run_h3(const void* Ap, int lda, long long aplane, const float* rinv, float rconst, const void* Wp, int ldw,
-           long long wplane, const float* csc, const float* bias, const float* R, int ldr, float* C, int ldc, int M,
-           int N, int K, int epi, KvOut kv, PlaneOut po, Batch bt, hipStream_t stream, bool batched = false) {
-  const auto* a = static_cast<const _Float16*>(Ap);
-  const auto* w = static_cast<const _Float16*>(Wp);
-  if (batched)  // batched GEMMs (convs, matmuls) on the default 128x128, 2 x 2 layout
-    return launch_t<128, 128, 2, 2, 32, 2, true>(a, lda, aplane, rinv, rconst, w, ldw, wplane, csc, bias, R, ldr, C,
-                                                 ldc, M, N, K, epi, kv, po, bt, stream);
-  if (g_layout == 3)
-    return launch_t<128, 128, 4, 1, 32, 3>(a, lda, aplane, rinv, rconst, w, ldw, wplane, csc, bias, R, ldr, C, ldc, M,
-                                           N, K, epi, kv, po, bt, stream);
-  if (g_layout == 4)
-    return launch_t<128, 128, 4, 1, 16, 4>(a, lda, aplane, rinv, rconst, w, ldw, wplane, csc, bias, R, ldr, C, ldc, M,
-                                           N, K, epi, kv, po, bt, stream);
-  if (g_layout == 5)
-    return launch_t<128, 128, 2, 2, 16, 4>(a, lda, aplane, rinv, rconst, w, ldw, wplane, csc, bias, R, ldr, C, ldc, M,
-                                           N, K, epi, kv, po, bt, stream);
-  if (g_layout == 7)  // 128 x 64 tiles (48 KiB ring: three workgroups per CU)
-    return launch_t<128, 64, 2, 2>(a, lda, aplane, rinv, rconst, w, ldw, wplane, csc, bias, R, ldr, C, ldc, M, N, K,
-                                   epi, kv, po, bt, stream);
-  if (g_layout == 6)
-    return launch_t<128, 128, 2, 2, 32, 3>(a, lda, aplane, rinv, rconst, w, ldw, wplane, csc, bias, R, ldr, C, ldc, M,
-                                           N, K, epi, kv, po, bt, stream);
-  if (g_layout == 2)
-    return launch_t<256, 128, 4, 2>(a, lda, aplane, rinv, rconst, w, ldw, wplane, csc, bias, R, ldr, C, ldc, M, N, K,
-                                    epi, kv, po, bt, stream);
-  if (g_layout == 1) {
-    if (g_lds_epi && kv.kvs == nullptr && po.p == nullptr && C != nullptr && !(N % 4) && !(ldc % 4) &&
-        !(((uintptr_t)C) & 15) && (!(epi & EPI_RESID) || (!(ldr % 4) && !(((uintptr_t)R) & 15)))) {
-      if (g_hot_bn == 64)
-        return launch_t<128, 64, 2, 2, 32, 2, false, 2>(a, lda, aplane, rinv, rconst, w, ldw, wplane, csc, bias, R,
-                                                        ldr, C, ldc, M, N, K, epi, kv, po, bt, stream);
-      if (g_hot_ring == 3)
-        return launch_t<128, 128, 2, 2, 32, 3, false, 2>(a, lda, aplane, rinv, rconst, w, ldw, wplane, csc, bias, R,
-                                                         ldr, C, ldc, M, N, K, epi, kv, po, bt, stream);
-      return launch_t<128, 128, 2, 2, 32, 2, false, 2>(a, lda, aplane, rinv, rconst, w, ldw, wplane, csc, bias, R, ldr,
-                                                       C, ldc, M, N, K, epi, kv, po, bt, stream);
-    }
-    return launch_t<128, 128, 2, 2>(a, lda, aplane, rinv, rconst, w, ldw, wplane, csc, bias, R, ldr, C, ldc, M, N, K,
-                                    epi, kv, po, bt, stream);
+int run_h3(const H3Call& c, hipStream_t st, bool batched = false) {
+  if (batched) return launch_t<128, 128, 2, 2, 32, 2, true>(c, st);  // convs, matmuls: the default layout
+  switch (g_layout) {  // nos_gemm_f32h3_set_layout
+    case 3: return launch_t<128, 128, 4, 1, 32, 3>(c, st);
+    case 4: return launch_t<128, 128, 4, 1, 16, 4>(c, st);
+    case 5: return launch_t<128, 128, 2, 2, 16, 4>(c, st);
+    case 7: return launch_t<128, 64, 2, 2>(c, st);  // 48 KiB ring: three workgroups per CU
+    case 6: return launch_t<128, 128, 2, 2, 32, 3>(c, st);
+    case 2: return launch_t<256, 128, 4, 2>(c, st);
+    case 1: return g_lds_epi && lds_epilogue_ok(c) ? launch_hot(c, st) : launch_t<128, 128, 2, 2>(c, st);
+    default: return launch_t<128, 128, 4, 1>(c, st);
   }
-  return launch_t<128, 128, 4, 1>(a, lda, aplane, rinv, rconst, w, ldw, wplane, csc, bias, R, ldr, C, ldc, M, N, K,
-                                  epi, kv, po, bt, stream);
+}
+
+// K columns of an operand's fp16 planes [2][rows][ld] (plane stride `plane`), rows of 16-byte chunks
+bool planes_ok(const void* p, int ld, long long plane, int rows, int K) {
+  return !(ld % 8) && ld >= K && plane >= (long long)rows * ld && !(((uintptr_t)p) & 15);
+}
+
+// the epilogue flags with the operands they need; `refused`: the flags this entry point does not take
+bool epi_ok(int epi, int refused, const float* bias, const float* R, int ldr, int N) {
+  const int b = epi & (EPI_BIAS | EPI_BIAS_ROW), r = epi & (EPI_RESID | EPI_RESID_PRE);
+  if ((epi & refused) || b == (EPI_BIAS | EPI_BIAS_ROW) || r == (EPI_RESID | EPI_RESID_PRE)) return false;
+  return (!b || bias) && (!r || (R && ldr >= N));
+}
+
+// The argument checks of the entry points, each filling its part of the call;
+// false: rejected (hipErrorInvalidValue, before any HIP call).
+// What all four share: the shape, W's planes and scales, the epilogue operands.
+bool fill_common(H3Call& c, const void* Wp, int ldw, long long wplane, const float* csc, const float* bias,
+                 const float* R, int ldr, float* C, int ldc, int M, int N, int K, int epi, int refused) {
+  if (M <= 0 || N <= 0 || K <= 0 || (K % BK) != 0) return false;
+  if (!planes_ok(Wp, ldw, wplane, N, K) || !csc || !epi_ok(epi, refused, bias, R, ldr, N)) return false;
+  c.w = static_cast<const _Float16*>(Wp);
+  c.ldw = ldw;
+  c.wplane = wplane;
+  c.csc = csc;
+  c.bias = bias;
+  c.R = R;
+  c.ldr = ldr;
+  c.C = C;
+  c.ldc = ldc;
+  c.M = M;
+  c.N = N;
+  c.K = K;
+  c.epi = epi;
+  return true;
+}
+
+// A as planes with their row scales (after fill_common)
+bool fill_a_planes(H3Call& c, const void* Ap, int lda, long long aplane, const float* rinv, float rconst) {
+  if (!planes_ok(Ap, lda, aplane, c.M, c.K) || (!rinv && !(rconst > 0.f))) return false;
+  c.a = static_cast<const _Float16*>(Ap);
+  c.lda = lda;
+  c.aplane = aplane;
+  c.rinv = rinv;
+  c.rconst = rconst;
+  return true;
+}
+
+// the outputs (after fill_common): K / V planes next to Q in C (kvs), or the
+// next GEMM's A planes instead of C (P), or fp32 C alone
+bool fill_outputs(H3Call& c, void* kvs, int S, int skvp, const float* kvsc, void* P, int ldp, long long pplane,
+                  float psc) {
+  const int M = c.M, N = c.N;
+  if (kvs != nullptr) {
+    if (!kvsc || N % 3 || (N / 3) % 64 || S <= 0 || M % S || skvp < S || (((uintptr_t)kvs) & 15) || P) return false;
+    c.kv.kvs = static_cast<unsigned short*>(kvs);
+    c.kv.kvsc = kvsc;
+    c.kv.hd = N / 3;
+    c.kv.qcols = c.kv.hd;
+    c.kv.S = S;
+    c.kv.skvp = skvp;
+  }
+  if (P == nullptr) return c.ldc >= (kvs != nullptr ? N / 3 : N);
+  if (ldp < N || pplane < (long long)M * ldp || !(psc > 0.f)) return false;
+  c.po.p = static_cast<unsigned short*>(P);
+  c.po.ldp = ldp;
+  c.po.pplane = pplane;
+  c.po.sc = psc;
+  return true;
 }
 
 }  // namespace
@@ -1105,36 +1144,11 @@ NOS_API int nos_gemm_f32h3(const void* Ap, int lda, long long aplane, const floa
                            const float* R, int ldr, float* C, int ldc, int M, int N, int K, int epi, void* kvs, int S,
                            int skvp, const float* kvsc, void* P, int ldp, long long pplane, float psc,
                            hipStream_t stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || (K % BK) != 0) return (int)hipErrorInvalidValue;
-  if ((lda % 8) || (ldw % 8) || lda < K || ldw < K || aplane < (long long)M * lda || wplane < (long long)N * ldw)
+  H3Call c;
+  if (!fill_common(c, Wp, ldw, wplane, csc, bias, R, ldr, C, ldc, M, N, K, epi, EPI_RESID_PRE) ||
+      !fill_a_planes(c, Ap, lda, aplane, rinv, rconst) || !fill_outputs(c, kvs, S, skvp, kvsc, P, ldp, pplane, psc))
     return (int)hipErrorInvalidValue;
-  if ((((uintptr_t)Ap) | ((uintptr_t)Wp)) & 15) return (int)hipErrorInvalidValue;
-  if ((!rinv && !(rconst > 0.f)) || !csc || ((epi & EPI_BIAS) && !bias) || ((epi & EPI_RESID) && (!R || ldr < N)))
-    return (int)hipErrorInvalidValue;
-  if (((epi & EPI_BIAS_ROW) && ((epi & EPI_BIAS) || !bias)) || (epi & EPI_RESID_PRE)) return (int)hipErrorInvalidValue;
-  KvOut kv;
-  PlaneOut po;
-  if (kvs != nullptr) {
-    if (!kvsc || N % 3 || (N / 3) % 64 || S <= 0 || M % S || skvp < S || (((uintptr_t)kvs) & 15) || P)
-      return (int)hipErrorInvalidValue;
-    kv.kvs = static_cast<unsigned short*>(kvs);
-    kv.kvsc = kvsc;
-    kv.hd = N / 3;
-    kv.qcols = kv.hd;
-    kv.S = S;
-    kv.skvp = skvp;
-  }
-  if (P != nullptr) {
-    if (ldp < N || pplane < (long long)M * ldp || !(psc > 0.f)) return (int)hipErrorInvalidValue;
-    po.p = static_cast<unsigned short*>(P);
-    po.ldp = ldp;
-    po.pplane = pplane;
-    po.sc = psc;
-  } else if (ldc < (kvs != nullptr ? N / 3 : N)) {
-    return (int)hipErrorInvalidValue;
-  }
-  return run_h3(Ap, lda, aplane, rinv, rconst, Wp, ldw, wplane, csc, bias, R, ldr, C, ldc, M, N, K, epi, kv, po,
-                Batch{}, stream);
+  return run_h3(c, stream);
 }
 
 // nb independent GEMMs C_b = act(rinv_b[m] csc_b[n] (A'_b . W'_b^T) + bias) (+ R_b),
@@ -1150,28 +1164,22 @@ NOS_API int nos_gemm_f32h3_batched(const void* Ap, int lda, long long aplane, lo
                                    long long sw, const float* csc, long long scsc, const float* bias, long long sbias,
                                    const float* R, int ldr, long long sr, float* C, int ldc, long long sc, int M, int N,
                                    int K, int nb, int epi, hipStream_t stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || nb <= 0 || (K % BK) != 0) return (int)hipErrorInvalidValue;
-  if ((lda % 8) || (ldw % 8) || lda < K || ldw < K || aplane < (long long)M * lda || wplane < (long long)N * ldw)
+  H3Call c;
+  if (!fill_common(c, Wp, ldw, wplane, csc, bias, R, ldr, C, ldc, M, N, K, epi, 0) ||
+      !fill_a_planes(c, Ap, lda, aplane, rinv, rconst) || nb <= 0 || !C || ldc < N)
     return (int)hipErrorInvalidValue;
   if (sa < 0 || sw < 0 || srinv < 0 || scsc < 0 || sr < 0 || sc < 0 || sbias < 0 || (sa % 8) || (sw % 8))
     return (int)hipErrorInvalidValue;
-  if ((((uintptr_t)Ap) | ((uintptr_t)Wp)) & 15) return (int)hipErrorInvalidValue;
-  if ((!rinv && !(rconst > 0.f)) || !csc || !C || ldc < N) return (int)hipErrorInvalidValue;
-  if ((epi & (EPI_BIAS | EPI_BIAS_ROW)) == (EPI_BIAS | EPI_BIAS_ROW) || ((epi & (EPI_BIAS | EPI_BIAS_ROW)) && !bias) ||
-      ((epi & (EPI_RESID | EPI_RESID_PRE)) && (!R || ldr < N)) || (epi & EPI_RESID && epi & EPI_RESID_PRE))
-    return (int)hipErrorInvalidValue;
   if (nb > 1 && sc < (long long)(M - 1) * ldc + N) return (int)hipErrorInvalidValue;  // outputs never overlap
-  Batch bt;
-  bt.nb = nb;
-  bt.a = sa;
-  bt.rinv = srinv;
-  bt.w = sw;
-  bt.csc = scsc;
-  bt.c = sc;
-  bt.r = sr;
-  bt.bias = sbias;
-  return run_h3(Ap, lda, aplane, rinv, rconst, Wp, ldw, wplane, csc, bias, R, ldr, C, ldc, M, N, K, epi, KvOut{},
-                PlaneOut{}, bt, stream, true);
+  c.bt.nb = nb;
+  c.bt.a = sa;
+  c.bt.rinv = srinv;
+  c.bt.w = sw;
+  c.bt.csc = scsc;
+  c.bt.c = sc;
+  c.bt.r = sr;
+  c.bt.bias = sbias;
+  return run_h3(c, stream, true);
 }
 
 // nos_gemm_f32h3's plain contract (fp32 C, no KV / plane outputs; N % 4 == 0,
@@ -1183,30 +1191,14 @@ NOS_API int nos_gemm_f32h3_stats(const void* Ap, int lda, long long aplane, cons
                                  const void* Wp, int ldw, long long wplane, const float* csc, const float* bias,
                                  const float* R, int ldr, float* C, int ldc, int M, int N, int K, int epi, void* stats,
                                  hipStream_t stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || (K % BK) != 0 || !C || ldc < N || !stats || (N % 4) || (ldc % 4) ||
-      (((uintptr_t)C) & 15))
+  H3Call c;
+  if (!fill_common(c, Wp, ldw, wplane, csc, bias, R, ldr, C, ldc, M, N, K, epi, EPI_BIAS_ROW | EPI_RESID_PRE) ||
+      !fill_a_planes(c, Ap, lda, aplane, rinv, rconst) || ldc < N || !lds_epilogue_ok(c) || !stats ||
+      (((uintptr_t)stats) & 7))
     return (int)hipErrorInvalidValue;
-  if ((epi & EPI_RESID) && ((ldr % 4) || (((uintptr_t)R) & 15))) return (int)hipErrorInvalidValue;
-  if ((lda % 8) || (ldw % 8) || lda < K || ldw < K || aplane < (long long)M * lda || wplane < (long long)N * ldw)
-    return (int)hipErrorInvalidValue;
-  if ((((uintptr_t)Ap) | ((uintptr_t)Wp)) & 15 || (((uintptr_t)stats) & 7)) return (int)hipErrorInvalidValue;
-  if ((!rinv && !(rconst > 0.f)) || !csc || ((epi & EPI_BIAS) && !bias) || ((epi & EPI_RESID) && (!R || ldr < N)) ||
-      (epi & (EPI_BIAS_ROW | EPI_RESID_PRE)))
-    return (int)hipErrorInvalidValue;
-  LnIo ln;
-  ln.sout = static_cast<float2*>(stats);
-  ln.spart = (N + g_hot_bn - 1) / g_hot_bn;
-  if (g_hot_bn == 64)
-    return launch_t<128, 64, 2, 2, 32, 2, false, 2>(static_cast<const _Float16*>(Ap), lda, aplane, rinv, rconst,
-                                                    static_cast<const _Float16*>(Wp), ldw, wplane, csc, bias, R, ldr,
-                                                    C, ldc, M, N, K, epi, KvOut{}, PlaneOut{}, Batch{}, stream, ln);
-  if (g_hot_ring == 3)
-    return launch_t<128, 128, 2, 2, 32, 3, false, 2>(static_cast<const _Float16*>(Ap), lda, aplane, rinv, rconst,
-                                                     static_cast<const _Float16*>(Wp), ldw, wplane, csc, bias, R, ldr,
-                                                     C, ldc, M, N, K, epi, KvOut{}, PlaneOut{}, Batch{}, stream, ln);
-  return launch_t<128, 128, 2, 2, 32, 2, false, 2>(static_cast<const _Float16*>(Ap), lda, aplane, rinv, rconst,
-                                                   static_cast<const _Float16*>(Wp), ldw, wplane, csc, bias, R, ldr,
-                                                   C, ldc, M, N, K, epi, KvOut{}, PlaneOut{}, Batch{}, stream, ln);
+  c.ln.sout = static_cast<float2*>(stats);
+  c.ln.spart = (N + g_hot_bn - 1) / g_hot_bn;
+  return launch_hot(c, stream);
 }
 
 // C = act(2^-eln csc[n] (LN(X)' . W'^T) + bias) with LN(X)' = (X - mean) rstd
@@ -1221,52 +1213,27 @@ NOS_API int nos_gemm_f32h3_lna(const float* X, int ldx, const void* stats, int n
                                const float* R, int ldr, float* C, int ldc, int M, int N, int K, int epi, void* kvs,
                                int S, int skvp, const float* kvsc, void* P, int ldp, long long pplane, float psc,
                                hipStream_t stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || (K % BK) != 0 || !X || (ldx % 4) || ldx < K || !stats || nparts <= 0 || pw <= 0 ||
-      (long long)nparts * pw < K || (long long)(nparts - 1) * pw >= K)
+  H3Call c;
+  if (!fill_common(c, Wp, ldw, wplane, csc, bias, R, ldr, C, ldc, M, N, K, epi, EPI_BIAS_ROW | EPI_RESID_PRE) ||
+      !fill_outputs(c, kvs, S, skvp, kvsc, P, ldp, pplane, psc) || (!P && !C))
     return (int)hipErrorInvalidValue;
-  if ((ldw % 8) || ldw < K || wplane < (long long)N * ldw || (((uintptr_t)Wp) & 15) || (((uintptr_t)X) & 15) ||
-      (((uintptr_t)stats) & 7))
+  if (!X || (ldx % 4) || ldx < K || (((uintptr_t)X) & 15) || !stats || (((uintptr_t)stats) & 7) || nparts <= 0 ||
+      pw <= 0 || (long long)nparts * pw < K || (long long)(nparts - 1) * pw >= K || !(eps >= 0.f) || eln < -126 ||
+      eln > 126)
     return (int)hipErrorInvalidValue;
-  if (!csc || ((epi & EPI_BIAS) && !bias) || ((epi & EPI_RESID) && (!R || ldr < N)) ||
-      (epi & (EPI_BIAS_ROW | EPI_RESID_PRE)) || !(eps >= 0.f) || eln < -126 || eln > 126)
-    return (int)hipErrorInvalidValue;
-  KvOut kv;
-  PlaneOut po;
-  if (kvs != nullptr) {
-    if (!kvsc || N % 3 || (N / 3) % 64 || S <= 0 || M % S || skvp < S || (((uintptr_t)kvs) & 15) || P)
-      return (int)hipErrorInvalidValue;
-    kv.kvs = static_cast<unsigned short*>(kvs);
-    kv.kvsc = kvsc;
-    kv.hd = N / 3;
-    kv.qcols = kv.hd;
-    kv.S = S;
-    kv.skvp = skvp;
-  }
-  if (P != nullptr) {
-    if (ldp < N || pplane < (long long)M * ldp || !(psc > 0.f)) return (int)hipErrorInvalidValue;
-    po.p = static_cast<unsigned short*>(P);
-    po.ldp = ldp;
-    po.pplane = pplane;
-    po.sc = psc;
-  } else if (!C || ldc < (kvs != nullptr ? N / 3 : N)) {
-    return (int)hipErrorInvalidValue;
-  }
-  LnIo ln;
-  ln.x = X;
-  ln.ldx = ldx;
-  ln.sin = static_cast<const float2*>(stats);
-  ln.nparts = nparts;
-  ln.pw = pw;
-  ln.eps = eps;
-  ln.sc = ldexpf(1.f, eln);
+  c.lda = K;  // no A planes: the kernel's MODE 1 reads ln.x
+  c.aplane = (long long)M * K;
+  c.rconst = ldexpf(1.f, -eln);
+  c.ln.x = X;
+  c.ln.ldx = ldx;
+  c.ln.sin = static_cast<const float2*>(stats);
+  c.ln.nparts = nparts;
+  c.ln.pw = pw;
+  c.ln.eps = eps;
+  c.ln.sc = ldexpf(1.f, eln);
   // 128 x 128 (or 128 x 256 for plane outputs, g_lna_wide): the LN-in-A-load normalises and
   // splits its A tile per workgroup, so 128 x 64 tiles doubled that VALU work (fleet 760 vs
   // 800 inf/s, profiles/r06_hot_bn_ab.json)
-  if (g_lna_wide && P != nullptr)
-    return launch_t<128, 256, 2, 4, 32, 2, false, 1>(nullptr, K, (long long)M * K, nullptr, ldexpf(1.f, -eln),
-                                                     static_cast<const _Float16*>(Wp), ldw, wplane, csc, bias, R, ldr,
-                                                     C, ldc, M, N, K, epi, kv, po, Batch{}, stream, ln);
-  return launch_t<128, 128, 2, 2, 32, 2, false, 1>(nullptr, K, (long long)M * K, nullptr, ldexpf(1.f, -eln),
-                                                   static_cast<const _Float16*>(Wp), ldw, wplane, csc, bias, R, ldr,
-                                                   C, ldc, M, N, K, epi, kv, po, Batch{}, stream, ln);
+  if (g_lna_wide && P != nullptr) return launch_t<128, 256, 2, 4, 32, 2, false, 1>(c, stream);
+  return launch_t<128, 128, 2, 2, 32, 2, false, 1>(c, stream);
 }

@@ -23,11 +23,11 @@
 //    v_mfma_f32_32x32x16_bf16 per 32x32 block and step;
 //  * epilogue and LayerNorm statistics as in gemm_f32.hip.
 #include "common.h"
+#include "epilogue.h"
+#include "lds_pipe.h"
 #include "split_bf16.h"
 
 namespace {
-
-enum : int { EPI_BIAS = 1, EPI_GELU = 2, EPI_RESID = 4, EPI_RELU = 8 };
 
 // LDS images of one K stage of BK (32 or 64): the fp32 A rows (AROW bytes,
 // ACH 16-byte chunks) and the bf16 W plane rows (WROW bytes, WCH chunks),
@@ -40,45 +40,8 @@ struct Lay {
   __device__ static int wswz(int row) { return BK == 32 ? ((row >> 2) & 3) : ((row >> 1) & 7); }
 };
 
-// LDS-DMA of 16 bytes per lane (lane L -> lds_wave_base + 16 L), issued as
-// inline asm: the compiler then does not know the instruction writes LDS and
-// inserts no vmcnt(0) before the next ds_read (hipcc assumes every ds_read may
-// alias an in-flight LDS-DMA, which drained the NEXT stage's loads before the
-// CURRENT stage's fragment reads -- a full L2/HBM round trip per K step).
-// The explicit counted waits (wait_stages) + barrier provide the ordering.
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-  const unsigned lds = __builtin_amdgcn_readfirstlane(
-      (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds_wave_base);
-  // m0 is an operand ("{m0}"), so the compiler writes it and knows it is live
-  // (a clobbered m0 is undefined behaviour: m0 is a reserved register); the
-  // s_nop is the SALU-write-m0 -> LDS-DMA wait state the compiler cannot see
-  asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "{m0}"(lds) : "memory");
-}
-
-__device__ __forceinline__ float erf_fast(float x) {  // Abramowitz-Stegun 7.1.26, |err| <= 1.5e-7
-  const float ax = fabsf(x);
-  const float t = 1.f / fmaf(0.3275911f, ax, 1.f);
-  float p = fmaf(1.061405429f, t, -1.453152027f);
-  p = fmaf(p, t, 1.421413741f);
-  p = fmaf(p, t, -0.284496736f);
-  p = fmaf(p, t, 0.254829592f);
-  const float r = fmaf(-p * t, expf(-ax * ax), 1.f);
-  return copysignf(r, x);
-}
-
-// s_waitcnt vmcnt(n * LPS) for a runtime n in [0, 3] (the immediate must be a constant)
-template <int LPS>
-__device__ __forceinline__ void wait_stages(int n) {
-  if (n <= 0)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if (n == 1)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");
-  else if (n == 2)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPS) : "memory");
-  else
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * LPS) : "memory");
-}
-
+using nos::glds16;  // the asm form: later stages stay in flight across the fragment reads
+using nos::wait_stages;
 
 // Optional second output of the fused-LN QKV projection: columns >= qcols (K
 // then V, hd = H * 64 each) are written as the six bf16 planes the bf16x6
@@ -397,7 +360,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_f3
         float v = acc[i][j][r];
         if constexpr (LN) v = fmaf(s_rstd[rl], v - s_mu[rl] * p1, p2);
         else v += p2;
-        if (epi & EPI_GELU) v = 0.5f * v * (1.f + erf_fast(v * 0.70710678118654752f));
+        if (epi & EPI_GELU) v = 0.5f * v * (1.f + nos::erf_ieee(v * 0.70710678118654752f));
         if (epi & EPI_RELU) v = fmaxf(v, 0.f);
         if (m < M && n < N) {
           if (epi & EPI_RESID) v += R[(long long)m * ldr + n];

@@ -300,22 +300,11 @@ def run_pod(status: str, slot: int, out: str, dtype: str = "fp32", graphs: bool 
             torch.cuda.set_device(0)  # the device plugin's HIP_VISIBLE_DEVICES leaves exactly the slice's GPU
             frac = apply_memory_limit(0)
             torch.backends.cuda.matmul.allow_tf32 = False  # true fp32 GEMMs (no reduced-precision shortcut)
-            from ..ops import (set_attention_f32_variant, set_cu_budget, set_f32_math, set_gemm_f32_policy,
-                               set_gemm_f32h3_hot_bn, set_gemm_f32h3_hot_ring, set_gemm_f32h3_layout,
-                               set_gemm_f32h3_lna_wide, set_gemm_f32x6_tile, set_gemm_policy, set_ln_handoff)
+            from ..ops import apply_kernel_config, set_cu_budget
 
             budget = slice_cu_budget(os.environ)
             cfg = kernel_config(frac, os.environ, budget)
-            set_gemm_policy(cfg["gemm_bf16"])
-            set_gemm_f32_policy(cfg["gemm_f32"])
-            set_attention_f32_variant(cfg["attention_f32"])
-            set_f32_math(cfg["f32_math"])
-            set_gemm_f32x6_tile(cfg["gemm_f32x6_tile"])
-            set_ln_handoff(cfg["ln_handoff"] == "on")
-            set_gemm_f32h3_layout(cfg["h3_layout"])
-            set_gemm_f32h3_hot_ring(int(cfg["h3_hot_ring"]))
-            set_gemm_f32h3_hot_bn(int(cfg["h3_hot_bn"]))
-            set_gemm_f32h3_lna_wide(cfg["h3_lna_wide"] == "on")
+            apply_kernel_config(cfg)
             if budget:  # CU-mask slice: slice-sized persistent grids (ops.set_cu_budget)
                 set_cu_budget(budget)
         m, x = _build(dtype, seed, demo_input_hw(), device)

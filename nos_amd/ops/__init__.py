@@ -17,7 +17,7 @@ import torch.nn.functional as F
 
 from . import _lib
 
-EPI_BIAS, EPI_GELU, EPI_RESID, EPI_RELU = 1, 2, 4, 8
+EPI_BIAS, EPI_GELU, EPI_RESID, EPI_RELU = 1, 2, 4, 8  # csrc/hip/epilogue.h (the other flags: ops/tenant.py)
 
 
 def _stream() -> int:
@@ -617,6 +617,24 @@ _ATTN_F32_VARIANT = "auto"
 
 def attention_f32_variant() -> str:
     return _ATTN_F32_VARIANT
+
+
+def apply_kernel_config(cfg: dict) -> None:
+    """Make a :func:`nos_amd.models.pod.kernel_config` dict the process-wide
+    kernel configuration: every key through its setter, a missing optional key
+    as its default (a graph keeps the configs it was captured under).  The CU
+    budget is not part of it (:func:`set_cu_budget`)."""
+    set_gemm_policy(cfg["gemm_bf16"])
+    set_gemm_f32_policy(cfg["gemm_f32"])
+    set_attention_f32_variant(cfg["attention_f32"])
+    set_f32_math(cfg["f32_math"])
+    set_gemm_f32x6_tile(cfg["gemm_f32x6_tile"])
+    set_ln_handoff(cfg.get("ln_handoff", "on") == "on")
+    set_gemm_f32h3_lds_epilogue(cfg.get("h3_epilogue", "lds") == "lds")
+    set_gemm_f32h3_layout(cfg.get("h3_layout", "2x2"))
+    set_gemm_f32h3_hot_ring(int(cfg.get("h3_hot_ring", "2")))
+    set_gemm_f32h3_hot_bn(int(cfg.get("h3_hot_bn", "128")))
+    set_gemm_f32h3_lna_wide(cfg.get("h3_lna_wide", "off") == "on")
 
 
 @torch.no_grad()

@@ -32,7 +32,7 @@ import torch.nn.functional as F
 
 from . import EPI_BIAS, EPI_GELU, EPI_RELU, EPI_RESID, _lib, _split_rows_h3, _stream, split_f32_weight_h3
 
-EPI_BIAS_ROW, EPI_RESID_PRE = 16, 32  # gemm_f32h.hip: bias per row; residual added before the activation
+EPI_BIAS_ROW, EPI_RESID_PRE = 16, 32  # csrc/hip/epilogue.h; gemm_f32h.hip: bias per row; residual added before the activation
 
 
 def _ptr(t):
@@ -722,7 +722,7 @@ def argmax(x: torch.Tensor, pos: torch.Tensor | None = None, pos_n: int = 0) -> 
 
 
 GEMV_MAX_ROWS = 8
-EPI_SILU = 64  # decode.hip's GEMV: SiLU epilogue
+EPI_SILU = 64  # csrc/hip/epilogue.h; decode.hip's GEMV: SiLU epilogue
 EPI_GLU = 256  # decode.hip's GEMV: W = [gate; up], y = silu(gate) * up
 
 

@@ -45,15 +45,7 @@ def main() -> None:
     cfg = kernel_config(a.memory_fraction, os.environ, budget)  # the pod's kernel choices (NOS_AMD_* overrides apply)
     if budget:
         ops.set_cu_budget(budget)
-    ops.set_gemm_policy(cfg["gemm_bf16"])
-    ops.set_gemm_f32_policy(cfg["gemm_f32"])
-    ops.set_attention_f32_variant(cfg["attention_f32"])
-    ops.set_f32_math(cfg["f32_math"])
-    ops.set_ln_handoff(cfg["ln_handoff"] == "on")
-    ops.set_gemm_f32h3_layout(cfg["h3_layout"])
-    ops.set_gemm_f32h3_hot_ring(int(cfg["h3_hot_ring"]))
-    ops.set_gemm_f32h3_hot_bn(int(cfg["h3_hot_bn"]))
-    ops.set_gemm_f32h3_lna_wide(cfg["h3_lna_wide"] == "on")
+    ops.apply_kernel_config(cfg)
     print("kernel config", cfg, flush=True)
     m, x = _build(a.dtype, 0, demo_input_hw())
     s = torch.cuda.Stream()
