@@ -11,7 +11,7 @@
 // (22 of an fp32's 24 bits, fp32 accumulation), within the exact-f32
 // kernel's error against fp64 (tests/test_tenant_ops_gpu.py).  What differs
 // is where the K / V scales come from: here K / V are arbitrary activations,
-// so a pre-pass measures them --
+// so a pre-pass (attn_kv_planes.h, shared with the backward) measures them --
 //
 //  1. kv_absmax: max |k| and |v| per (batch, kv head) over row chunks;
 //  2. kv_scale: the power of two that puts each head's max just under 2^14
@@ -31,137 +31,33 @@
 //     grouped-query heads read their K / V head's planes (h * Hkv / H);
 //     key splits (merged by merge_kernel) when the grid leaves CU slots idle;
 //     slice-sized persistent grids under a CU budget (nos::xcd_chunk).
+//
+// nos_attn_h3g_lse also stores every query row's log-sum-exp (natural log of
+// sum_j exp(scale q_i . k_j) over the keys the row sees) for the backward
+// (attention_h3g_bwd.hip); O is the same bits with or without it.
 #include <float.h>
 #include <limits.h>
 #include <math.h>
 
+#include "attn_kv_planes.h"
 #include "common.h"
 #include "lds_pipe.h"
 #include "split_f16.h"
 
 namespace {
 
-constexpr int KVB = 32;                 // keys per tile
 constexpr int IMG = KVB * 64 * 2;       // one 64-dim fp16 piece image: 32 rows x 128 B = 4 KiB
 constexpr float RESCALE_THR = 8.f;      // log2 units
 constexpr int MAX_SPLIT = 4;
 constexpr int HW = 8;                   // waves per workgroup
 constexpr int QB = 32 * HW;             // query rows per workgroup
-constexpr int ABS_ROWS = 256;           // rows per absmax chunk
 
 __device__ __forceinline__ int kswz(int row) { return (row >> 1) & 7; }
 __device__ __forceinline__ int vswz(int row) { return ((row >> 1) & 1) << 2; }
 
-__device__ __forceinline__ float xor32_max(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-
-__device__ __forceinline__ float xor32_sum(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
 using nos::dma_wait_publish;
 using nos::glds16;  // the asm form: in-flight tiles are not drained before every LDS read
 using nos::glds16_s;
-
-// ---------------------------------------------------------------- 1. absmax
-// part[(bh * nchunk + chunk) * 2 + (0: K, 1: V)] = max |x| over the chunk's rows
-__global__ __launch_bounds__(256) void kv_absmax_kernel(const float* __restrict__ k, const float* __restrict__ v,
-                                                        float* __restrict__ part, int S, int Hkv, int D, int ldk,
-                                                        long long bsk, int ldv, long long bsv, int nchunk) {
-  __shared__ float red[2][4];
-  const int bh = blockIdx.y, chunk = blockIdx.x;
-  const int b = bh / Hkv, h = bh - b * Hkv;
-  const int r0 = chunk * ABS_ROWS, r1 = min(S, r0 + ABS_ROWS);
-  const int d4 = D / 4;
-  const int n = (r1 - r0) * d4;
-  float mk = 0.f, mv = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int r = r0 + i / d4, c = (i % d4) * 4;
-    const float4 a = *reinterpret_cast<const float4*>(k + b * bsk + (long long)r * ldk + h * D + c);
-    const float4 e = *reinterpret_cast<const float4*>(v + b * bsv + (long long)r * ldv + h * D + c);
-    mk = fmaxf(mk, fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))));
-    mv = fmaxf(mv, fmaxf(fmaxf(fabsf(e.x), fabsf(e.y)), fmaxf(fabsf(e.z), fabsf(e.w))));
-  }
-  mk = nos::wave_max(mk);
-  mv = nos::wave_max(mv);
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = mk;
-    red[1][threadIdx.x >> 6] = mv;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    const float* r = red[threadIdx.x];
-    part[((long long)bh * nchunk + chunk) * 2 + threadIdx.x] = fmaxf(fmaxf(r[0], r[1]), fmaxf(r[2], r[3]));
-  }
-}
-
-// ---------------------------------------------------------------- 2. scales
-// kvsc[bh * 2 + t] = 2^e with (max_t * bound_t) 2^e < 2^14 (bound: K's rotary growth)
-__global__ __launch_bounds__(256) void kv_scale_kernel(const float* __restrict__ part, float* __restrict__ kvsc,
-                                                       int n, int nchunk, float kbound) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int bh = i >> 1, t = i & 1;
-  float m = 0.f;
-  for (int c = 0; c < nchunk; ++c) m = fmaxf(m, part[((long long)bh * nchunk + c) * 2 + t]);
-  kvsc[i] = nos::pow2i(nos::h3_scale_exp(t == 0 ? m * kbound : m));
-}
-
-// ---------------------------------------------------------------- 3. split
-// one thread: 8 dims of one (b, kv head, token, K|V): planes
-// kvs[(bh * skvp + s) * 4 + 2t + piece][D]; K rotated first when cos != null
-// (rows of the [Skv][D] tables = key positions)
-__global__ __launch_bounds__(256) void split_kv_kernel(const float* __restrict__ k, const float* __restrict__ v,
-                                                       const float* __restrict__ kvsc, _Float16* __restrict__ kvs,
-                                                       int S, int skvp, int Hkv, int D, int ldk, long long bsk,
-                                                       int ldv, long long bsv, const float* __restrict__ rc,
-                                                       const float* __restrict__ rs, long long n8) {
-  typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n8) return;
-  const int c8 = D / 8;
-  const int ch = (int)(i % c8);
-  long long rest = i / c8;
-  const int t = (int)(rest & 1);
-  rest >>= 1;
-  const int s = (int)(rest % S);
-  const int bh = (int)(rest / S);
-  const int b = bh / Hkv, h = bh - b * Hkv;
-  const float* src = t == 0 ? k + b * bsk + (long long)s * ldk + h * D : v + b * bsv + (long long)s * ldv + h * D;
-  float x[8];
-  {
-    const float4 a = *reinterpret_cast<const float4*>(src + ch * 8);
-    const float4 e = *reinterpret_cast<const float4*>(src + ch * 8 + 4);
-    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = e.x; x[5] = e.y; x[6] = e.z; x[7] = e.w;
-  }
-  if (t == 0 && rc != nullptr) {  // rotate_half: partner chunk D/16 away
-    const int half = c8 / 2;
-    const bool lo = ch < half;
-    const int pc = lo ? ch + half : ch - half;
-    const float4 a = *reinterpret_cast<const float4*>(src + pc * 8);
-    const float4 e = *reinterpret_cast<const float4*>(src + pc * 8 + 4);
-    const float p[8] = {a.x, a.y, a.z, a.w, e.x, e.y, e.z, e.w};
-    const float* cr = rc + (long long)s * D + ch * 8;
-    const float* sr = rs + (long long)s * D + ch * 8;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = lo ? fmaf(x[j], cr[j], -p[j] * sr[j]) : fmaf(x[j], cr[j], p[j] * sr[j]);
-  }
-  const float sc = kvsc[bh * 2 + t];
-  f16x8 hi, lo;
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) {
-    f16x2_t h2, l2;
-    nos::split2h(f32x2_t{x[j] * sc, x[j + 1] * sc}, h2, l2);
-    hi[j] = h2.x; hi[j + 1] = h2.y;
-    lo[j] = l2.x; lo[j + 1] = l2.y;
-  }
-  _Float16* dst = kvs + (((long long)bh * skvp + s) * 4 + 2 * t) * D + ch * 8;
-  *reinterpret_cast<f16x8*>(dst) = hi;
-  *reinterpret_cast<f16x8*>(dst + D) = lo;
-}
 
 // ---------------------------------------------------------------- 4. attention
 template <int D, bool CAUSAL, bool ROPE, bool PERSIST>
@@ -169,7 +65,7 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
     const float* __restrict__ q, int ldq, long long bsq, const _Float16* __restrict__ kvs,
     const float* __restrict__ kvsc, float* __restrict__ o, int ldo, long long bso, int B, int H, int Hkv, int Sq,
     int Skv, float c, int nqb, int nsplit, float* __restrict__ part, const float* __restrict__ rc,
-    const float* __restrict__ rs) {
+    const float* __restrict__ rs, float* __restrict__ lse) {
   constexpr int NH = D / 64;                 // 64-dim halves
   constexpr int NKS = D / 16;                // 16-deep MFMA steps over D
   constexpr int STAGE = 4 * NH * IMG;
@@ -437,6 +333,11 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
           *reinterpret_cast<float4*>(op + 32 * db + 8 * g + 4 * hh) =
               float4{oacc[db][4 * g + 0] * inv, oacc[db][4 * g + 1] * inv, oacc[db][4 * g + 2] * inv,
                      oacc[db][4 * g + 3] * inv};
+      // m: the reference in log2 units, lt: the row sum against it; (m + log2 lt) ln 2 with one
+      // rounding at the row's magnitude (a backward recomputes P = exp(s - lse) from it)
+      if (lse != nullptr && hh == 0)
+        lse[((long long)b * H + h) * Sq + qrow] =
+            fmaf(m, 0.6931471805599453f, __builtin_amdgcn_logf(lt) * 0.6931471805599453f);
     }
   }  // items
 }
@@ -444,7 +345,7 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
 // key-split merge: O = sum_i O_i 2^(m_i - M) / sum_i l_i 2^(m_i - M)
 __global__ __launch_bounds__(256) void merge_kernel(const float* __restrict__ part, float* __restrict__ o, int B,
                                                     int H, int D, int Sq, int nsplit, int ldo, long long bso,
-                                                    long long n4) {
+                                                    long long n4, float* __restrict__ lse) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n4) return;
   const int ldh = H * D;
@@ -470,6 +371,7 @@ __global__ __launch_bounds__(256) void merge_kernel(const float* __restrict__ pa
   const float inv = 1.f / L;
   const long long b = row / Sq, s = row - b * Sq;
   *reinterpret_cast<float4*>(o + b * bso + s * ldo + col) = float4{acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv};
+  if (lse != nullptr && col == h * D) lse[(b * H + h) * Sq + s] = fmaf(mx, 0.6931471805599453f, __builtin_amdgcn_logf(L) * 0.6931471805599453f);
 }
 
 struct Layout {
@@ -506,16 +408,16 @@ int pick_split(long long nwg1, int ntiles, int wg_per_cu) {
 template <int D, bool CAUSAL, bool ROPE>
 int launch(const float* q, int ldq, long long bsq, const _Float16* kvs, const float* kvsc, float* o, int ldo,
            long long bso, int B, int H, int Hkv, int Sq, int Skv, float c, int nqb, int nsplit, float* part,
-           const float* rc, const float* rs, hipStream_t stream) {
+           const float* rc, const float* rs, float* lse, hipStream_t stream) {
   constexpr int lds = 2 * 4 * (D / 64) * IMG;
   const long long nwg = (long long)B * H * nqb * nsplit;
   const int grid = nos_grid_for((const void*)attn_h3g_kernel<D, CAUSAL, ROPE, true>, 64 * HW, lds, nwg);
   if (grid < nwg)
     hipLaunchKernelGGL((attn_h3g_kernel<D, CAUSAL, ROPE, true>), dim3((unsigned)grid), dim3(64 * HW), lds, stream, q,
-                       ldq, bsq, kvs, kvsc, o, ldo, bso, B, H, Hkv, Sq, Skv, c, nqb, nsplit, part, rc, rs);
+                       ldq, bsq, kvs, kvsc, o, ldo, bso, B, H, Hkv, Sq, Skv, c, nqb, nsplit, part, rc, rs, lse);
   else
     hipLaunchKernelGGL((attn_h3g_kernel<D, CAUSAL, ROPE, false>), dim3((unsigned)nwg), dim3(64 * HW), lds, stream,
-                       q, ldq, bsq, kvs, kvsc, o, ldo, bso, B, H, Hkv, Sq, Skv, c, nqb, nsplit, part, rc, rs);
+                       q, ldq, bsq, kvs, kvsc, o, ldo, bso, B, H, Hkv, Sq, Skv, c, nqb, nsplit, part, rc, rs, lse);
   return (int)hipGetLastError();
 }
 
@@ -533,18 +435,13 @@ NOS_API int nos_attn_h3g_set_kvsplit(int n) {
   return 0;
 }
 
-// O = softmax(scale Q K^T [causal]) V for fp32 q [B, Sq, H, D], k / v
-// [B, Skv, Hkv, D] (token row strides ld*, batch strides bs*, each head's D
-// dims contiguous; H % Hkv == 0: grouped-query heads) into o [B, Sq, H, D]
-// (ldo, bso).  D = 64 or 128.  causal: query i attends keys <= i + Skv - Sq.
-// rope_cos / rope_sin (fp32 [Skv][D], or null): rotate Q (rows i + Skv - Sq)
-// and K (rows = key positions) by rotate_half first; rope_bound >=
-// max |cos| + max |sin| of the tables (bounds the rotated keys).  ws: at
-// least nos_attn_h3g_workspace() bytes, 256-byte aligned.
-NOS_API int nos_attn_h3g(const float* q, int ldq, long long bsq, const float* k, int ldk, long long bsk,
-                         const float* v, int ldv, long long bsv, float* o, int ldo, long long bso, int B, int H, int Hkv,
-                         int Sq, int Skv, int D, int causal, float scale, const float* rope_cos, const float* rope_sin,
-                         float rope_bound, void* ws, long long ws_bytes, hipStream_t stream) {
+namespace {
+
+// the one host path of nos_attn_h3g (lse == nullptr) and nos_attn_h3g_lse
+int attn_h3g_run(const float* q, int ldq, long long bsq, const float* k, int ldk, long long bsk, const float* v, int ldv,
+                 long long bsv, float* o, int ldo, long long bso, int B, int H, int Hkv, int Sq, int Skv, int D,
+                 int causal, float scale, const float* rope_cos, const float* rope_sin, float rope_bound, void* ws,
+                 long long ws_bytes, float* lse, hipStream_t stream) {
   if (B <= 0 || H <= 0 || Hkv <= 0 || H % Hkv || Sq <= 0 || Skv <= 0 || (D != 64 && D != 128) || !(scale > 0.f))
     return (int)hipErrorInvalidValue;
   if (causal && Sq > Skv) return (int)hipErrorInvalidValue;
@@ -580,7 +477,7 @@ NOS_API int nos_attn_h3g(const float* q, int ldq, long long bsq, const float* k,
   const bool rope = rope_cos != nullptr;
 #define NOS_H3G(d, cz, rp)                                                                                          \
   rc = launch<d, cz, rp>(q, ldq, bsq, kvs, kvsc, o, ldo, bso, B, H, Hkv, Sq, Skv, c, nqb, nsplit, part, rope_cos, \
-                         rope_sin, stream)
+                         rope_sin, lse, stream)
   if (D == 64) {
     if (causal) {
       if (rope) NOS_H3G(64, true, true); else NOS_H3G(64, true, false);
@@ -598,6 +495,35 @@ NOS_API int nos_attn_h3g(const float* q, int ldq, long long bsq, const float* k,
   if (rc != 0 || nsplit == 1) return rc;
   const long long n4 = (long long)B * Sq * H * (D / 4);
   hipLaunchKernelGGL(merge_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, part, o, B, H, D, Sq,
-                     nsplit, ldo, bso, n4);
+                     nsplit, ldo, bso, n4, lse);
   return (int)hipGetLastError();
+}
+}  // namespace
+
+// O = softmax(scale Q K^T [causal]) V for fp32 q [B, Sq, H, D], k / v
+// [B, Skv, Hkv, D] (token row strides ld*, batch strides bs*, each head's D
+// dims contiguous; H % Hkv == 0: grouped-query heads) into o [B, Sq, H, D]
+// (ldo, bso).  D = 64 or 128.  causal: query i attends keys <= i + Skv - Sq.
+// rope_cos / rope_sin (fp32 [Skv][D], or null): rotate Q (rows i + Skv - Sq)
+// and K (rows = key positions) by rotate_half first; rope_bound >=
+// max |cos| + max |sin| of the tables (bounds the rotated keys).  ws: at
+// least nos_attn_h3g_workspace() bytes, 256-byte aligned.
+NOS_API int nos_attn_h3g(const float* q, int ldq, long long bsq, const float* k, int ldk, long long bsk,
+                         const float* v, int ldv, long long bsv, float* o, int ldo, long long bso, int B, int H, int Hkv,
+                         int Sq, int Skv, int D, int causal, float scale, const float* rope_cos, const float* rope_sin,
+                         float rope_bound, void* ws, long long ws_bytes, hipStream_t stream) {
+  return attn_h3g_run(q, ldq, bsq, k, ldk, bsk, v, ldv, bsv, o, ldo, bso, B, H, Hkv, Sq, Skv, D, causal, scale, rope_cos,
+                      rope_sin, rope_bound, ws, ws_bytes, nullptr, stream);
+}
+
+// nos_attn_h3g that also writes lse [B][H][Sq] (contiguous fp32): the natural
+// log of sum_j exp(scale q_i . k_j) over the keys query row i sees.
+NOS_API int nos_attn_h3g_lse(const float* q, int ldq, long long bsq, const float* k, int ldk, long long bsk,
+                             const float* v, int ldv, long long bsv, float* o, int ldo, long long bso, int B, int H,
+                             int Hkv, int Sq, int Skv, int D, int causal, float scale, const float* rope_cos,
+                             const float* rope_sin, float rope_bound, void* ws, long long ws_bytes, float* lse,
+                             hipStream_t stream) {
+  if (lse == nullptr || ((uintptr_t)lse & 3)) return (int)hipErrorInvalidValue;
+  return attn_h3g_run(q, ldq, bsq, k, ldk, bsk, v, ldv, bsv, o, ldo, bso, B, H, Hkv, Sq, Skv, D, causal, scale, rope_cos,
+                      rope_sin, rope_bound, ws, ws_bytes, lse, stream);
 }

@@ -1,0 +1,128 @@
+// The K / V pre-pass of the general h3 attention (attention_h3g.hip) and its
+// backward (attention_h3g_bwd.hip): measure max |k|, |v| per (batch, kv head),
+// turn them into power-of-two scales and write K / V as four fp16 planes per
+// token.  Each including source gets its own copy of the kernels (internal
+// linkage); both sources produce the same planes from the same K / V.
+//
+//  1. kv_absmax: max |k| and |v| per (batch, kv head) over row chunks;
+//  2. kv_scale: the power of two that puts each head's max just under 2^14
+//     (for rotated keys: the host's bound max|cos| + max|sin| on top);
+//  3. split_kv: K (rotated on the fly) and V as four fp16 planes per token,
+//     [b][kv head][token][K hi, K lo, V hi, V lo][D], 16-byte stores.
+#pragma once
+#include "common.h"
+#include "split_f16.h"
+
+namespace {
+
+constexpr int KVB = 32;                 // keys per tile
+constexpr int ABS_ROWS = 256;           // rows per absmax chunk
+
+__device__ __forceinline__ float xor32_max(float v) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+
+__device__ __forceinline__ float xor32_sum(float v) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// ---------------------------------------------------------------- 1. absmax
+// part[(bh * nchunk + chunk) * 2 + (0: K, 1: V)] = max |x| over the chunk's rows
+__global__ __launch_bounds__(256) void kv_absmax_kernel(const float* __restrict__ k, const float* __restrict__ v,
+                                                        float* __restrict__ part, int S, int Hkv, int D, int ldk,
+                                                        long long bsk, int ldv, long long bsv, int nchunk) {
+  __shared__ float red[2][4];
+  const int bh = blockIdx.y, chunk = blockIdx.x;
+  const int b = bh / Hkv, h = bh - b * Hkv;
+  const int r0 = chunk * ABS_ROWS, r1 = min(S, r0 + ABS_ROWS);
+  const int d4 = D / 4;
+  const int n = (r1 - r0) * d4;
+  float mk = 0.f, mv = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int r = r0 + i / d4, c = (i % d4) * 4;
+    const float4 a = *reinterpret_cast<const float4*>(k + b * bsk + (long long)r * ldk + h * D + c);
+    const float4 e = *reinterpret_cast<const float4*>(v + b * bsv + (long long)r * ldv + h * D + c);
+    mk = fmaxf(mk, fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))));
+    mv = fmaxf(mv, fmaxf(fmaxf(fabsf(e.x), fabsf(e.y)), fmaxf(fabsf(e.z), fabsf(e.w))));
+  }
+  mk = nos::wave_max(mk);
+  mv = nos::wave_max(mv);
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = mk;
+    red[1][threadIdx.x >> 6] = mv;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const float* r = red[threadIdx.x];
+    part[((long long)bh * nchunk + chunk) * 2 + threadIdx.x] = fmaxf(fmaxf(r[0], r[1]), fmaxf(r[2], r[3]));
+  }
+}
+
+// ---------------------------------------------------------------- 2. scales
+// kvsc[bh * 2 + t] = 2^e with (max_t * bound_t) 2^e < 2^14 (bound: K's rotary growth)
+__global__ __launch_bounds__(256) void kv_scale_kernel(const float* __restrict__ part, float* __restrict__ kvsc,
+                                                       int n, int nchunk, float kbound) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int bh = i >> 1, t = i & 1;
+  float m = 0.f;
+  for (int c = 0; c < nchunk; ++c) m = fmaxf(m, part[((long long)bh * nchunk + c) * 2 + t]);
+  kvsc[i] = nos::pow2i(nos::h3_scale_exp(t == 0 ? m * kbound : m));
+}
+
+// ---------------------------------------------------------------- 3. split
+// one thread: 8 dims of one (b, kv head, token, K|V): planes
+// kvs[(bh * skvp + s) * 4 + 2t + piece][D]; K rotated first when cos != null
+// (rows of the [Skv][D] tables = key positions)
+__global__ __launch_bounds__(256) void split_kv_kernel(const float* __restrict__ k, const float* __restrict__ v,
+                                                       const float* __restrict__ kvsc, _Float16* __restrict__ kvs,
+                                                       int S, int skvp, int Hkv, int D, int ldk, long long bsk,
+                                                       int ldv, long long bsv, const float* __restrict__ rc,
+                                                       const float* __restrict__ rs, long long n8) {
+  typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  const int c8 = D / 8;
+  const int ch = (int)(i % c8);
+  long long rest = i / c8;
+  const int t = (int)(rest & 1);
+  rest >>= 1;
+  const int s = (int)(rest % S);
+  const int bh = (int)(rest / S);
+  const int b = bh / Hkv, h = bh - b * Hkv;
+  const float* src = t == 0 ? k + b * bsk + (long long)s * ldk + h * D : v + b * bsv + (long long)s * ldv + h * D;
+  float x[8];
+  {
+    const float4 a = *reinterpret_cast<const float4*>(src + ch * 8);
+    const float4 e = *reinterpret_cast<const float4*>(src + ch * 8 + 4);
+    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = e.x; x[5] = e.y; x[6] = e.z; x[7] = e.w;
+  }
+  if (t == 0 && rc != nullptr) {  // rotate_half: partner chunk D/16 away
+    const int half = c8 / 2;
+    const bool lo = ch < half;
+    const int pc = lo ? ch + half : ch - half;
+    const float4 a = *reinterpret_cast<const float4*>(src + pc * 8);
+    const float4 e = *reinterpret_cast<const float4*>(src + pc * 8 + 4);
+    const float p[8] = {a.x, a.y, a.z, a.w, e.x, e.y, e.z, e.w};
+    const float* cr = rc + (long long)s * D + ch * 8;
+    const float* sr = rs + (long long)s * D + ch * 8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = lo ? fmaf(x[j], cr[j], -p[j] * sr[j]) : fmaf(x[j], cr[j], p[j] * sr[j]);
+  }
+  const float sc = kvsc[bh * 2 + t];
+  f16x8 hi, lo;
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) {
+    f16x2_t h2, l2;
+    nos::split2h(f32x2_t{x[j] * sc, x[j + 1] * sc}, h2, l2);
+    hi[j] = h2.x; hi[j + 1] = h2.y;
+    lo[j] = l2.x; lo[j + 1] = l2.y;
+  }
+  _Float16* dst = kvs + (((long long)bh * skvp + s) * 4 + 2 * t) * D + ch * 8;
+  *reinterpret_cast<f16x8*>(dst) = hi;
+  *reinterpret_cast<f16x8*>(dst + D) = lo;
+}
+
+}  // namespace

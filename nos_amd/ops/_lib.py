@@ -134,10 +134,19 @@ _SIGS = {
     "nos_attn_h3g": [c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p, c_int, c_ll,
                      c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_float, c_void_p,
                      c_ll, c_void_p],
+    # training tenants (attention_h3g.hip / attention_h3g_bwd.hip): the forward with the rows' log-sum-exp, the backward
+    "nos_attn_h3g_lse": [c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p, c_int, c_ll,
+                         c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_float,
+                         c_void_p, c_ll, c_void_p, c_void_p],
+    "nos_attn_h3g_bwd_workspace": [c_int, c_int, c_int, c_int, c_int, c_int],
+    "nos_attn_h3g_bwd": [c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p, c_int, c_ll,
+                         c_void_p, c_int, c_ll, c_void_p, c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p, c_int,
+                         c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_ll, c_void_p],
 }
 
 
-_RESTYPES = {"nos_attn_f32x6_workspace": c_ll, "nos_attn_h3g_workspace": c_ll, "nos_attn_decode_workspace": c_ll}
+_RESTYPES = {"nos_attn_f32x6_workspace": c_ll, "nos_attn_h3g_workspace": c_ll, "nos_attn_decode_workspace": c_ll,
+             "nos_attn_h3g_bwd_workspace": c_ll}
 
 
 class NativeUnavailable(RuntimeError):

@@ -109,6 +109,57 @@ def sdpa_ref(q, k, v, causal: bool = False, scale: float | None = None, rope=Non
     return torch.einsum("bhqk,bkhd->bqhd", p, vf).to(q.dtype)
 
 
+def _train_scores(q, k, causal: bool, scale: float):
+    """scale q k^T [B, H, Sq, Skv] in q's dtype (grouped-query heads repeated), masked keys at -inf."""
+    Sq, Skv = q.shape[1], k.shape[1]
+    s = torch.einsum("bqhd,bkhd->bhqk", q, k.repeat_interleave(q.shape[2] // k.shape[2], dim=2)) * scale
+    if causal:
+        i = torch.arange(Sq, device=q.device)[:, None] + (Skv - Sq)
+        j = torch.arange(Skv, device=q.device)[None, :]
+        s = s.masked_fill(j > i, float("-inf"))
+    return s
+
+
+def _train_dtype(t: torch.Tensor) -> torch.dtype:
+    return t.dtype if t.dtype in (torch.float32, torch.float64) else torch.float32
+
+
+def sdpa_lse_ref(q, k, v, causal: bool = False, scale: float | None = None):
+    """(o, lse) of :func:`sdpa_lse` in plain torch math in the input dtype
+    (fp64 stays fp64): lse [B, H, Sq] = log sum_j exp(scale q_i . k_j) over
+    the keys row i sees, o = exp(s - lse) v."""
+    ct = _train_dtype(q)
+    scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    qf, kf, vf = q.to(ct), k.to(ct), v.to(ct)
+    s = _train_scores(qf, kf, causal, scale)
+    m = s.amax(-1, keepdim=True)
+    lse = (m + torch.log(torch.exp(s - m).sum(-1, keepdim=True))).squeeze(-1)
+    p = torch.exp(s - lse[..., None])
+    o = torch.einsum("bhqk,bkhd->bqhd", p, vf.repeat_interleave(q.shape[2] // k.shape[2], dim=2))
+    return o.to(q.dtype), lse
+
+
+def sdpa_bwd_ref(q, k, v, o, lse, do, causal: bool = False, scale: float | None = None):
+    """(dq, dk, dv) of :func:`sdpa_bwd` by the recompute-from-log-sum-exp
+    formulas the kernel implements (no autograd): P = exp(s - lse),
+    dV = P^T dO, dP = dO V^T, delta = rowsum(dO . O), dS = scale P (dP - delta),
+    dQ = dS K, dK = dS^T Q; the heads of a group sum into their K / V head."""
+    ct = _train_dtype(q)
+    B, Sq, H, D = q.shape
+    Skv, Hkv = k.shape[1], k.shape[2]
+    g = H // Hkv
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    qf, kf, vf, of, dof = (t.to(ct) for t in (q, k, v, o, do))
+    p = torch.exp(_train_scores(qf, kf, causal, scale) - lse.to(ct)[..., None])
+    dp = torch.einsum("bqhd,bkhd->bhqk", dof, vf.repeat_interleave(g, dim=2))
+    delta = (dof * of).sum(-1).permute(0, 2, 1)                        # [B, H, Sq]
+    ds = p * (dp - delta[..., None]) * scale
+    dq = torch.einsum("bhqk,bkhd->bqhd", ds, kf.repeat_interleave(g, dim=2))
+    dk = torch.einsum("bhqk,bqhd->bkhd", ds, qf).reshape(B, Skv, Hkv, g, D).sum(3)
+    dv = torch.einsum("bhqk,bqhd->bkhd", p, dof).reshape(B, Skv, Hkv, g, D).sum(3)
+    return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
+
+
 def rmsnorm_ref(x, weight, eps=1e-6):
     xf = x.float()
     y = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
@@ -534,6 +585,119 @@ def sdpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False
     return o if dt == torch.float32 else o.to(dt)
 
 
+# ------------------------------------------------------------------ training attention (attention_h3g_bwd.hip)
+BWD_MAX_QSPLIT = 8   # attention_h3g_bwd.hip MAX_QSPLIT: ranges of the dK / dV sweep
+BWD_ABS_ROWS = 256   # attn_kv_planes.h ABS_ROWS: rows per absmax chunk
+
+
+def sdpa_bwd_workspace_bytes(B: int, H: int, Hkv: int, Sq: int, Skv: int, D: int) -> int:
+    """Workspace bytes of :func:`sdpa_bwd` from the shapes alone (the memory
+    estimate of a training tenant needs no library): equals
+    ``nos_attn_h3g_bwd_workspace`` (attention_h3g_bwd.hip ``layout``)."""
+    def al(x: int) -> int:
+        return -(-x // 256) * 256
+
+    skvp, sqp = -(-Skv // 32) * 32, -(-Sq // 32) * 32
+    nck, ncq = -(-Skv // BWD_ABS_ROWS), -(-Sq // BWD_ABS_ROWS)
+    return (al(B * Hkv * skvp * 4 * D * 2)          # K / V row planes
+            + al(B * Hkv * skvp * 2 * D * 2)        # K transposed planes
+            + 2 * al(B * H * sqp * 4 * D * 2)       # Q / dO row planes, transposed planes
+            + al(B * H * sqp * 16)                  # per-row constants (delta, log-sum-exp, Q scale)
+            + al(B * Hkv * nck * 2 * 4) + al(B * H * ncq * 2 * 4)   # absmax partials
+            + al(B * Hkv * 2 * 4) + al(B * Hkv * 8 * 4)             # scales, per-group constants
+            + BWD_MAX_QSPLIT * B * Skv * Hkv * 2 * D * 4)           # partial dK / dV of a split sweep
+
+
+def _train_rows(t: torch.Tensor) -> tuple[torch.Tensor, int, int]:
+    """fp32 t [B, S, H, D] as the kernels take it (heads contiguous per token,
+    16-byte aligned, strides in multiples of 4 floats), copied only if it is not."""
+    t = _f32(t)
+    try:
+        ld, bs = _rows_view(t)
+    except ValueError:
+        t = t.contiguous()
+        ld, bs = _rows_view(t)
+    if ld % 4 or bs % 4 or t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.contiguous_format)
+        ld, bs = _rows_view(t)
+    return t, ld, bs
+
+
+def _check_attn_shapes(what: str, q, k, v) -> None:
+    B, Sq, H, D = q.shape
+    Hkv = k.shape[2]
+    if D not in (64, 128) or H % Hkv or v.shape != k.shape or k.shape[0] != B or k.shape[3] != D:
+        raise ValueError(f"native {what}: head_dim 64/128, H % Hkv == 0; got q {tuple(q.shape)}, k {tuple(k.shape)}")
+
+
+def sdpa_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False, scale: float | None = None):
+    """:func:`sdpa` (no rotary) that also returns the rows' log-sum-exp for
+    :func:`sdpa_bwd`: (o [B, Sq, H, D], lse fp32 [B, H, Sq]); the same O bits
+    as :func:`sdpa` (``nos_attn_h3g_lse``)."""
+    if not q.is_cuda:
+        return sdpa_lse_ref(q, k, v, causal, scale)
+    _check_attn_shapes("sdpa_lse", q, k, v)
+    dt = q.dtype
+    B, Sq, H, D = q.shape
+    Skv, Hkv = k.shape[1], k.shape[2]
+    (qf, ldq, bsq), (kf, ldk, bsk), (vf, ldv, bsv) = _train_rows(q), _train_rows(k), _train_rows(v)
+    o = torch.empty((B, Sq, H, D), dtype=torch.float32, device=q.device)
+    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+    L = _lib.lib()
+    nbytes = int(L.nos_attn_h3g_workspace(B, H, Hkv, Sq, Skv, D))
+    ws = torch.empty((nbytes + 256,), dtype=torch.uint8, device=q.device)
+    wptr = (ws.data_ptr() + 255) // 256 * 256
+    sc = scale if scale is not None else 1.0 / math.sqrt(D)
+    rc = L.nos_attn_h3g_lse(qf.data_ptr(), ldq, bsq, kf.data_ptr(), ldk, bsk, vf.data_ptr(), ldv, bsv, o.data_ptr(),
+                            o.stride(1), o.stride(0), B, H, Hkv, Sq, Skv, D, int(bool(causal)), float(sc), None, None,
+                            0.0, wptr, nbytes, lse.data_ptr(), _stream())
+    _lib.check(rc, "nos_attn_h3g_lse")
+    return (o if dt == torch.float32 else o.to(dt)), lse
+
+
+def sdpa_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, lse: torch.Tensor, do: torch.Tensor,
+             causal: bool = False, scale: float | None = None, out: tuple | None = None):
+    """(dq, dk, dv) of :func:`sdpa_lse`'s o for the upstream gradient ``do``
+    (``nos_attn_h3g_bwd``: two kernels that recompute P from ``lse``, no
+    atomics -- the same bits on every call).  Tensors as in :func:`sdpa`,
+    any token / batch strides; gradients contiguous, in the inputs' dtypes.
+    ``out`` = (dq, dk, dv): fp32 CUDA tensors to write instead (heads
+    contiguous per token; every element is overwritten, none is read)."""
+    if not q.is_cuda:
+        return sdpa_bwd_ref(q, k, v, o, lse, do, causal, scale)
+    _check_attn_shapes("sdpa_bwd", q, k, v)
+    B, Sq, H, D = q.shape
+    Skv, Hkv = k.shape[1], k.shape[2]
+    if o.shape != q.shape or do.shape != q.shape or lse.shape != (B, H, Sq):
+        raise ValueError(f"sdpa_bwd: o / do must be {tuple(q.shape)} and lse {(B, H, Sq)}")
+    (qf, ldq, bsq), (kf, ldk, bsk), (vf, ldv, bsv) = _train_rows(q), _train_rows(k), _train_rows(v)
+    (of, ldo, bso), (dof, lddo, bsdo) = _train_rows(o), _train_rows(do)
+    lf = lse.float().contiguous()
+    if out is not None:
+        dq, dk, dv = out
+        for t, ref in ((dq, q), (dk, k), (dv, k)):
+            if t.shape != ref.shape or t.dtype != torch.float32 or not t.is_cuda or t.data_ptr() % 16 \
+                    or any(x % 4 for x in _rows_view(t)):
+                raise ValueError("sdpa_bwd: out must be aligned fp32 CUDA tensors in the shapes of q, k, v")
+    else:
+        dq = torch.empty((B, Sq, H, D), dtype=torch.float32, device=q.device)
+        dk = torch.empty((B, Skv, Hkv, D), dtype=torch.float32, device=q.device)
+        dv = torch.empty((B, Skv, Hkv, D), dtype=torch.float32, device=q.device)
+    nbytes = sdpa_bwd_workspace_bytes(B, H, Hkv, Sq, Skv, D)
+    ws = torch.empty((nbytes + 256,), dtype=torch.uint8, device=q.device)
+    wptr = (ws.data_ptr() + 255) // 256 * 256
+    sc = scale if scale is not None else 1.0 / math.sqrt(D)
+    rc = _lib.lib().nos_attn_h3g_bwd(qf.data_ptr(), ldq, bsq, kf.data_ptr(), ldk, bsk, vf.data_ptr(), ldv, bsv,
+                                     of.data_ptr(), ldo, bso, dof.data_ptr(), lddo, bsdo, lf.data_ptr(),
+                                     dq.data_ptr(), dq.stride(1), dq.stride(0), dk.data_ptr(), dk.stride(1),
+                                     dk.stride(0), dv.data_ptr(), dv.stride(1), dv.stride(0), B, H, Hkv, Sq, Skv, D,
+                                     int(bool(causal)), float(sc), wptr, nbytes, _stream())
+    _lib.check(rc, "nos_attn_h3g_bwd")
+    if out is not None:
+        return dq, dk, dv
+    return tuple(t if x.dtype == torch.float32 else t.to(x.dtype) for t, x in ((dq, q), (dk, k), (dv, v)))
+
+
 # ------------------------------------------------------------------ stateful decoding (decode.hip)
 def _i32_pos(pos: torch.Tensor, B: int) -> torch.Tensor:
     if pos.dtype != torch.int32 or pos.shape != (B,) or not pos.is_contiguous():
@@ -789,4 +953,5 @@ def set_attention_h3g_kvsplit(n: int) -> None:
 
 __all__ = ["glu", "kv_write", "rotary_at", "sdpa_cache", "pos_update", "argmax", "gemv", "gemv_ok", "gemv_partials",
            "DecodePartials", "conv2d", "matmul", "sdpa", "linear_rms", "embedding", "rmsnorm", "softmax", "rotary", "conv2d_ref",
-           "sdpa_ref", "rope_ref", "rmsnorm_ref", "linear_rms_ref", "set_attention_h3g_kvsplit", "EPI_BIAS_ROW"]
+           "sdpa_ref", "rope_ref", "rmsnorm_ref", "linear_rms_ref", "set_attention_h3g_kvsplit", "EPI_BIAS_ROW",
+           "sdpa_lse", "sdpa_bwd", "sdpa_lse_ref", "sdpa_bwd_ref", "sdpa_bwd_workspace_bytes"]

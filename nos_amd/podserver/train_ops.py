@@ -17,6 +17,12 @@ backward).  Here both run on ``libnos_hip.so``:
   the live scores are ``B x H x C x S``), then ``dV += P^T dO_c``,
   ``dP = dO_c V^T``, ``dS = P (dP - rowsum(dO_c O_c))``, ``dQ_c = dS K``,
   ``dK += dS^T Q_c`` -- the four products per chunk on the h3 GEMM;
+* :class:`FlashAttention` -- the same attention as ONE fused kernel forward
+  (``nos_attn_h3g_lse``: the inference flash kernel, also storing the rows'
+  log-sum-exp) and two backward (``nos_attn_h3g_bwd``: dK / dV per key block,
+  dQ per query block, P recomputed from the log-sum-exp; no atomics), on
+  strided [B, S, H, D] views -- no head permutes, no score tensor at all.
+  Opt-in per tenant (train spec ``"attention": "flash"``);
 * :class:`CrossEntropy` -- the classification loss from the rows'
   log-sum-exp (no softmax kernel; the round-5 step ran ``F.cross_entropy``).
 
@@ -157,6 +163,57 @@ def attention(q, k, v, causal: bool = False, scale: float | None = None):
     return ChunkedAttention.apply(q, k, v, bool(causal), sc)
 
 
+class FlashAttention(torch.autograd.Function):
+    """:class:`ChunkedAttention`'s function on the fused flash kernels
+    (``ops.tenant.sdpa_lse`` / ``sdpa_bwd``): q [B, Sq, H, D], k / v [B, Skv,
+    Hkv, D] read through their strides (slices of a fused QKV projection are
+    not copied); saved for backward: q, k, v, o and the log-sum-exp rows.
+    CPU tensors take the same formulas in torch math (fp64 kept for tests)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, causal: bool, scale: float):
+        from ..ops import tenant as T
+
+        o, lse = T.sdpa_lse(q, k, v, causal, scale)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.causal, ctx.scale = causal, scale
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        from ..ops import tenant as T
+
+        q, k, v, o, lse = ctx.saved_tensors
+        dq, dk, dv = T.sdpa_bwd(q, k, v, o, lse, do, ctx.causal, ctx.scale)
+        return dq, dk, dv, None, None
+
+
+def flash_supported(q, k) -> bool:
+    """Whether the flash kernels take these shapes (CPU: the torch formulas take any)."""
+    return not q.is_cuda or (q.shape[-1] in (64, 128) and q.shape[2] % k.shape[2] == 0
+                             and q.dtype in (torch.float32, torch.bfloat16))
+
+
+def flash_attention(q, k, v, causal: bool = False, scale: float | None = None):
+    """:func:`attention` on :class:`FlashAttention`; shapes the kernels do not
+    take (head_dim other than 64 / 128 on the GPU) run :class:`ChunkedAttention`."""
+    sc = float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    if not flash_supported(q, k):
+        return ChunkedAttention.apply(q, k, v, bool(causal), sc)
+    return FlashAttention.apply(q, k, v, bool(causal), sc)
+
+
+def flash_workspace_bytes(b: int, h: int, hkv: int, sq: int, skv: int, d: int) -> int:
+    """Transient bytes of one :class:`FlashAttention` backward (the kernels'
+    workspace; the forward's is smaller and not live at the same time);
+    shapes the kernels do not take are charged as :class:`ChunkedAttention`."""
+    if d not in (64, 128) or h % hkv:
+        return scores_bytes(b, h, sq, skv)
+    from ..ops.tenant import sdpa_bwd_workspace_bytes
+
+    return sdpa_bwd_workspace_bytes(b, h, hkv, sq, skv, d)
+
+
 class CrossEntropy(torch.autograd.Function):
     """Mean cross-entropy of logits x [N, C] against class ids t [N]
     (``ignore_index`` -100, as ``F.cross_entropy``): the loss from the rows'
@@ -191,5 +248,5 @@ def scores_bytes(b: int, h: int, sq: int, skv: int) -> int:
     return 4 * b * h * min(sq, CHUNK) * skv * 4
 
 
-__all__ = ["H3Linear", "ChunkedAttention", "CrossEntropy", "linear", "attention", "cross_entropy", "scores_bytes",
-           "CHUNK"]
+__all__ = ["H3Linear", "ChunkedAttention", "FlashAttention", "CrossEntropy", "linear", "attention", "flash_attention",
+           "flash_supported", "flash_workspace_bytes", "cross_entropy", "scores_bytes", "CHUNK"]

@@ -42,8 +42,12 @@ from .program import Program, ProgramError, _eager, _qkv_views, _req
 LOSSES = ("mse", "cross_entropy")
 _STEP_SPLIT = 1 << 24   # a checkpointed step count = hi * 2^24 + lo, both exact in float32
 OPTIMIZERS = ("sgd", "adam", "adamw")
+# attention of a native training step: "chunked" = train_ops.ChunkedAttention (h3 GEMMs around PyTorch
+# elementwise kernels, per 512-row query chunk), "flash" = train_ops.FlashAttention (one fused gfx950
+# kernel forward, two backward: attention_h3g.hip / attention_h3g_bwd.hip)
+ATTENTIONS = ("chunked", "flash")
 SPEC_KEYS = {"loss", "optimizer", "lr", "momentum", "nesterov", "weight_decay", "betas", "eps", "output", "frozen",
-             "resume"}
+             "resume", "attention"}
 
 
 def parse_train_spec(spec, prog: Program) -> dict:
@@ -65,6 +69,8 @@ def parse_train_spec(spec, prog: Program) -> dict:
 
     for key in ("resume", "nesterov"):   # strict: bool("false") is True
         _req(isinstance(spec.get(key, False), bool), f"train.{key} must be true or false")
+    attention = spec.get("attention", "chunked")
+    _req(isinstance(attention, str) and attention in ATTENTIONS, f"train.attention must be one of {ATTENTIONS}")
     lr = num("lr", 1e-3, 0.0, 10.0)
     _req(not spec.get("nesterov") or (opt == "sgd" and num("momentum", 0.0, 0.0, 0.999) > 0),
          "train.nesterov needs sgd with momentum > 0")
@@ -88,7 +94,7 @@ def parse_train_spec(spec, prog: Program) -> dict:
             "weight_decay": num("weight_decay", 0.0, 0.0, 1.0), "betas": [float(b) for b in betas],
             "eps": num("eps", 1e-8, 1e-12, 1.0), "output": out, "frozen": sorted(set(frozen) | constant_weights(prog)),
             "resume": bool(spec.get("resume", False)), "nesterov": bool(spec.get("nesterov", False)),
-            "target_shape": tshape, "target_dtype": tdt}
+            "attention": attention, "target_shape": tshape, "target_dtype": tdt}
 
 
 def constant_weights(prog: Program) -> set[str]:
@@ -120,10 +126,14 @@ def train_bytes_estimate(prog: Program, spec: dict) -> int:
     # scores of one query chunk at a time; NOS_AMD_TRAIN_NATIVE=0: the full
     # B x H x Sq x Skv scores, masked copy and probabilities of every layer)
 
-    from .train_ops import scores_bytes
+    # "attention": "flash" (train_ops.FlashAttention): per layer the saved
+    # log-sum-exp rows as above; no live score chunk, instead the backward
+    # kernels' workspace of the largest node, once (freed between nodes)
+    from .train_ops import flash_workspace_bytes, scores_bytes
 
     native = os.environ.get("NOS_AMD_TRAIN_NATIVE", "1") != "0"
-    scores = live = 0
+    flash = spec.get("attention", "chunked") == "flash"
+    scores = live = flash_ws = 0
     for n in prog.nodes:
         if n.op == "sdpa":
             (b, sq, h, _), skv = prog.values[n.inputs[0]].shape, prog.values[n.inputs[1]].shape[1]
@@ -134,19 +144,25 @@ def train_bytes_estimate(prog: Program, spec: dict) -> int:
             continue
         if native:
             scores += 4 * b * h * sq
-            live = max(live, scores_bytes(b, h, sq, skv))
+            if flash:
+                hkv = prog.values[n.inputs[1]].shape[2] if n.op == "sdpa" else h
+                d = prog.values[n.inputs[0]].shape[-1] if n.op == "sdpa" else prog.values[n.inputs[0]].shape[-1] // (3 * h)
+                flash_ws = max(flash_ws, flash_workspace_bytes(b, h, hkv, sq, skv, d))
+            else:
+                live = max(live, scores_bytes(b, h, sq, skv))
         else:
             scores += 3 * b * h * sq * skv * 4
     scores += live
     tgt = math.prod(spec["target_shape"]) * 4
     return (w + trainable * (1 + states) + sum(v.numel * 4 for v in prog.inputs) + tgt + 2 * acts
-            + 2 * scores)
+            + 2 * scores + flash_ws)
 
 
-def _train_op(op: str, args: list, attrs: dict):
+def _train_op(op: str, args: list, attrs: dict, attention: str = "chunked"):
     """One node, differentiable: GEMMs and attention on the gfx950 kernels
     (train_ops: h3 GEMMs for the forward and both backward products, chunked
-    attention with a log-sum-exp recompute -- no S x S scores kept), the rest
+    attention with a log-sum-exp recompute -- no S x S scores kept -- or, with
+    ``attention`` = "flash", the fused flash forward and backward), the rest
     in PyTorch.  ``NOS_AMD_TRAIN_NATIVE=0``: PyTorch throughout (A/B)."""
 
     native = os.environ.get("NOS_AMD_TRAIN_NATIVE", "1") != "0"
@@ -158,12 +174,14 @@ def _train_op(op: str, args: list, attrs: dict):
         if "q_start" in attrs:
             q = q[:, attrs["q_start"]:attrs["q_end"]]
         if native:
-            return train_ops.attention(q, k, v, attrs.get("causal", False), attrs.get("scale")).flatten(2)
+            fn = train_ops.flash_attention if attention == "flash" else train_ops.attention
+            return fn(q, k, v, attrs.get("causal", False), attrs.get("scale")).flatten(2)
         return T.sdpa_ref(q, k, v, attrs.get("causal", False), attrs.get("scale")).flatten(2)
     if op == "sdpa" and native:
         from . import train_ops
 
-        return train_ops.attention(args[0], args[1], args[2], attrs.get("causal", False), attrs.get("scale"))
+        fn = train_ops.flash_attention if attention == "flash" else train_ops.attention
+        return fn(args[0], args[1], args[2], attrs.get("causal", False), attrs.get("scale"))
     if op == "linear" and native:
         import torch.nn.functional as F
 
@@ -184,9 +202,10 @@ def _module_cls():
         """A program's graph as a module over its weights (fp32 Parameters,
         frozen ones as buffers)."""
 
-        def __init__(self, prog: Program, params: dict, frozen):
+        def __init__(self, prog: Program, params: dict, frozen, attention: str = "chunked"):
             super().__init__()
             self.prog = prog
+            self.attention = attention
             self.slots: dict[str, tuple[str, int]] = {}
             self.weights = nn.ParameterList()
             fixed = []
@@ -209,7 +228,7 @@ def _module_cls():
             env = {name: self.weight(name) for name in self.prog.params}
             env[self.prog.inputs[0].name] = x if self.prog.inputs[0].dtype == "i32" else x.float()
             for n in self.prog.nodes:
-                env[n.output] = _train_op(n.op, [env[i] for i in n.inputs], n.attrs)
+                env[n.output] = _train_op(n.op, [env[i] for i in n.inputs], n.attrs, self.attention)
             return tuple(env[o] for o in self.prog.outputs)
 
     return ProgramModule
@@ -241,7 +260,8 @@ class Trainer:
 
         self.prog, self.spec = prog, spec
         self.device = torch.device(device)
-        self.module = _module_cls()(prog, prog.tensors(self.device), set(spec["frozen"])).to(self.device)
+        self.module = _module_cls()(prog, prog.tensors(self.device), set(spec["frozen"]),
+                                    spec.get("attention", "chunked")).to(self.device)
         ps = list(self.module.weights)
         cap = self.device.type == "cuda"
         if spec["optimizer"] == "sgd":

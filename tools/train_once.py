@@ -1,7 +1,7 @@
 """One training tenant stepping in this process, for rocprofv3 kernel stats
 (no hipBLASLt GEMM, no at::native softmax in a step).
 
-python tools/train_once.py --seq 2048 --steps 6
+python tools/train_once.py --seq 2048 --steps 6 [--attention flash]
 """
 from __future__ import annotations
 
@@ -20,6 +20,8 @@ def main() -> None:
     ap.add_argument("--seq", type=int, default=2048)
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--small", type=int, default=1)
+    ap.add_argument("--attention", choices=["chunked", "flash"], default="chunked",
+                    help="the train spec's attention: chunked h3 GEMMs (default) or the fused flash kernels")
     a = ap.parse_args()
     import numpy as np
 
@@ -33,13 +35,13 @@ def main() -> None:
     try:
         c = PodClient(srv.path, connect_timeout_s=60)
         rep = c.register("ft", prog, w, memory_limit_gb=10,
-                         train={"loss": "cross_entropy", "optimizer": "adamw", "lr": 1e-4})
+                         train={"loss": "cross_entropy", "optimizer": "adamw", "lr": 1e-4, "attention": a.attention})
         ids = np.random.default_rng(0).integers(0, 32000 if a.small else 512, (1, a.seq + 1)).astype(np.int32)
         c.train_step(ids[:, :-1], ids[:, 1:])
         t0 = time.monotonic()
         losses = [c.train_step(ids[:, :-1], ids[:, 1:])["loss"] for _ in range(a.steps)]
         dt = (time.monotonic() - t0) / a.steps
-        print(json.dumps({"seq": a.seq, "footprint_gb": rep["footprint_gb"], "step_s": round(dt, 4),
+        print(json.dumps({"seq": a.seq, "attention": a.attention, "footprint_gb": rep["footprint_gb"], "step_s": round(dt, 4),
                           "tokens_per_s": round(a.seq / dt, 1), "losses": [round(x, 4) for x in losses]}), flush=True)
         c.close()
     finally:
