@@ -69,14 +69,11 @@ using nos::dma_wait_publish;
 using nos::glds16;
 using nos::glds16_s;
 
-// dma_wait_publish with the newest N DMAs left in flight (a deeper ring): a counted
-// vmcnt and a raw barrier -- __syncthreads() would drain them (vmcnt(0))
-template <int N>
-__device__ __forceinline__ void dma_wait_publish_keep(bool keep) {
-  if (keep)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-  else
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+// the h3 kernel's dma_wait_publish: the same waits ahead of a raw barrier
+// (with __syncthreads() the compiler emits other code around the barrier;
+// this is the form the kernel was measured with)
+__device__ __forceinline__ void dma_wait_publish_raw() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 }
@@ -325,15 +322,14 @@ __global__ __launch_bounds__(NT, 3) void attn_fwd_f32x6_d64_kernel(
 // the one FMA that already turns a score into exp2 units; P <= 2^8 (deferred
 // rescale) needs no scale; the value scale is divided out with 1/l.
 constexpr int H3_STAGE = 4 * IMG;            // K hi, K lo, V hi, V lo
-constexpr int H3_RING = 2;  // stages; 3 (two tiles in flight) measured slower: 138 VGPRs, 802 vs 818 inf/s
-constexpr int H3_LDS_BYTES = H3_RING * H3_STAGE;  // 48 KiB
-constexpr int H3_WG_PER_CU = 4;  // 4-wave workgroups (HW = 4); HW = 8: 2 (134 VGPRs, 3 waves / SIMD; forcing
-                                 // 4 waves / SIMD -- 128 VGPRs, one spill -- fleet 797-799 vs 823-824 inf/s)
+constexpr int H3_LDS_BYTES = 2 * H3_STAGE;   // a 2-stage ring: 48 KiB
+constexpr int H3_WAVES = 8;                  // per workgroup, 32 query rows each
+constexpr int H3_WG_PER_CU = 2;  // 134 VGPRs, 3 waves / SIMD (forcing 4 waves / SIMD -- 128 VGPRs, one spill --
+                                 // fleet 797-799 vs 823-824 inf/s)
 
-// HW waves per workgroup (4 or 8) x 32 query rows; the 16 DMA pieces of a
-// key tile are spread over the waves (16 / HW each)
-template <bool PERSIST, int HW>
-__global__ __launch_bounds__(64 * HW, HW == 8 ? 2 : H3_WG_PER_CU) void attn_fwd_f32h3_d64_kernel(
+// the 16 DMA pieces of a key tile are spread over the waves (2 each)
+template <bool PERSIST>
+__global__ __launch_bounds__(64 * H3_WAVES, H3_WG_PER_CU) void attn_fwd_f32h3_d64_kernel(
     const float* __restrict__ q, const _Float16* __restrict__ kvs, float* __restrict__ o, int B, int H, int Sq,
     int Skv, int ld_in, long long bs_in, int ld_out, long long bs_out, float c, const float* __restrict__ kvsc,
     int nqb, int nsplit, float* __restrict__ part, _Float16* __restrict__ op, long long opl, float osc) {
@@ -370,7 +366,7 @@ __global__ __launch_bounds__(64 * HW, HW == 8 ? 2 : H3_WG_PER_CU) void attn_fwd_
 
   const int ntiles = (Skv + KVB - 1) / KVB;
   const int skvp = ntiles * KVB;
-  constexpr int PPW = 16 / HW, HQBLK = 32 * HW;
+  constexpr int PPW = 16 / H3_WAVES, HQBLK = 32 * H3_WAVES;
   int soff[PPW];  // staging: per-lane element offset of instruction i within a tile
 #pragma unroll
   for (int i = 0; i < PPW; ++i) {
@@ -457,12 +453,9 @@ __global__ __launch_bounds__(64 * HW, HW == 8 ? 2 : H3_WG_PER_CU) void attn_fwd_
         for (int i = 0; i < PPW; ++i) stage_piece(u, slot, i);
       }
     };
-    // the first H3_RING - 1 tiles in flight; tile t0 landed and published
+    // tile t0 in flight, then landed and published
 #pragma unroll
     for (int i = 0; i < PPW; ++i) stage_piece(t0, 0, i);
-#pragma unroll
-    for (int q = 1; q < H3_RING - 1; ++q)
-      if (t0 + q < t1) stage_tile(t0 + q, q);
 
     f32x16_t oacc[2];
 #pragma unroll
@@ -472,23 +465,20 @@ __global__ __launch_bounds__(64 * HW, HW == 8 ? 2 : H3_WG_PER_CU) void attn_fwd_
     }
     float m = 0.f, l = 0.f;
 
-    static_assert(H3_RING == 2 || H3_RING == 3, "ring depth");
-    dma_wait_publish_keep<PPW>(H3_RING == 3 && t0 + 1 < t1);
+    dma_wait_publish_raw();
 
     // the tile body; MASKED: the tail tile (keys past Skv masked).  Peeled out of
     // the main loop -- if-converted into it, the mask cost 48 VALU per tile
     auto tile = [&](int t, auto masked) {
       constexpr bool MASKED = decltype(masked)::value;
-      const int buf = (t - t0) % H3_RING;
-      // tile t + H3_RING - 1 into the slot tile t - 1 left (every wave passed
-      // the barrier that ended tile t - 1)
-      if (t + H3_RING - 1 < t1) stage_tile(t + H3_RING - 1, (t - t0 + H3_RING - 1) % H3_RING);
-      // at the end: tile t + 1 landed (the ring's newer tile may stay in flight)
-      const bool keep = H3_RING == 3 && t + 2 < t1;
+      const int buf = (t - t0) % 2;
+      // tile t + 1 into the slot tile t - 1 left (every wave passed the barrier
+      // that ended tile t - 1); at the end of this tile it has landed
+      if (t + 1 < t1) stage_tile(t + 1, (t - t0 + 1) % 2);
       // a wave whose 32 query rows all lie past Sq (the last query block of a
       // head, a query range) only stages and keeps the barriers
       if (!live) {
-        dma_wait_publish_keep<PPW>(keep);
+        dma_wait_publish_raw();
         return;
       }
       const unsigned char* kl = smem + buf * H3_STAGE;
@@ -557,7 +547,7 @@ __global__ __launch_bounds__(64 * HW, HW == 8 ? 2 : H3_WG_PER_CU) void attn_fwd_
           }
           oacc[db] = nos::mma3h(a, pf[s2], oacc[db]);
         }
-      dma_wait_publish_keep<PPW>(keep);
+      dma_wait_publish_raw();
     };
     const int tm = (Skv % KVB) ? max(t0, min(t1, ntiles - 1)) : t1;  // the tail tile, if any, is the last
     for (int t = t0; t < tm; ++t) tile(t, std::false_type{});
@@ -802,22 +792,17 @@ NOS_API int nos_attn_fwd_f32x6_presplit_d64(const float* q, float* o, int B, int
 
 namespace {
 
-// nos_attn_f32h3_set_waves; 8: the 28-tenant fleet 756 vs 743 inf/s over
-// 4 rounds (profiles/r04_h3_attn_waves_ab.json)
-int g_h3_waves = 8;
-
-template <int HW>
 int launch_h3(const float* q, const _Float16* kvs, float* o, int B, int H, int Sq, int Skv, int ld_in,
               long long bs_in, int ld_out, long long bs_out, float c, const float* kvsc, int nqb, int nsplit,
               float* part, _Float16* op, long long opl, float osc, hipStream_t stream) {
   const long long nwg = (long long)B * H * nqb * nsplit;
-  const int grid = nos_grid_for((const void*)attn_fwd_f32h3_d64_kernel<true, HW>, 64 * HW, H3_LDS_BYTES, nwg);
+  const int grid = nos_grid_for((const void*)attn_fwd_f32h3_d64_kernel<true>, 64 * H3_WAVES, H3_LDS_BYTES, nwg);
   if (grid < nwg)
-    hipLaunchKernelGGL((attn_fwd_f32h3_d64_kernel<true, HW>), dim3((unsigned)grid), dim3(64 * HW), H3_LDS_BYTES,
+    hipLaunchKernelGGL((attn_fwd_f32h3_d64_kernel<true>), dim3((unsigned)grid), dim3(64 * H3_WAVES), H3_LDS_BYTES,
                        stream, q,
                        kvs, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c, kvsc, nqb, nsplit, part, op, opl, osc);
   else
-    hipLaunchKernelGGL((attn_fwd_f32h3_d64_kernel<false, HW>), dim3((unsigned)nwg), dim3(64 * HW), H3_LDS_BYTES,
+    hipLaunchKernelGGL((attn_fwd_f32h3_d64_kernel<false>), dim3((unsigned)nwg), dim3(64 * H3_WAVES), H3_LDS_BYTES,
                        stream, q,
                        kvs, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c, kvsc, nqb, nsplit, part, op, opl, osc);
   return (int)hipGetLastError();
@@ -844,30 +829,18 @@ NOS_API int nos_attn_fwd_f32h3_presplit_d64(const float* q, float* o, int B, int
   if (op != nullptr && ((((uintptr_t)op) & 7) || opl < (long long)B * bs_out || !(osc > 0.f)))
     return (int)hipErrorInvalidValue;
   const float c = scale * 1.4426950408889634f;
-  const int hw = g_h3_waves;
-  const int nqb = (Sq + 32 * hw - 1) / (32 * hw);
+  const int nqb = (Sq + 32 * H3_WAVES - 1) / (32 * H3_WAVES);
   const long long nwg = (long long)B * H * nqb;
   const int skvp = (Skv + KVB - 1) / KVB * KVB;
-  const int nsplit = pick_split(nwg, skvp / KVB, hw == 8 ? 2 : H3_WG_PER_CU);
+  const int nsplit = pick_split(nwg, skvp / KVB, H3_WG_PER_CU);
   auto* kvs = static_cast<const _Float16*>(ws);
   float* part = reinterpret_cast<float*>(static_cast<unsigned char*>(ws) +
                                          ((long long)B * skvp * 6 * H * D * 2 + 15) / 16 * 16);
-  const int rc = hw == 8 ? launch_h3<8>(q, kvs, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c, kvsc, nqb, nsplit,
-                                        part, op, opl, osc, stream)
-                         : launch_h3<4>(q, kvs, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c, kvsc, nqb, nsplit,
-                                        part, op, opl, osc, stream);
+  const int rc = launch_h3(q, kvs, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c, kvsc, nqb, nsplit, part, op, opl,
+                           osc, stream);
   if (rc != 0 || nsplit == 1) return rc;
   const long long n4 = (long long)B * Sq * H * (D / 4);
   hipLaunchKernelGGL(merge_splits_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, part, o, B, H, Sq,
                      nsplit, ld_out, bs_out, n4, op, opl, osc);
   return (int)hipGetLastError();
-}
-
-// h3 attention workgroup size: 8 waves (default: 256 query rows, 2
-// workgroups per CU: each key tile is loaded once for twice the queries) or
-// 4 (128 rows, 4 per CU).  The results are bit-identical.
-NOS_API int nos_attn_f32h3_set_waves(int waves) {
-  if (waves != 4 && waves != 8) return (int)hipErrorInvalidValue;
-  g_h3_waves = waves;
-  return 0;
 }

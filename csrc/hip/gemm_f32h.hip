@@ -12,7 +12,7 @@
 //    written as hi / lo planes [2][M][K]; rinv[m] = 2^-e_m;
 //  * W' = the weight's rows on their own scales 2^f_n, split once per
 //    weight by the host (ops.split_f32_weight_h3); csc[n] = 2^-f_n;
-//  * 4 waves per workgroup (2 x 2, or 4 x 1: 32-row strips), 128 x 128
+//  * 4 waves per workgroup (2 x 2), 128 x 128
 //    tiles, BK = 32 per stage in a 2-deep LDS ring filled by LDS-DMA
 //    (global_load_lds_dwordx4; every plane as rows of 64 B, 16-byte chunks
 //    XOR-swizzled by (row >> 2) & 3 -- conflict-free fragment reads);
@@ -50,13 +50,12 @@ struct Batch {
   long long a = 0, rinv = 0, w = 0, csc = 0, c = 0, r = 0, bias = 0;  // bias: grouped convs' per-group rows
 };
 
-constexpr int BK = 32;  // K granule of the API (K % 32 == 0); stages are BKT = 32 or 16 deep
+constexpr int BK = 32;  // K depth of an LDS stage (two 16-deep MFMA steps); K % 32 == 0
 
-// 16-byte chunk swizzle of a plane row of CH chunks (BKT 32: 64 B rows, 4
-// chunks; BKT 16: 32 B rows, 2 chunks): 16 consecutive lanes reading the same
-// logical chunk of 16 consecutive rows hit 16 distinct 16-byte slots
-template <int CH>
-__device__ __forceinline__ int swz(int row) { return CH == 4 ? ((row >> 2) & 3) : ((row >> 3) & 1); }
+// 16-byte chunk swizzle of a plane row (64 B, 4 chunks): 16 consecutive lanes
+// reading the same logical chunk of 16 consecutive rows hit 16 distinct
+// 16-byte slots
+__device__ __forceinline__ int swz(int row) { return (row >> 2) & 3; }
 
 // the K / V columns (>= qcols) of a fused QKV projection as the h3
 // attention's planes kvs[b][s][K hi, K lo, V hi, V lo][hd], each head on
@@ -106,32 +105,27 @@ __device__ __forceinline__ void chan_merge(float& n, float& mean, float& m2, flo
   n = tot;
 }
 
-// BKT: K depth of an LDS stage (32: two 16-deep MFMA steps, or 16: one);
 // RS: stages in the ring (RS - 1 of them in flight ahead of the one computed)
 // BATCHED: the tile index spans nb batch elements (Batch strides); false: one
 // GEMM, no per-tile batch offsets (fewer live SGPRs in the hot path)
 // MODE: 0 A as planes (LDS-DMA); 1 A = LayerNorm(X) (LnIo); 2 row statistics out
-template <int BM, int BN, int WGM, int WGN, bool PERSIST, int BKT = 32, int RS = 2, int MODE = 0,
-          bool BATCHED = false>
-__global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3_kernel(
+template <int BM, int BN, int WGM, int WGN, bool PERSIST, int RS = 2, int MODE = 0, bool BATCHED = false>
+__global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_h3_kernel(
     const _Float16* __restrict__ Ap, int lda, long long aplane, const float* __restrict__ rinv, float rconst,
     const _Float16* __restrict__ Wp, int ldw, long long wplane, const float* __restrict__ csc,
     const float* __restrict__ bias, const float* __restrict__ R, int ldr0, float* __restrict__ C, int ldc0, int M,
     int N, int K, int epi, int tiles_m, int tiles_n, KvOut kv, PlaneOut po, Batch bt, LnIo ln) {
   constexpr int NW = WGM * WGN, MI = BM / (32 * WGM), NI = BN / (32 * WGN);
-  static_assert((NW == 4 || NW == 8) && MI >= 1 && NI >= 1, "4 or 8 waves");
-  constexpr int ROWB = BKT * 2, CH = ROWB / 16, RPP = 1024 / ROWB, NSTEP = BKT / 16;
-  static_assert((BKT == 32 || BKT == 16) && RS >= 2 && RS <= 4, "stage shape");
+  static_assert(NW == 4 && MI >= 1 && NI >= 1, "4 waves");
+  constexpr int ROWB = BK * 2, CH = ROWB / 16, RPP = 1024 / ROWB;
+  static_assert(RS == 2 || RS == 3, "ring depth");
   constexpr int TA = 2 * BM * ROWB, STAGE = TA + 2 * BN * ROWB;
   constexpr int APW = TA / 1024 / NW, WPW = 2 * BN * ROWB / 1024 / NW;  // 1 KiB DMA pieces per wave
   static_assert(APW * NW * 1024 == TA && WPW * NW * 1024 == 2 * BN * ROWB, "equal DMA count per wave");
   constexpr int LPS = APW + WPW;
   static_assert((RS - 2) * LPS < 64, "vmcnt range");
-  static_assert(MODE == 0 || (BM == 128 && BKT == 32 && !BATCHED &&
-                              (((BN == 128 || BN == 64) && NW == 4 && (RS == 2 || (MODE == 2 && RS == 3))) ||
-                               (MODE == 1 && BN == 256 && NW == 8 && RS == 2))),
-                "the LayerNorm hand-off runs 128 x 128 or 128 x 64 2 x 2 tiles (the producer also on a 3-deep ring); "
-                "the LN-in-A-load also 128 x 256 with 2 x 4 waves");
+  static_assert(MODE == 0 || (BM == 128 && !BATCHED && (BN == 128 || BN == 64) && (RS == 2 || (MODE == 2 && RS == 3))),
+                "the LayerNorm hand-off runs 128 x 128 or 128 x 64 tiles (the producer also on a 3-deep ring)");
   static_assert(MODE != 2 || BM * BN * 4 <= RS * STAGE, "the statistics tile fits the ring");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -141,7 +135,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
   const bool wide = (epi & EPI_WIDE) != 0;
   epi &= ~EPI_WIDE;
   const int ntiles1 = tiles_m * tiles_n, ntiles = BATCHED ? ntiles1 * bt.nb : ntiles1;
-  const int nk = K / BKT;
+  const int nk = K / BK;
   nos::XcdChunk chunk;
   if constexpr (PERSIST) {
     chunk = nos::xcd_chunk(blockIdx.x, gridDim.x, ntiles);
@@ -173,7 +167,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
         const int row = rb + lane / CH;
         int g = m0 + row;
         g = g < M ? g : M - 1;
-        glds16(Ab + plane * aplane + (long long)g * lda + k0 + (((lane % CH) ^ swz<CH>(row)) << 3),
+        glds16(Ab + plane * aplane + (long long)g * lda + k0 + (((lane % CH) ^ swz(row)) << 3),
                dst + plane * BM * ROWB + rb * ROWB);
       }
     };
@@ -185,7 +179,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
         const int row = rb + lane / CH;
         int g = n0 + row;
         g = g < N ? g : N - 1;
-        glds16(Wb + plane * wplane + (long long)g * ldw + k0 + (((lane % CH) ^ swz<CH>(row)) << 3),
+        glds16(Wb + plane * wplane + (long long)g * ldw + k0 + (((lane % CH) ^ swz(row)) << 3),
                dst + TA + plane * BN * ROWB + rb * ROWB);
       }
     };
@@ -213,7 +207,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
 #pragma unroll
         for (int p = 0; p < 2; ++p)
           f.a[i][p] = *reinterpret_cast<const f16x8_t*>(base + p * BM * ROWB + row * ROWB +
-                                                        (((NSTEP * s + h0) ^ swz<CH>(row)) << 4));
+                                                        (((2 * s + h0) ^ swz(row)) << 4));
       }
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
@@ -221,7 +215,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
 #pragma unroll
         for (int p = 0; p < 2; ++p)
           f.w[j][p] = *reinterpret_cast<const f16x8_t*>(base + TA + p * BN * ROWB + row * ROWB +
-                                                        (((NSTEP * s + h0) ^ swz<CH>(row)) << 4));
+                                                        (((2 * s + h0) ^ swz(row)) << 4));
       }
     };
     auto mma = [&](const Frag& f) {
@@ -234,7 +228,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
     if constexpr (MODE == 1) {
     // A = LayerNorm(X): thread t owns rows t/4 and 64 + t/4 of the tile and the
     // 8-deep k chunk t%4 of each stage (one 16-byte piece per plane and row)
-    constexpr int AR = BM * 4 / (64 * NW);   // rows per thread: 2 with 4 waves, 1 with 8
+    constexpr int AR = BM * 4 / (64 * NW);   // rows per thread
     constexpr int RSTEP = 64 * NW / 4;       // rows between a thread's rows
     const int q = tid & 3;
     float mul[AR], add[AR];
@@ -272,7 +266,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
         nos::split2h(f32x2_t{fmaf(u.z, mul[i], add[i]), fmaf(u.w, mul[i], add[i])}, h1, l1);
         nos::split2h(f32x2_t{fmaf(w.x, mul[i], add[i]), fmaf(w.y, mul[i], add[i])}, h2, l2);
         nos::split2h(f32x2_t{fmaf(w.z, mul[i], add[i]), fmaf(w.w, mul[i], add[i])}, h3, l3);
-        const int off = row * ROWB + ((q ^ swz<CH>(row)) << 4);
+        const int off = row * ROWB + ((q ^ swz(row)) << 4);
         *reinterpret_cast<f16x8_t*>(dst + off) = f16x8_t{h0.x, h0.y, h1.x, h1.y, h2.x, h2.y, h3.x, h3.y};
         *reinterpret_cast<f16x8_t*>(dst + BM * ROWB + off) = f16x8_t{l0.x, l0.y, l1.x, l1.y, l2.x, l2.y, l3.x, l3.y};
       }
@@ -282,8 +276,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     awrite(smem);
     if (nk > 1) {
-      aload(BKT);
-      stage_w(BKT, smem + STAGE);
+      aload(BK);
+      stage_w(BK, smem + STAGE);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -308,16 +302,16 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         if (kt + 2 < nk) {
-          aload((kt + 2) * BKT);
-          stage_w((kt + 2) * BKT, smem + (kt & 1) * STAGE);
+          aload((kt + 2) * BK);
+          stage_w((kt + 2) * BK, smem + (kt & 1) * STAGE);
         }
         load(smem + ((kt + 1) & 1) * STAGE, 0, fa);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    } else if constexpr (BKT == 32 && RS == 2) {
+    } else if constexpr (RS == 2) {
     stage(0, smem);
-    if (nk > 1) stage(BKT, smem + STAGE);
+    if (nk > 1) stage(BK, smem + STAGE);
     if (nk > 1) {
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");  // stage 0 landed, stage 1 in flight
     } else {
@@ -336,7 +330,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        if (kt + 2 < nk) stage((kt + 2) * BKT, smem + (kt & 1) * STAGE);
+        if (kt + 2 < nk) stage((kt + 2) * BK, smem + (kt & 1) * STAGE);
         load(smem + ((kt + 1) & 1) * STAGE, 0, fa);  // next stage's step 0 under step 1's MFMAs
       }
       mma(fb);
@@ -346,25 +340,20 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_h3
     // deep ring: RS - 1 stages in flight ahead of the one computed
 #pragma unroll
     for (int q = 0; q < RS - 1; ++q)
-      if (q < nk) stage(q * BKT, smem + q * STAGE);
+      if (q < nk) stage(q * BK, smem + q * STAGE);
     for (int kt = 0; kt < nk; ++kt) {
       // stage kt landed (later ones may stay in flight); every wave is done
       // with stage kt - 1, whose buffer stage kt + RS - 1 reuses
       wait_stages<LPS>(min(RS - 2, nk - 1 - kt));
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
-      if (kt + RS - 1 < nk) stage((kt + RS - 1) * BKT, smem + ((kt + RS - 1) % RS) * STAGE);
+      if (kt + RS - 1 < nk) stage((kt + RS - 1) * BK, smem + ((kt + RS - 1) % RS) * STAGE);
       const unsigned char* cur = smem + (kt % RS) * STAGE;
-      Frag f0;
+      Frag f0, f1;
       load(cur, 0, f0);
-      if constexpr (NSTEP == 2) {
-        Frag f1;
-        load(cur, 1, f1);
-        mma(f0);
-        mma(f1);
-      } else {
-        mma(f0);
-      }
+      load(cur, 1, f1);
+      mma(f0);
+      mma(f1);
     }
     }
     __syncthreads();  // every wave is done with the ring (the next tile's prologue)
@@ -694,12 +683,12 @@ struct H3Call {
   LnIo ln;
 };
 
-template <int BM, int BN, int WGM, int WGN, int BKT = 32, int RS = 2, bool BATCHED = false, int MODE = 0>
+template <int BM, int BN, int WGM, int WGN, int RS = 2, bool BATCHED = false, int MODE = 0>
 int launch_t(const H3Call& c, hipStream_t st) {
   const int tiles_m = (c.M + BM - 1) / BM, tiles_n = (c.N + BN - 1) / BN;
   const long long ntiles = (long long)tiles_m * tiles_n * c.bt.nb;
   if (ntiles > (1LL << 30)) return (int)hipErrorInvalidValue;
-  const size_t lds = RS * (size_t)(2 * BM * BKT * 2 + 2 * BN * BKT * 2);
+  const size_t lds = RS * (size_t)(2 * BM * BK * 2 + 2 * BN * BK * 2);
   constexpr int NT = 64 * WGM * WGN;
   const int epi = !BATCHED && wide_planes_ok(c.kv, c.po) ? c.epi | EPI_WIDE : c.epi;
   auto launch = [&](auto* kernel, long long grid) {
@@ -712,20 +701,13 @@ int launch_t(const H3Call& c, hipStream_t st) {
   // form (a CU slice's capped grid) needs 21 more VGPRs than 256 and spilled
   // to scratch; the CU mask bounds where the tiles run either way
   if constexpr (!BATCHED) {
-    auto* persistent = gemm_h3_kernel<BM, BN, WGM, WGN, true, BKT, RS, MODE, BATCHED>;
+    auto* persistent = gemm_h3_kernel<BM, BN, WGM, WGN, true, RS, MODE, BATCHED>;
     const int grid = nos_grid_for((const void*)persistent, NT, lds, ntiles);
     if (grid < ntiles) return launch(persistent, grid);
   }
-  return launch(gemm_h3_kernel<BM, BN, WGM, WGN, false, BKT, RS, MODE, BATCHED>, ntiles);
+  return launch(gemm_h3_kernel<BM, BN, WGM, WGN, false, RS, MODE, BATCHED>, ntiles);
 }
 
-// nos_gemm_f32h3_set_layout: 0: 128x128, 4 x 1 waves; 1: 128x128, 2 x 2;
-// 2: 256x128, 4 x 2 (8 waves); 3: 128x128 4 x 1, 3-deep ring of BK-32
-// stages (96 KiB); 4 / 5: 128x128 4 x 1 / 2 x 2, 4-deep ring of BK-16 stages.
-// Default 2 x 2: 64 x 64 per wave reads 8 KiB of fragments per 12 MFMAs
-// (4 x 1: 10 KiB); 28-tenant fleet 679.9 / 679.8 vs 679.0 / 676.2 inf/s,
-// the deeper rings 605-635 (profiles/r04_h3_layout_ab.json)
-int g_layout = 1;
 // plain fp32-C GEMMs (no KV / plane output, N % 4 == 0, aligned C / R) through
 // the LDS epilogue of MODE 2 (float4 stores and residual loads along rows)
 bool g_lds_epi = true;  // 28-tenant fleet 801 vs 799 inf/s, batch-1 residual GEMMs 15-18 % faster
@@ -737,9 +719,6 @@ int g_hot_ring = 2;
 // residual GEMMs of a transformer): 128, or 64 (48 KiB ring: three workgroups
 // per CU); the statistics parts are this many columns wide
 int g_hot_bn = 128;
-// LN-in-A-load GEMMs that write the next GEMM's planes (fc1 -> fc2) on 128 x 256
-// tiles with 8 waves: half the per-workgroup A normalise-and-split work per MFMA
-bool g_lna_wide = false;
 
 // ------------------------------------------------------------ row split
 // LPR lanes per row (64: a wave; 32: a half-wave, two rows per wave), the
@@ -953,12 +932,6 @@ NOS_API int nos_gemm_f32h3_set_lds_epilogue(int on) {
   return 0;
 }
 
-NOS_API int nos_gemm_f32h3_set_layout(int layout) {
-  if (layout < 0 || layout > 7) return (int)hipErrorInvalidValue;
-  g_layout = layout;
-  return 0;
-}
-
 NOS_API int nos_gemm_f32h3_set_hot_bn(int bn) {
   if (bn != 128 && bn != 64) return (int)hipErrorInvalidValue;
   g_hot_bn = bn;
@@ -966,11 +939,6 @@ NOS_API int nos_gemm_f32h3_set_hot_bn(int bn) {
 }
 
 NOS_API int nos_gemm_f32h3_hot_bn() { return g_hot_bn; }
-
-NOS_API int nos_gemm_f32h3_set_lna_wide(int on) {
-  g_lna_wide = on != 0;
-  return 0;
-}
 
 NOS_API int nos_gemm_f32h3_set_hot_ring(int rs) {
   if (rs != 2 && rs != 3) return (int)hipErrorInvalidValue;
@@ -1039,25 +1007,16 @@ bool lds_epilogue_ok(const H3Call& c) {
 // the LDS-epilogue / row-statistics GEMMs (MODE 2) on the tile and ring of
 // nos_gemm_f32h3_set_hot_bn / nos_gemm_f32h3_set_hot_ring
 int launch_hot(const H3Call& c, hipStream_t st) {
-  if (g_hot_bn == 64) return launch_t<128, 64, 2, 2, 32, 2, false, 2>(c, st);
-  if (g_hot_ring == 3) return launch_t<128, 128, 2, 2, 32, 3, false, 2>(c, st);
-  return launch_t<128, 128, 2, 2, 32, 2, false, 2>(c, st);
+  if (g_hot_bn == 64) return launch_t<128, 64, 2, 2, 2, false, 2>(c, st);
+  if (g_hot_ring == 3) return launch_t<128, 128, 2, 2, 3, false, 2>(c, st);
+  return launch_t<128, 128, 2, 2, 2, false, 2>(c, st);
 }
 
 // batched: the BATCHED instantiation (batch strides, per-row bias, residual
 // before the activation -- kept out of the one-GEMM kernels' registers)
 int run_h3(const H3Call& c, hipStream_t st, bool batched = false) {
-  if (batched) return launch_t<128, 128, 2, 2, 32, 2, true>(c, st);  // convs, matmuls: the default layout
-  switch (g_layout) {  // nos_gemm_f32h3_set_layout
-    case 3: return launch_t<128, 128, 4, 1, 32, 3>(c, st);
-    case 4: return launch_t<128, 128, 4, 1, 16, 4>(c, st);
-    case 5: return launch_t<128, 128, 2, 2, 16, 4>(c, st);
-    case 7: return launch_t<128, 64, 2, 2>(c, st);  // 48 KiB ring: three workgroups per CU
-    case 6: return launch_t<128, 128, 2, 2, 32, 3>(c, st);
-    case 2: return launch_t<256, 128, 4, 2>(c, st);
-    case 1: return g_lds_epi && lds_epilogue_ok(c) ? launch_hot(c, st) : launch_t<128, 128, 2, 2>(c, st);
-    default: return launch_t<128, 128, 4, 1>(c, st);
-  }
+  if (batched) return launch_t<128, 128, 2, 2, 2, true>(c, st);
+  return g_lds_epi && lds_epilogue_ok(c) ? launch_hot(c, st) : launch_t<128, 128, 2, 2>(c, st);
 }
 
 // K columns of an operand's fp16 planes [2][rows][ld] (plane stride `plane`), rows of 16-byte chunks
@@ -1231,9 +1190,8 @@ NOS_API int nos_gemm_f32h3_lna(const float* X, int ldx, const void* stats, int n
   c.ln.pw = pw;
   c.ln.eps = eps;
   c.ln.sc = ldexpf(1.f, eln);
-  // 128 x 128 (or 128 x 256 for plane outputs, g_lna_wide): the LN-in-A-load normalises and
-  // splits its A tile per workgroup, so 128 x 64 tiles doubled that VALU work (fleet 760 vs
-  // 800 inf/s, profiles/r06_hot_bn_ab.json)
-  if (g_lna_wide && P != nullptr) return launch_t<128, 256, 2, 4, 32, 2, false, 1>(c, stream);
-  return launch_t<128, 128, 2, 2, 32, 2, false, 1>(c, stream);
+  // 128 x 128 whatever g_hot_bn: the LN-in-A-load normalises and splits its A tile per
+  // workgroup, so 128 x 64 tiles doubled that VALU work (fleet 760 vs 800 inf/s,
+  // profiles/r06_hot_bn_ab.json)
+  return launch_t<128, 128, 2, 2, 2, false, 1>(c, stream);
 }

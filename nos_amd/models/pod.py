@@ -171,15 +171,11 @@ def kernel_config(memory_fraction: float | None, env: dict | None = None, cu_bud
             "ln_handoff": env.get("NOS_AMD_LN_HANDOFF") or "on",
             # plain fp32-C h3 GEMMs store C through LDS (float4 rows): 801 vs 799 inf/s
             "h3_epilogue": env.get("NOS_AMD_H3_EPILOGUE") or "lds",
-            # h3 GEMM tile layout (ops.set_gemm_f32h3_layout; the LN hand-off GEMMs keep 2x2)
-            "h3_layout": env.get("NOS_AMD_H3_LAYOUT") or "2x2",
             # LDS ring of the residual (row-statistics) h3 GEMMs: "2" or "3" stages
             "h3_hot_ring": env.get("NOS_AMD_H3_HOT_RING") or "2",
             # tile width of the residual (row-statistics) h3 GEMMs: 128 x 128 (two workgroups per CU);
             # 128 x 64 (48 KiB, three) measured 2 % slower with the LN hand-off (profiles/r06_hot_bn_ab.json)
-            "h3_hot_bn": env.get("NOS_AMD_H3_HOT_BN") or "128",
-            # fc1-class LN-GEMMs (plane outputs) on 128 x 256 tiles, 8 waves
-            "h3_lna_wide": env.get("NOS_AMD_H3_LNA_WIDE") or "off"}
+            "h3_hot_bn": env.get("NOS_AMD_H3_HOT_BN") or "128"}
 
 
 def slice_cu_budget(env: dict | None = None) -> int:

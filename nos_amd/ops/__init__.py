@@ -473,36 +473,9 @@ def set_gemm_f32h3_hot_bn(bn: int) -> None:
     _lib.check(_lib.lib().nos_gemm_f32h3_set_hot_bn(int(bn)), "nos_gemm_f32h3_set_hot_bn")
 
 
-def set_gemm_f32h3_lna_wide(on: bool) -> None:
-    """LN-in-A-load GEMMs writing the next GEMM's planes (fc1 -> fc2) on
-    128 x 256 tiles with 8 waves (half the A normalise-and-split work per
-    MFMA) instead of 128 x 128 -- A/B; the results are bit-identical."""
-    _lib.check(_lib.lib().nos_gemm_f32h3_set_lna_wide(int(bool(on))), "nos_gemm_f32h3_set_lna_wide")
-
-
 def stats_pw() -> int:
     """Column width of a row-statistics part (the producer GEMM's tile width)."""
     return int(_lib.lib().nos_gemm_f32h3_hot_bn())
-
-
-def set_gemm_f32h3_layout(layout: str) -> None:
-    """h3 GEMM tiles / waves: ``"2x2"`` (default: 128x128, 64x64 per wave),
-    ``"4x1"`` (128x128, 32-row strips, each wave reads the whole W tile),
-    ``"256x128"`` (8 waves of 64x64, one workgroup per CU), ``"4x1r3"``
-    (3-deep ring of BK-32 stages), ``"4x1k16"`` / ``"2x2k16"`` (4-deep ring
-    of BK-16 stages), ``"2x2r3"`` (2x2, 3-deep BK-32 ring), ``"2x2n64"``
-    (128 x 64 tiles, 48 KiB: three workgroups per CU) -- A/B; the
-    results are bit-identical."""
-    _lib.check(_lib.lib().nos_gemm_f32h3_set_layout({"4x1": 0, "2x2": 1, "256x128": 2, "4x1r3": 3, "4x1k16": 4,
-                                                     "2x2k16": 5, "2x2r3": 6, "2x2n64": 7}[layout]),
-               "nos_gemm_f32h3_set_layout")
-
-
-def set_attention_f32h3_waves(waves: int) -> None:
-    """h3 attention workgroups of 8 waves (default: 256 query rows, 2 per CU,
-    each key tile loaded once for twice the queries; fleet 756 vs 743 inf/s)
-    or 4 (128 rows, 4 per CU); bit-identical results."""
-    _lib.check(_lib.lib().nos_attn_f32h3_set_waves(int(waves)), "nos_attn_f32h3_set_waves")
 
 
 def set_gemm_f32x6_pipeline(on: bool) -> None:
@@ -631,10 +604,8 @@ def apply_kernel_config(cfg: dict) -> None:
     set_gemm_f32x6_tile(cfg["gemm_f32x6_tile"])
     set_ln_handoff(cfg.get("ln_handoff", "on") == "on")
     set_gemm_f32h3_lds_epilogue(cfg.get("h3_epilogue", "lds") == "lds")
-    set_gemm_f32h3_layout(cfg.get("h3_layout", "2x2"))
     set_gemm_f32h3_hot_ring(int(cfg.get("h3_hot_ring", "2")))
     set_gemm_f32h3_hot_bn(int(cfg.get("h3_hot_bn", "128")))
-    set_gemm_f32h3_lna_wide(cfg.get("h3_lna_wide", "off") == "on")
 
 
 @torch.no_grad()
@@ -996,5 +967,5 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | 
     return out
 
 
-__all__ = ["set_ln_handoff", "ln_handoff_active", "set_f32_math", "f32_math", "h3_head_scales", "linear_ln_qkv_h3", "split_f32_weight_h3", "set_gemm_f32h3_layout", "set_gemm_f32h3_hot_ring", "set_gemm_f32h3_hot_bn", "set_gemm_f32h3_lna_wide", "stats_pw", "H3Planes", "set_attention_f32h3_waves", "linear_planes", "linear_ln_to_planes", "h3_planes_active", "attention_presplit_h3", "ln_qkv_fusable", "ln_qkv_attention", "set_gemm_f32x6_tile", "set_gemm_f32x6_pipeline", "linear_ln_qkv_x6", "attention_presplit", "split_f32_weight", "split_bf16x3", "set_cu_budget", "cu_budget", "set_gemm_policy", "set_gemm_persistent", "linear", "linear_ln", "fold_layernorm", "layernorm", "attention", "attention_qkv", "linear_ref",
+__all__ = ["set_gemm_f32h3_hot_ring", "set_gemm_f32h3_hot_bn", "set_ln_handoff", "ln_handoff_active", "set_f32_math", "f32_math", "h3_head_scales", "linear_ln_qkv_h3", "split_f32_weight_h3", "stats_pw", "H3Planes", "linear_planes", "linear_ln_to_planes", "h3_planes_active", "attention_presplit_h3", "ln_qkv_fusable", "ln_qkv_attention", "set_gemm_f32x6_tile", "set_gemm_f32x6_pipeline", "linear_ln_qkv_x6", "attention_presplit", "split_f32_weight", "split_bf16x3", "set_cu_budget", "cu_budget", "set_gemm_policy", "set_gemm_persistent", "linear", "linear_ln", "fold_layernorm", "layernorm", "attention", "attention_qkv", "linear_ref",
            "linear_ln_ref", "layernorm_ref", "attention_ref"]

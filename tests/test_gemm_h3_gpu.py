@@ -101,23 +101,6 @@ def test_h3_linear_layernorm(M, N, K, act):
     assert errs["h3"] <= 1.5 * errs["exact"] + 1e-6 * max(1.0, ref.abs().max().item()), errs
 
 
-def test_h3_wave_layouts_are_bit_identical():
-    torch.manual_seed(2)
-    x = torch.randn(1000, 384, device=DEV)
-    w = torch.randn(384, 384, device=DEV) * 0.05
-    b = torch.randn(384, device=DEV)
-    outs = []
-    lays = ("4x1", "2x2", "256x128", "4x1r3", "4x1k16", "2x2k16", "2x2r3", "2x2n64")
-    for lay in lays:
-        ops.set_gemm_f32h3_layout(lay)
-        try:
-            outs.append(_with_math("h3", lambda: ops.linear(x, w, b, act="gelu", residual=x)))
-        finally:
-            ops.set_gemm_f32h3_layout("2x2")
-    for lay, o in zip(lays[1:], outs[1:]):
-        assert torch.equal(outs[0], o), lay
-
-
 @pytest.mark.parametrize("B,S,H", [(1, 3401, 6), (2, 77, 3)])
 def test_h3_qkv_projection_with_h3_attention(B, S, H):
     """The whole h3 path (LN pre-pass, h3 QKV GEMM writing the fp16 K / V

@@ -75,8 +75,13 @@ def test_h3_gemm_entry_rejects(lib, fn, what, bad):
     assert getattr(lib, fn)(*args.values()) == INVALID
 
 
-def test_h3_layout_setter_rejects_unknown_codes(lib):
-    assert lib.nos_gemm_f32h3_set_layout(9) == INVALID
+def test_retired_h3_switches_are_gone_from_the_library(lib):
+    """The A/B switches whose variants lost (docs/kernels.md) have no entry
+    point left; the statistics part width defaults to 128."""
+    for name in ("nos_gemm_f32h3_set_layout", "nos_gemm_f32h3_set_lna_wide", "nos_attn_f32h3_set_waves"):
+        assert not hasattr(lib, name), name
+    assert lib.nos_gemm_f32h3_hot_bn() == 128
+    # the two switches that remain still refuse unknown codes
     assert lib.nos_gemm_f32h3_set_hot_bn(96) == INVALID
     assert lib.nos_gemm_f32h3_set_hot_ring(4) == INVALID
 
@@ -116,16 +121,15 @@ def applied(monkeypatch):
 
 # every native setter once, with the codes of the named values (ops.set_*)
 _WHOLE = [("nos_attn_f32_set_variant", 0), ("nos_attn_f32x6_set_kvsplit", 0), ("nos_gemm_f32_set_policy", 1),
-          ("nos_gemm_f32h3_set_hot_bn", 128), ("nos_gemm_f32h3_set_hot_ring", 2), ("nos_gemm_f32h3_set_layout", 1),
-          ("nos_gemm_f32h3_set_lds_epilogue", 1), ("nos_gemm_f32h3_set_lna_wide", 0), ("nos_gemm_f32x6_set_tile", -1),
-          ("nos_gemm_set_policy", 1)]
+          ("nos_gemm_f32h3_set_hot_bn", 128), ("nos_gemm_f32h3_set_hot_ring", 2),
+          ("nos_gemm_f32h3_set_lds_epilogue", 1), ("nos_gemm_f32x6_set_tile", -1), ("nos_gemm_set_policy", 1)]
 
 
 def test_apply_kernel_config_reaches_every_setter_once(applied):
     from nos_amd.models.pod import kernel_config
 
     whole = kernel_config(None, {})
-    assert len(whole) == 11  # the keys of tests/test_podbench.py::test_pod_kernel_config_follows_the_slice
+    assert len(whole) == 9  # the keys of tests/test_podbench.py::test_pod_kernel_config_follows_the_slice
     assert applied(whole) == (_WHOLE, ("h3", True, "h3"))
     # the 36 / 288 slice: throughput bf16 tiles, small fp32 tiles, keys never split, x6 GEMMs on 128 x 128
     frac = dict(_WHOLE, nos_gemm_set_policy=0, nos_gemm_f32_set_policy=2, nos_attn_f32x6_set_kvsplit=1,
@@ -134,11 +138,9 @@ def test_apply_kernel_config_reaches_every_setter_once(applied):
     # every key reaches its setter: a config that differs from the defaults everywhere
     env = {"NOS_AMD_GEMM_POLICY": "wide", "NOS_AMD_GEMM_F32_POLICY": "throughput", "NOS_AMD_ATTN_F32_VARIANT": "w4k32",
            "NOS_AMD_F32_MATH": "x6", "NOS_AMD_X6_TILE": "128x64", "NOS_AMD_LN_HANDOFF": "off",
-           "NOS_AMD_H3_EPILOGUE": "regs", "NOS_AMD_H3_LAYOUT": "4x1", "NOS_AMD_H3_HOT_RING": "3",
-           "NOS_AMD_H3_HOT_BN": "64", "NOS_AMD_H3_LNA_WIDE": "on"}
+           "NOS_AMD_H3_EPILOGUE": "regs", "NOS_AMD_H3_HOT_RING": "3", "NOS_AMD_H3_HOT_BN": "64"}
     other = [("nos_attn_f32_set_variant", 3), ("nos_gemm_f32_set_policy", 0), ("nos_gemm_f32h3_set_hot_bn", 64),
-             ("nos_gemm_f32h3_set_hot_ring", 3), ("nos_gemm_f32h3_set_layout", 0),
-             ("nos_gemm_f32h3_set_lds_epilogue", 0), ("nos_gemm_f32h3_set_lna_wide", 1),
+             ("nos_gemm_f32h3_set_hot_ring", 3), ("nos_gemm_f32h3_set_lds_epilogue", 0),
              ("nos_gemm_f32x6_set_tile", 3), ("nos_gemm_set_policy", 4)]
     assert applied(kernel_config(None, env)) == (other, ("x6", False, "w4k32"))
 

@@ -1,4 +1,4 @@
-# rocprofv3 PMC passes over the h3 GEMM (2x2 / 4x1), the LN row split and h3 attention
+# rocprofv3 PMC passes over the h3 GEMM, the LN row split and h3 attention
 # (tools/h3_pmc_once.py).  usage (GPU box, repo root): bash tools/gpu/pmc_h3.sh <tag>
 set -o pipefail
 R=$PWD

@@ -13,7 +13,3 @@ one bf16_28 --tenants 28 --window 10 --dtype bf16 || exit 1
 one mix3 --mix yolos:16,resnet:6,llama:6 --window 10 || exit 1
 one fp32_28_b --tenants 28 --window 10 || exit 1
 one bf16_28_b --tenants 28 --window 10 --dtype bf16 || exit 1
-# ring-depth A/B on the MODE-0 GEMMs (LN hand-off off, so every h3 GEMM takes the layout)
-for lay in 2x2 2x2k16 4x1r3; do
-  NOS_AMD_LN_HANDOFF=off one nolnh_$lay --tenants 28 --window 10 --h3-layout $lay || exit 1
-done

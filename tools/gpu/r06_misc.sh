@@ -1,5 +1,5 @@
 # Strided unary / host-copy tests, the fleet's kernel stats (no per-inference
-# at::native copy left), then the h3 attention waves A/B (8 vs 4) and a bf16 fleet.
+# at::native copy left), then a bf16 fleet.
 set -o pipefail
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06_misc; mkdir -p $O
@@ -19,8 +19,4 @@ one() {  # tag, args
   timeout -k 10 300 python3 tools/podserver_once.py --tenants 28 --window 10 "$@" > $O/$tag.json 2> $O/$tag.err || { echo "$tag failed"; tail -5 $O/$tag.err; return 1; }
   python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], d['inf_per_s'], d['sclk_mhz'], round(d['inf_per_s']/d['sclk_mhz'],4))" $O/$tag.json $tag
 }
-for r in 1 2; do
-  one w8_r$r --h3-attn-waves 8 || exit 1
-  one w4_r$r --h3-attn-waves 4 || exit 1
-done
 one bf16 --dtype bf16 || exit 1

@@ -1,7 +1,7 @@
 """h3 kernels at batch-8 YOLOS shapes for rocprofv3 PMC passes
-(tools/gpu/pmc_h3.sh): the h3 GEMM (2x2 and 4x1 waves) at the qkv and fc2
-shapes, the LN row-split pre-pass and the h3 attention without key splits;
-three launches each, told apart by kernel name and dispatch order."""
+(tools/gpu/pmc_h3.sh): the h3 GEMM at the qkv and fc2 shapes, the LN
+row-split pre-pass and the h3 attention without key splits; three launches
+each, told apart by kernel name and dispatch order."""
 from __future__ import annotations
 
 import sys
@@ -23,11 +23,8 @@ def main() -> None:
         x = torch.randn(M, K, device="cuda")
         w = torch.randn(N, K, device="cuda") * 0.05
         o = torch.empty(M, N, device="cuda")
-        for lay in ("2x2", "4x1"):
-            ops.set_gemm_f32h3_layout(lay)
-            for _ in range(3):
-                ops.linear(x, w, out=o)
-    ops.set_gemm_f32h3_layout("2x2")
+        for _ in range(3):
+            ops.linear(x, w, out=o)
     ops.set_attention_f32_variant("h3n")
     x = torch.randn(8, S, hid, device="cuda")
     w = torch.randn(3 * hid, hid, device="cuda") * 0.05

@@ -93,15 +93,10 @@ def main() -> None:
     ap.add_argument("--slice-gb", type=float, default=10.0)
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--pipeline", type=int, default=1, help="x6 GEMM software-pipelined K loop (1) or plain (0)")
-    ap.add_argument("--h3-layout", default=None, choices=["4x1", "2x2", "256x128", "4x1r3", "4x1k16", "2x2k16", "2x2r3", "2x2n64"],
-                    help="h3 GEMM tile / wave layout / ring (NOS_AMD_H3_LAYOUT: the server's kernel config)")
     ap.add_argument("--h3-hot-ring", default=None, choices=["2", "3"],
                     help="LDS ring of the residual / row-statistics h3 GEMMs (NOS_AMD_H3_HOT_RING)")
     ap.add_argument("--h3-hot-bn", default=None, choices=["64", "128"],
                     help="tile width of the LN hand-off h3 GEMMs (NOS_AMD_H3_HOT_BN)")
-    ap.add_argument("--h3-lna-wide", default=None, choices=["on", "off"],
-                    help="fc1-class LN-GEMMs on 128 x 256 tiles, 8 waves (NOS_AMD_H3_LNA_WIDE)")
-    ap.add_argument("--h3-attn-waves", type=int, default=8, choices=[4, 8], help="h3 attention waves per workgroup")
     ap.add_argument("--lds-epi", type=int, default=None, help="plain fp32-C h3 GEMMs store C through LDS (1) or "
                     "from the MFMA registers (0) (NOS_AMD_H3_EPILOGUE: the server's kernel config)")
     ap.add_argument("--mix", default="", help="heterogeneous tenants instead of --tenants YOLOS pods, e.g. "
@@ -119,12 +114,8 @@ def main() -> None:
     os.environ["GPU_MAX_HW_QUEUES"] = str(min(a.hw_queues or (a.lanes + a.priority_lanes), 32))
     # kernel-config A/B knobs go through the server's config (env), which it re-applies around every
     # capture -- a process-wide setter called after start() would be undone by the first registration
-    if a.h3_layout is not None:
-        os.environ["NOS_AMD_H3_LAYOUT"] = a.h3_layout
     if a.h3_hot_ring is not None:
         os.environ["NOS_AMD_H3_HOT_RING"] = a.h3_hot_ring
-    if a.h3_lna_wide is not None:
-        os.environ["NOS_AMD_H3_LNA_WIDE"] = a.h3_lna_wide
     if a.h3_hot_bn is not None:
         os.environ["NOS_AMD_H3_HOT_BN"] = a.h3_hot_bn
     if a.lds_epi is not None:
@@ -139,7 +130,6 @@ def main() -> None:
     from nos_amd import ops
 
     ops.set_gemm_f32x6_pipeline(bool(a.pipeline))  # process-wide: every capture below
-    ops.set_attention_f32h3_waves(a.h3_attn_waves)
     try:
         t0 = time.monotonic()
         clients = [PodClient(path, connect_timeout_s=30) for _ in range(a.tenants)]
@@ -248,7 +238,7 @@ def main() -> None:
                           "server_compile_ms_p50": sorted(r["compile"].get("compile_ms", 0) for r in reps)[len(reps) // 2],
                           "inf_per_s": round(sum(done) / (w1 - w0), 2),
                           "min_done": min(done), "max_done": max(done), "solo_replays": solo,
-                          "kernel_config": srv.kernel_config, "pipeline": a.pipeline, "h3_layout": a.h3_layout, "lds_epi": a.lds_epi,
+                          "kernel_config": srv.kernel_config, "pipeline": a.pipeline, "lds_epi": a.lds_epi,
                           "sclk_mhz": sclk}), flush=True)
     finally:
         srv.stop()
