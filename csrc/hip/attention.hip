@@ -279,7 +279,7 @@ NOS_API int nos_attn_fwd_d64(const void* q, const void* k, const void* v, void* 
   if ((ld_in % 8) != 0 || (ld_out % 4) != 0) return (int)hipErrorInvalidValue;
   const int nqb = (Sq + QBLK - 1) / QBLK;
   const int nwg = B * H * nqb;
-  const float c = scale * 1.4426950408889634f;
+  const float c = scale * nos::LOG2E;
   hipLaunchKernelGGL(attn_fwd_d64_kernel, dim3(nwg), dim3(NT), LDS_BYTES, stream, (const unsigned short*)q,
                      (const unsigned short*)k, (const unsigned short*)v, (unsigned short*)o, B, H, Sq, Skv, ld_in,
                      bs_in, ld_out, bs_out, c, nqb);

@@ -283,14 +283,9 @@ int launch(const float* q, const float* k, const float* v, float* o, int B, int 
   const long long nwg = (long long)B * H * nqb;
   if (nwg > (1LL << 30)) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)G * 2 * 2 * KVB * ROW_BYTES;
-  const int grid = nos_grid_for((const void*)attn_fwd_f32_d64_kernel<W, KVB, G, OCC, true>, 64 * W * G, lds, nwg);
-  if (grid < nwg)
-    hipLaunchKernelGGL((attn_fwd_f32_d64_kernel<W, KVB, G, OCC, true>), dim3((unsigned)grid), dim3(64 * W * G), lds,
-                       stream, q, k, v, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c, nqb);
-  else
-    hipLaunchKernelGGL((attn_fwd_f32_d64_kernel<W, KVB, G, OCC, false>), dim3((unsigned)nwg), dim3(64 * W * G), lds,
-                       stream, q, k, v, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c, nqb);
-  return (int)hipGetLastError();
+  return nos::launch_items(attn_fwd_f32_d64_kernel<W, KVB, G, OCC, true>, attn_fwd_f32_d64_kernel<W, KVB, G, OCC, false>,
+                           64 * W * G, lds, nwg, stream, q, k, v, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c,
+                           nqb);
 }
 
 // 0 auto, 1: 4 waves x 64-key tiles, 2: the same with 2 wave groups (split keys),
@@ -319,7 +314,7 @@ NOS_API int nos_attn_fwd_f32_d64(const float* q, const float* k, const float* v,
   if (ld_in < H * D || ld_out < H * D || (ld_in & 3) || (ld_out & 3) || (bs_in & 3) || (bs_out & 3))
     return (int)hipErrorInvalidValue;
   if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) return (int)hipErrorInvalidValue;
-  const float c = scale * 1.4426950408889634f;
+  const float c = scale * nos::LOG2E;
   // auto: 2 wave groups when the grid leaves CUs without a workgroup (one pod
   // at B=1: 162 workgroups, 240 vs 269 us), else 32-key tiles at 4 waves per
   // SIMD (B=8: 1298 vs 1357 us for 64-key tiles at 2;

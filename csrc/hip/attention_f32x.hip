@@ -32,6 +32,8 @@
 //    as in attention_f32.hip; PERSIST: slice-sized grid (nos::xcd_chunk).
 #include <type_traits>
 
+#include "attn_d64_planes.h"
+#include "attn_split.h"
 #include "common.h"
 #include "lds_pipe.h"
 #include "split_bf16.h"
@@ -43,7 +45,7 @@ constexpr int D = 64;
 constexpr int W = 4;                    // waves per workgroup
 constexpr int NT = 64 * W;
 constexpr int QBLK = 32 * W;            // query rows per workgroup
-constexpr int KVB = 32;                 // keys per tile
+using nos::kvp::KVB;                    // keys per tile
 constexpr int IMG = KVB * D * 2;        // one bf16 piece image: 4 KiB
 constexpr int STAGE = 6 * IMG;          // K0 K1 K2 V0 V1 V2
 constexpr int LDS_BYTES = 2 * STAGE;    // 48 KiB ring
@@ -116,7 +118,7 @@ __global__ __launch_bounds__(NT, 3) void attn_fwd_f32x6_d64_kernel(
     voff[db] = (4 * hh + tq) * 128 + (((4 * (db ^ vlb)) + 2 * g16 + (tp >> 1)) << 4) + 8 * (tp & 1);
 
   const int ntiles = (Skv + KVB - 1) / KVB;
-  const int skvp = ntiles * KVB;
+  const int skvp = nos::kvp::padded_keys(Skv);
   int soff[6];  // staging: per-lane element offset of instruction i within a tile
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
@@ -124,7 +126,7 @@ __global__ __launch_bounds__(NT, 3) void attn_fwd_f32x6_d64_kernel(
     const int plane = p >> 2;
     const int row = (p & 3) * 8 + (lane >> 3);
     const int lc = (lane & 7) ^ (plane < 3 ? kswz(row) : vswz(row));
-    soff[i] = (row * 6 + plane) * ldh + lc * 8;
+    soff[i] = (row * nos::kvp::X6 + plane) * ldh + lc * 8;
   }
 
   for (int w = chunk.first; w < chunk.end; w += chunk.step) {
@@ -170,13 +172,13 @@ __global__ __launch_bounds__(NT, 3) void attn_fwd_f32x6_d64_kernel(
     // The tail tile's rows past Skv re-read the last key's planes (finite
     // values; the -inf mask makes their P exactly 0), so the padding rows of
     // the planes are never read and need no zeroing (no memset per call).
-    const unsigned short* pb = kvs + (long long)b * skvp * (6 * ldh) + hd * D;
+    const unsigned short* pb = nos::kvp::batch_planes<nos::kvp::X6>(kvs, b, skvp, ldh) + hd * D;
     auto stage_piece = [&](int t, int buf, int i) {
       const int p = wid * 6 + i;
-      long long off = (long long)t * (KVB * 6) * ldh + soff[i];
+      long long off = (long long)t * (KVB * nos::kvp::X6) * ldh + soff[i];
       if ((t + 1) * KVB > Skv) {
         const int over = t * KVB + (p & 3) * 8 + (lane >> 3) - (Skv - 1);
-        if (over > 0) off -= (long long)over * 6 * ldh;
+        if (over > 0) off -= (long long)over * nos::kvp::X6 * ldh;
       }
       glds16(pb + off, smem + buf * STAGE + (p >> 2) * IMG + (p & 3) * 8 * 128);
     };
@@ -275,8 +277,8 @@ __global__ __launch_bounds__(NT, 3) void attn_fwd_f32x6_d64_kernel(
     const float lt = xor32_sum(l);
     if (nsplit > 1) {  // unnormalised partial (O, m, l) of this key range: nos_attn_f32x6 merges them
       if (qrow < Sq) {
-        const long long row = ((long long)sp * B + b) * Sq + qrow;
-        float* op = part + row * ldh + hd * D;
+        const long long row = part_row(sp, B, b, Sq, qrow);
+        float* op = part_o(part, row, ldh, D, hd);
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -284,7 +286,7 @@ __global__ __launch_bounds__(NT, 3) void attn_fwd_f32x6_d64_kernel(
             *reinterpret_cast<float4*>(op + 32 * db + 8 * g + 4 * hh) =
                 float4{oacc[db][4 * g + 0], oacc[db][4 * g + 1], oacc[db][4 * g + 2], oacc[db][4 * g + 3]};
         if (hh == 0) {
-          float* ml = part + (long long)nsplit * B * Sq * ldh + (row * H + hd) * 2;
+          float* ml = part_ml(part, nsplit, B, Sq, H, ldh, row, hd);
           ml[0] = m;
           ml[1] = lt;
         }
@@ -365,7 +367,7 @@ __global__ __launch_bounds__(64 * H3_WAVES, H3_WG_PER_CU) void attn_fwd_f32h3_d6
     voff[db] = (4 * hh + tq) * 128 + (((4 * (db ^ vlb)) + 2 * g16 + (tp >> 1)) << 4) + 8 * (tp & 1);
 
   const int ntiles = (Skv + KVB - 1) / KVB;
-  const int skvp = ntiles * KVB;
+  const int skvp = nos::kvp::padded_keys(Skv);
   constexpr int PPW = 16 / H3_WAVES, HQBLK = 32 * H3_WAVES;
   int soff[PPW];  // staging: per-lane element offset of instruction i within a tile
 #pragma unroll
@@ -374,7 +376,7 @@ __global__ __launch_bounds__(64 * H3_WAVES, H3_WG_PER_CU) void attn_fwd_f32h3_d6
     const int plane = p >> 2;
     const int row = (p & 3) * 8 + (lane >> 3);
     const int lc = (lane & 7) ^ (plane < 2 ? kswz(row) : vswz(row));
-    soff[i] = (row * 4 + plane) * ldh + lc * 8;
+    soff[i] = (row * nos::kvp::H3 + plane) * ldh + lc * 8;
   }
 
   for (int w = chunk.first; w < chunk.end; w += chunk.step) {
@@ -427,20 +429,20 @@ __global__ __launch_bounds__(64 * H3_WAVES, H3_WG_PER_CU) void attn_fwd_f32h3_d6
         for (int p = 0; p < 2; ++p) asm volatile("" : "+v"(qf[ks][p]));
     }
 
-    const _Float16* pb = kvs + (long long)b * skvp * (4 * ldh) + hd * D;
+    const _Float16* pb = nos::kvp::batch_planes<nos::kvp::H3>(kvs, b, skvp, ldh) + hd * D;
     auto stage_piece = [&](int t, int buf, int i) {
       const int p = wid * PPW + i;
-      long long off = (long long)t * (KVB * 4) * ldh + soff[i];
+      long long off = (long long)t * (KVB * nos::kvp::H3) * ldh + soff[i];
       if ((t + 1) * KVB > Skv) {  // tail tile: rows past Skv re-read the last key
         const int over = t * KVB + (p & 3) * 8 + (lane >> 3) - (Skv - 1);
-        if (over > 0) off -= (long long)over * 4 * ldh;
+        if (over > 0) off -= (long long)over * nos::kvp::H3 * ldh;
       }
       glds16(pb + off, smem + buf * H3_STAGE + (p >> 2) * IMG + (p & 3) * 8 * 128);
     };
     // full tiles: uniform base + the per-lane byte offsets (2 * soff)
     auto stage_full = [&](int t, int buf, int i) {
       const int p = wid * PPW + i;
-      glds16_s(pb + (long long)t * (KVB * 4) * ldh, (unsigned)soff[i] * 2u,
+      glds16_s(pb + (long long)t * (KVB * nos::kvp::H3) * ldh, (unsigned)soff[i] * 2u,
                smem + buf * H3_STAGE + (p >> 2) * IMG + (p & 3) * 8 * 128);
     };
     // tile u into ring slot `slot` (full tiles from a uniform base)
@@ -556,8 +558,8 @@ __global__ __launch_bounds__(64 * H3_WAVES, H3_WG_PER_CU) void attn_fwd_f32h3_d6
     const float lt = xor32_sum(l);
     if (nsplit > 1) {  // unnormalised partial (O, m, l), O on the unit scale
       if (qrow < Sq) {
-        const long long row = ((long long)sp * B + b) * Sq + qrow;
-        float* op = part + row * ldh + hd * D;
+        const long long row = part_row(sp, B, b, Sq, qrow);
+        float* op = part_o(part, row, ldh, D, hd);
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -566,7 +568,7 @@ __global__ __launch_bounds__(64 * H3_WAVES, H3_WG_PER_CU) void attn_fwd_f32h3_d6
                 float4{oacc[db][4 * g + 0] * vinv, oacc[db][4 * g + 1] * vinv, oacc[db][4 * g + 2] * vinv,
                        oacc[db][4 * g + 3] * vinv};
         if (hh == 0) {
-          float* ml = part + (long long)nsplit * B * Sq * ldh + (row * H + hd) * 2;
+          float* ml = part_ml(part, nsplit, B, Sq, H, ldh, row, hd);
           ml[0] = m;
           ml[1] = lt;
         }
@@ -627,92 +629,15 @@ __global__ __launch_bounds__(256) void split_kv_kernel(const float* __restrict__
 #pragma unroll
     for (int j = 0; j < 8; ++j) p[0][j] = p[1][j] = p[2][j] = (__bf16)0.f;
   }
-  unsigned short* dst = kvs + ((long long)tok * 6 + 3 * is_v) * (H * D) + ch * 8;
+  unsigned short* dst = kvs + ((long long)tok * nos::kvp::X6 + nos::kvp::X6 / 2 * is_v) * (H * D) + ch * 8;
 #pragma unroll
   for (int j = 0; j < 3; ++j) *reinterpret_cast<bf16x8_t*>(dst + j * H * D) = p[j];
 }
 
-int launch(const float* q, const unsigned short* kvs, float* o, int B, int H, int Sq, int Skv, int ld_in,
-           long long bs_in, int ld_out, long long bs_out, float c, int nqb, int nsplit, float* part,
-           hipStream_t stream) {
-  const long long nwg = (long long)B * H * nqb * nsplit;
-  const int grid = nos_grid_for((const void*)attn_fwd_f32x6_d64_kernel<true>, NT, LDS_BYTES, nwg);
-  if (grid < nwg)
-    hipLaunchKernelGGL((attn_fwd_f32x6_d64_kernel<true>), dim3((unsigned)grid), dim3(NT), LDS_BYTES, stream,
-                       q, kvs, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c, nqb, nsplit, part);
-  else
-    hipLaunchKernelGGL((attn_fwd_f32x6_d64_kernel<false>), dim3((unsigned)nwg), dim3(NT), LDS_BYTES, stream,
-                       q, kvs, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c, nqb, nsplit, part);
-  return (int)hipGetLastError();
-}
-
 int g_kvsplit = 0;  // 0 = auto (nos_attn_f32x6_set_kvsplit)
-constexpr int MAX_SPLIT = 4;
-constexpr int WG_PER_CU = 3;  // the kernel's launch bound
-
-// Key splits: when one split per q-block leaves resident-workgroup slots of
-// the (budgeted) CUs empty -- one YOLOS image is 162 q-blocks for 768 slots --
-// split the keys so the grid fills them, at most MAX_SPLIT ways and never so
-// finely that a split has no tile.
-int pick_split(long long nwg1, int ntiles, int wg_per_cu = WG_PER_CU) {
-  int n = g_kvsplit;
-  if (n == 0) {
-    const long long slots = (long long)wg_per_cu * nos_effective_cus();
-    n = nwg1 >= slots ? 1 : (int)(slots / nwg1);
-  }
-  n = n < 1 ? 1 : (n > MAX_SPLIT ? MAX_SPLIT : n);
-  while (n > 1 && (long long)(n - 1) * ((ntiles + n - 1) / n) >= ntiles) --n;  // the last split non-empty
-  return n;
-}
-
-// KV-split merge: per (batch, row, head) and 4 dims, O = sum_i O_i 2^(m_i - M) /
-// sum_i l_i 2^(m_i - M), M = max_i m_i (m in log2 units, O_i unnormalised)
-__global__ __launch_bounds__(256) void merge_splits_kernel(const float* __restrict__ part, float* __restrict__ o,
-                                                           int B, int H, int Sq, int nsplit, int ld_out,
-                                                           long long bs_out, long long n4,
-                                                           _Float16* __restrict__ op = nullptr, long long opl = 0,
-                                                           float osc = 1.f) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  const int ldh = H * D;
-  const long long row = i / (ldh / 4);               // b * Sq + s
-  const int col = (int)(i - row * (ldh / 4)) * 4;    // hd * 64 + d
-  const int hd = col / D;
-  const long long per_split = (long long)B * Sq;
-  const float* ml = part + (long long)nsplit * per_split * ldh;
-  float mx = -INFINITY;
-  for (int sp = 0; sp < nsplit; ++sp) mx = fmaxf(mx, ml[((sp * per_split + row) * H + hd) * 2]);
-  float L = 0.f;
-  float4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int sp = 0; sp < nsplit; ++sp) {
-    const long long r = sp * per_split + row;
-    const float a = __builtin_amdgcn_exp2f(ml[(r * H + hd) * 2] - mx);
-    L = fmaf(ml[(r * H + hd) * 2 + 1], a, L);
-    const float4 v = *reinterpret_cast<const float4*>(part + r * ldh + col);
-    acc.x = fmaf(v.x, a, acc.x);
-    acc.y = fmaf(v.y, a, acc.y);
-    acc.z = fmaf(v.z, a, acc.z);
-    acc.w = fmaf(v.w, a, acc.w);
-  }
-  const float inv = 1.f / L;
-  const long long b = row / Sq, s = row - b * Sq;
-  const float4 y = float4{acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv};
-  if (op != nullptr) {
-    f16x2_t h01, l01, h23, l23;
-    nos::split2h(f32x2_t{y.x * osc, y.y * osc}, h01, l01);
-    nos::split2h(f32x2_t{y.z * osc, y.w * osc}, h23, l23);
-    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
-    *reinterpret_cast<f16x4_t*>(op + b * bs_out + s * ld_out + col) = f16x4_t{h01.x, h01.y, h23.x, h23.y};
-    *reinterpret_cast<f16x4_t*>(op + opl + b * bs_out + s * ld_out + col) = f16x4_t{l01.x, l01.y, l23.x, l23.y};
-    return;
-  }
-  *reinterpret_cast<float4*>(o + b * bs_out + s * ld_out + col) = y;
-}
 
 }  // namespace
 
-
-// Workspace bytes of nos_attn_fwd_f32x6_d64 (the split K/V planes).
 NOS_API int nos_attn_f32x6_set_kvsplit(int n) {
   if (n < 0 || n > MAX_SPLIT) return (int)hipErrorInvalidValue;
   g_kvsplit = n;
@@ -722,16 +647,14 @@ NOS_API int nos_attn_f32x6_set_kvsplit(int n) {
 // Workspace bytes of nos_attn_fwd_f32x6_d64: the split K/V planes, then room
 // for MAX_SPLIT partial (O, m, l) per query row and head.
 NOS_API long long nos_attn_f32x6_workspace(int B, int H, int Sq, int Skv) {
-  const long long skvp = (Skv + KVB - 1) / KVB * KVB;
-  const long long planes = ((long long)B * skvp * 6 * H * D * 2 + 15) / 16 * 16;
-  return planes + (long long)MAX_SPLIT * B * Sq * H * (D + 2) * 4;
+  return nos::kvp::planes_bytes(B, H, Skv) + part_bytes(B, H, Sq, D);
 }
 
 // The exact-fp32 kernel's contract (attention_f32.hip: nos_attn_fwd_f32_d64)
 // plus a workspace of nos_attn_f32x6_workspace() bytes (16-byte aligned).
 namespace {
 
-// shared argument checks of the two entries; 0 = ok
+// shared argument checks of the entries; 0 = ok
 int check_args(const void* q, const void* o, const void* ws, long long ws_bytes, int B, int H, int Sq, int Skv,
                int ld_in, long long bs_in, int ld_out, long long bs_out) {
   if (B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0) return (int)hipErrorInvalidValue;
@@ -739,30 +662,30 @@ int check_args(const void* q, const void* o, const void* ws, long long ws_bytes,
     return (int)hipErrorInvalidValue;
   if (((uintptr_t)q | (uintptr_t)o | (uintptr_t)ws) & 15) return (int)hipErrorInvalidValue;
   if (ws == nullptr || ws_bytes < nos_attn_f32x6_workspace(B, H, Sq, Skv)) return (int)hipErrorInvalidValue;
-  const long long skvp = (Skv + KVB - 1) / KVB * KVB;
+  const long long skvp = nos::kvp::padded_keys(Skv);
   if ((long long)B * H * ((Sq + QBLK - 1) / QBLK) > (1LL << 28) || (long long)B * skvp * 2 * H * 8 > INT_MAX ||
-      skvp * 6 * H * D > INT_MAX)
+      skvp * nos::kvp::X6 * H * D > INT_MAX)
     return (int)hipErrorInvalidValue;
   return 0;
+}
+
+// the key-split partials follow the planes
+float* partials(void* ws, int B, int H, int Skv) {
+  return reinterpret_cast<float*>(static_cast<unsigned char*>(ws) + nos::kvp::planes_bytes(B, H, Skv));
 }
 
 // the attention proper, from the six planes at the start of ws
 int run_from_planes(const float* q, float* o, int B, int H, int Sq, int Skv, int ld_in, long long bs_in, int ld_out,
                     long long bs_out, float scale, void* ws, hipStream_t stream) {
-  const float c = scale * 1.4426950408889634f;
   const int nqb = (Sq + QBLK - 1) / QBLK;
   const long long nwg = (long long)B * H * nqb;
-  const int skvp = (Skv + KVB - 1) / KVB * KVB;
-  const int nsplit = pick_split(nwg, skvp / KVB);
-  auto* kvs = static_cast<unsigned short*>(ws);
-  float* part = reinterpret_cast<float*>(static_cast<unsigned char*>(ws) +
-                                         ((long long)B * skvp * 6 * H * D * 2 + 15) / 16 * 16);
-  const int rc = launch(q, kvs, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c, nqb, nsplit, part, stream);
+  const int nsplit = pick_split(g_kvsplit, nwg, nos::kvp::padded_keys(Skv) / KVB, 3);  // the kernel's launch bound
+  float* part = partials(ws, B, H, Skv);
+  const int rc = nos::launch_items(attn_fwd_f32x6_d64_kernel<true>, attn_fwd_f32x6_d64_kernel<false>, NT, LDS_BYTES,
+                                   nwg * nsplit, stream, q, static_cast<const unsigned short*>(ws), o, B, H, Sq, Skv,
+                                   ld_in, bs_in, ld_out, bs_out, scale * nos::LOG2E, nqb, nsplit, part);
   if (rc != 0 || nsplit == 1) return rc;
-  const long long n4 = (long long)B * Sq * H * (D / 4);
-  hipLaunchKernelGGL(merge_splits_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, part, o, B, H, Sq,
-                     nsplit, ld_out, bs_out, n4);
-  return (int)hipGetLastError();
+  return run_merge<D, false, false>(part, o, B, H, D, Sq, nsplit, ld_out, bs_out, stream);
 }
 
 }  // namespace
@@ -772,7 +695,7 @@ NOS_API int nos_attn_fwd_f32x6_d64(const float* q, const float* k, const float* 
                                    void* ws, long long ws_bytes, hipStream_t stream) {
   if (int rc = check_args(q, o, ws, ws_bytes, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out)) return rc;
   if (((uintptr_t)k | (uintptr_t)v) & 15) return (int)hipErrorInvalidValue;
-  const int skvp = (Skv + KVB - 1) / KVB * KVB;
+  const int skvp = nos::kvp::padded_keys(Skv);
   const long long n8 = (long long)B * skvp * 2 * H * 8;
   hipLaunchKernelGGL(split_kv_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, k, v,
                      static_cast<unsigned short*>(ws), Skv, skvp, H, ld_in, bs_in, (int)n8);
@@ -789,26 +712,6 @@ NOS_API int nos_attn_fwd_f32x6_presplit_d64(const float* q, float* o, int B, int
   if (int rc = check_args(q, o, ws, ws_bytes, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out)) return rc;
   return run_from_planes(q, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, scale, ws, stream);
 }
-
-namespace {
-
-int launch_h3(const float* q, const _Float16* kvs, float* o, int B, int H, int Sq, int Skv, int ld_in,
-              long long bs_in, int ld_out, long long bs_out, float c, const float* kvsc, int nqb, int nsplit,
-              float* part, _Float16* op, long long opl, float osc, hipStream_t stream) {
-  const long long nwg = (long long)B * H * nqb * nsplit;
-  const int grid = nos_grid_for((const void*)attn_fwd_f32h3_d64_kernel<true>, 64 * H3_WAVES, H3_LDS_BYTES, nwg);
-  if (grid < nwg)
-    hipLaunchKernelGGL((attn_fwd_f32h3_d64_kernel<true>), dim3((unsigned)grid), dim3(64 * H3_WAVES), H3_LDS_BYTES,
-                       stream, q,
-                       kvs, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c, kvsc, nqb, nsplit, part, op, opl, osc);
-  else
-    hipLaunchKernelGGL((attn_fwd_f32h3_d64_kernel<false>), dim3((unsigned)nwg), dim3(64 * H3_WAVES), H3_LDS_BYTES,
-                       stream, q,
-                       kvs, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c, kvsc, nqb, nsplit, part, op, opl, osc);
-  return (int)hipGetLastError();
-}
-
-}  // namespace
 
 // fp16x3 attention from the four fp16 planes per token that the QKV
 // projection's epilogue wrote at the start of ws (nos_gemm_ln_f32x6_qkv_h3)
@@ -828,19 +731,15 @@ NOS_API int nos_attn_fwd_f32h3_presplit_d64(const float* q, float* o, int B, int
   auto* op = static_cast<_Float16*>(oplanes);
   if (op != nullptr && ((((uintptr_t)op) & 7) || opl < (long long)B * bs_out || !(osc > 0.f)))
     return (int)hipErrorInvalidValue;
-  const float c = scale * 1.4426950408889634f;
   const int nqb = (Sq + 32 * H3_WAVES - 1) / (32 * H3_WAVES);
   const long long nwg = (long long)B * H * nqb;
-  const int skvp = (Skv + KVB - 1) / KVB * KVB;
-  const int nsplit = pick_split(nwg, skvp / KVB, H3_WG_PER_CU);
-  auto* kvs = static_cast<const _Float16*>(ws);
-  float* part = reinterpret_cast<float*>(static_cast<unsigned char*>(ws) +
-                                         ((long long)B * skvp * 6 * H * D * 2 + 15) / 16 * 16);
-  const int rc = launch_h3(q, kvs, o, B, H, Sq, Skv, ld_in, bs_in, ld_out, bs_out, c, kvsc, nqb, nsplit, part, op, opl,
-                           osc, stream);
+  const int nsplit = pick_split(g_kvsplit, nwg, nos::kvp::padded_keys(Skv) / KVB, H3_WG_PER_CU);
+  float* part = partials(ws, B, H, Skv);
+  const int rc = nos::launch_items(attn_fwd_f32h3_d64_kernel<true>, attn_fwd_f32h3_d64_kernel<false>, 64 * H3_WAVES,
+                                   H3_LDS_BYTES, nwg * nsplit, stream, q, static_cast<const _Float16*>(ws), o, B, H,
+                                   Sq, Skv, ld_in, bs_in, ld_out, bs_out, scale * nos::LOG2E, kvsc, nqb, nsplit, part,
+                                   op, opl, osc);
   if (rc != 0 || nsplit == 1) return rc;
-  const long long n4 = (long long)B * Sq * H * (D / 4);
-  hipLaunchKernelGGL(merge_splits_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, part, o, B, H, Sq,
-                     nsplit, ld_out, bs_out, n4, op, opl, osc);
-  return (int)hipGetLastError();
+  if (op == nullptr) return run_merge<D, false, false>(part, o, B, H, D, Sq, nsplit, ld_out, bs_out, stream);
+  return run_merge<D, true, false>(part, o, B, H, D, Sq, nsplit, ld_out, bs_out, stream, nullptr, op, opl, osc);
 }

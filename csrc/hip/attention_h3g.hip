@@ -29,7 +29,7 @@
 //     causal tiles past a workgroup's last query are never loaded, the
 //     diagonal tiles masked per lane, heavy (late) query blocks first;
 //     grouped-query heads read their K / V head's planes (h * Hkv / H);
-//     key splits (merged by merge_kernel) when the grid leaves CU slots idle;
+//     key splits (attn_split.h) when the grid leaves CU slots idle;
 //     slice-sized persistent grids under a CU budget (nos::xcd_chunk).
 //
 // nos_attn_h3g_lse also stores every query row's log-sum-exp (natural log of
@@ -40,6 +40,7 @@
 #include <math.h>
 
 #include "attn_kv_planes.h"
+#include "attn_split.h"
 #include "common.h"
 #include "lds_pipe.h"
 #include "split_f16.h"
@@ -48,7 +49,6 @@ namespace {
 
 constexpr int IMG = KVB * 64 * 2;       // one 64-dim fp16 piece image: 32 rows x 128 B = 4 KiB
 constexpr float RESCALE_THR = 8.f;      // log2 units
-constexpr int MAX_SPLIT = 4;
 constexpr int HW = 8;                   // waves per workgroup
 constexpr int QB = 32 * HW;             // query rows per workgroup
 
@@ -306,8 +306,8 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
     const int ldh = H * D;
     if (nsplit > 1) {  // unnormalised partial (O on the unit scale, m, l) of this key range
       if (qrow < Sq) {
-        const long long row = ((long long)sp * B + b) * Sq + qrow;
-        float* op = part + row * ldh + h * D;
+        const long long row = part_row(sp, B, b, Sq, qrow);
+        float* op = part_o(part, row, ldh, D, h);
 #pragma unroll
         for (int db = 0; db < 2 * NH; ++db)
 #pragma unroll
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
                 float4{oacc[db][4 * g + 0] * vinv, oacc[db][4 * g + 1] * vinv, oacc[db][4 * g + 2] * vinv,
                        oacc[db][4 * g + 3] * vinv};
         if (hh == 0) {
-          float* ml = part + (long long)nsplit * B * Sq * ldh + (row * H + h) * 2;
+          float* ml = part_ml(part, nsplit, B, Sq, H, ldh, row, h);
           ml[0] = t0 < t1 ? m : -1e30f;
           ml[1] = lt;
         }
@@ -342,38 +342,6 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
   }  // items
 }
 
-// key-split merge: O = sum_i O_i 2^(m_i - M) / sum_i l_i 2^(m_i - M)
-__global__ __launch_bounds__(256) void merge_kernel(const float* __restrict__ part, float* __restrict__ o, int B,
-                                                    int H, int D, int Sq, int nsplit, int ldo, long long bso,
-                                                    long long n4, float* __restrict__ lse) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  const int ldh = H * D;
-  const long long row = i / (ldh / 4);
-  const int col = (int)(i - row * (ldh / 4)) * 4;
-  const int h = col / D;
-  const long long per_split = (long long)B * Sq;
-  const float* ml = part + (long long)nsplit * per_split * ldh;
-  float mx = -INFINITY;
-  for (int sp = 0; sp < nsplit; ++sp) mx = fmaxf(mx, ml[((sp * per_split + row) * H + h) * 2]);
-  float L = 0.f;
-  float4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int sp = 0; sp < nsplit; ++sp) {
-    const long long r = sp * per_split + row;
-    const float a = __builtin_amdgcn_exp2f(ml[(r * H + h) * 2] - mx);
-    L = fmaf(ml[(r * H + h) * 2 + 1], a, L);
-    const float4 v = *reinterpret_cast<const float4*>(part + r * ldh + col);
-    acc.x = fmaf(v.x, a, acc.x);
-    acc.y = fmaf(v.y, a, acc.y);
-    acc.z = fmaf(v.z, a, acc.z);
-    acc.w = fmaf(v.w, a, acc.w);
-  }
-  const float inv = 1.f / L;
-  const long long b = row / Sq, s = row - b * Sq;
-  *reinterpret_cast<float4*>(o + b * bso + s * ldo + col) = float4{acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv};
-  if (lse != nullptr && col == h * D) lse[(b * H + h) * Sq + s] = fmaf(mx, 0.6931471805599453f, __builtin_amdgcn_logf(L) * 0.6931471805599453f);
-}
-
 struct Layout {
   long long planes, absmax, scales, part, total;
   int nchunk, skvp;
@@ -388,38 +356,11 @@ Layout layout(int B, int H, int Hkv, int Sq, int Skv, int D) {
   L.absmax = al((long long)B * Hkv * L.skvp * 4 * D * 2);
   L.scales = L.absmax + al((long long)B * Hkv * L.nchunk * 2 * 4);
   L.part = L.scales + al((long long)B * Hkv * 2 * 4);
-  L.total = L.part + (long long)MAX_SPLIT * B * Sq * H * (D + 2) * 4;
+  L.total = L.part + part_bytes(B, H, Sq, D);
   return L;
 }
 
 int g_kvsplit = 0;  // 0: auto
-
-int pick_split(long long nwg1, int ntiles, int wg_per_cu) {
-  int n = g_kvsplit;
-  if (n == 0) {
-    const long long slots = (long long)wg_per_cu * nos_effective_cus();
-    n = nwg1 >= slots ? 1 : (int)(slots / nwg1);
-  }
-  n = n < 1 ? 1 : (n > MAX_SPLIT ? MAX_SPLIT : n);
-  while (n > 1 && (long long)(n - 1) * ((ntiles + n - 1) / n) >= ntiles) --n;
-  return n;
-}
-
-template <int D, bool CAUSAL, bool ROPE>
-int launch(const float* q, int ldq, long long bsq, const _Float16* kvs, const float* kvsc, float* o, int ldo,
-           long long bso, int B, int H, int Hkv, int Sq, int Skv, float c, int nqb, int nsplit, float* part,
-           const float* rc, const float* rs, float* lse, hipStream_t stream) {
-  constexpr int lds = 2 * 4 * (D / 64) * IMG;
-  const long long nwg = (long long)B * H * nqb * nsplit;
-  const int grid = nos_grid_for((const void*)attn_h3g_kernel<D, CAUSAL, ROPE, true>, 64 * HW, lds, nwg);
-  if (grid < nwg)
-    hipLaunchKernelGGL((attn_h3g_kernel<D, CAUSAL, ROPE, true>), dim3((unsigned)grid), dim3(64 * HW), lds, stream, q,
-                       ldq, bsq, kvs, kvsc, o, ldo, bso, B, H, Hkv, Sq, Skv, c, nqb, nsplit, part, rc, rs, lse);
-  else
-    hipLaunchKernelGGL((attn_h3g_kernel<D, CAUSAL, ROPE, false>), dim3((unsigned)nwg), dim3(64 * HW), lds, stream,
-                       q, ldq, bsq, kvs, kvsc, o, ldo, bso, B, H, Hkv, Sq, Skv, c, nqb, nsplit, part, rc, rs, lse);
-  return (int)hipGetLastError();
-}
 
 }  // namespace
 
@@ -469,15 +410,16 @@ int attn_h3g_run(const float* q, int ldq, long long bsq, const float* k, int ldk
   hipLaunchKernelGGL(split_kv_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, k, v, kvsc, kvs, Skv,
                      L.skvp, Hkv, D, ldk, bsk, ldv, bsv, rope_cos, rope_sin, n8);
   if (int rc = (int)hipGetLastError()) return rc;
-  const float c = scale * 1.4426950408889634f;
+  const float c = scale * nos::LOG2E;
   const int nqb = (Sq + QB - 1) / QB;
   const long long nwg1 = (long long)B * H * nqb;
-  const int nsplit = pick_split(nwg1, L.skvp / KVB, D == 64 ? 2 : 1);
+  const int nsplit = pick_split(g_kvsplit, nwg1, L.skvp / KVB, D == 64 ? 2 : 1);
   int rc;
   const bool rope = rope_cos != nullptr;
-#define NOS_H3G(d, cz, rp)                                                                                          \
-  rc = launch<d, cz, rp>(q, ldq, bsq, kvs, kvsc, o, ldo, bso, B, H, Hkv, Sq, Skv, c, nqb, nsplit, part, rope_cos, \
-                         rope_sin, lse, stream)
+#define NOS_H3G(d, cz, rp)                                                                                         \
+  rc = nos::launch_items(attn_h3g_kernel<d, cz, rp, true>, attn_h3g_kernel<d, cz, rp, false>, 64 * HW,             \
+                         2 * 4 * (d / 64) * IMG, nwg1 * nsplit, stream, q, ldq, bsq, kvs, kvsc, o, ldo, bso, B, H, \
+                         Hkv, Sq, Skv, c, nqb, nsplit, part, rope_cos, rope_sin, lse)
   if (D == 64) {
     if (causal) {
       if (rope) NOS_H3G(64, true, true); else NOS_H3G(64, true, false);
@@ -493,10 +435,8 @@ int attn_h3g_run(const float* q, int ldq, long long bsq, const float* k, int ldk
   }
 #undef NOS_H3G
   if (rc != 0 || nsplit == 1) return rc;
-  const long long n4 = (long long)B * Sq * H * (D / 4);
-  hipLaunchKernelGGL(merge_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, part, o, B, H, D, Sq,
-                     nsplit, ldo, bso, n4, lse);
-  return (int)hipGetLastError();
+  if (lse != nullptr) return run_merge<0, false, true>(part, o, B, H, D, Sq, nsplit, ldo, bso, stream, lse);
+  return run_merge<0, false, false>(part, o, B, H, D, Sq, nsplit, ldo, bso, stream);
 }
 }  // namespace
 

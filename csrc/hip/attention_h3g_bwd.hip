@@ -756,7 +756,7 @@ NOS_API int nos_attn_h3g_bwd(const float* q, int ldq, long long bsq, const float
   auto* grp = reinterpret_cast<float*>(base + L.grp);
   auto* part = reinterpret_cast<float*>(base + L.part);
   const int nbk = B * Hkv, nbq = B * H, g = H / Hkv;
-  const float c = scale * 1.4426950408889634f;
+  const float c = scale * nos::LOG2E;
   auto blocks = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
 
   // K / V as the forward sees them; Q / dO maxima through the same kernel (H heads of Sq rows)

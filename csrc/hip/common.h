@@ -74,6 +74,9 @@ __device__ __forceinline__ XcdChunk xcd_chunk(int block, int grid, int n) {
   return XcdChunk{lo + j, lo + cnt, wgs_x > 0 ? wgs_x : 1};
 }
 
+// log2 e: a softmax scale times this turns scores into exp2 units
+constexpr float LOG2E = 1.4426950408889634f;
+
 }  // namespace nos
 
 // Grid cap for CU-slice tenants (runtime.hip): with a CU budget set
@@ -87,6 +90,24 @@ int nos_grid_for(const void* kernel, int block_threads, size_t lds_bytes, long l
 // CUs the tile/variant cost models plan for: the CU budget when one is set
 // (a CU-mask slice), else the current device's CU count.
 int nos_effective_cus();
+
+namespace nos {
+
+// The launch pair of the item-loop kernels: `persistent` (walks nos::xcd_chunk)
+// on the capped grid when a CU budget caps it below `items`, else `plain`
+// (always, for a kernel without a persistent form: persistent == nullptr).
+template <class... P, class... A>
+int launch_items(void (*persistent)(P...), void (*plain)(P...), int threads, size_t lds, long long items,
+                 hipStream_t st, A... args) {
+  const long long grid = persistent ? nos_grid_for((const void*)persistent, threads, lds, items) : items;
+  if (grid < items)
+    hipLaunchKernelGGL(persistent, dim3((unsigned)grid), dim3(threads), lds, st, args...);
+  else
+    hipLaunchKernelGGL(plain, dim3((unsigned)items), dim3(threads), lds, st, args...);
+  return (int)hipGetLastError();
+}
+
+}  // namespace nos
 
 #define HIP_CHECK_RET(expr)                       \
   do {                                            \

@@ -214,14 +214,8 @@ int launch_t(const float* A, int lda, const float* W, int ldw, const float* bias
   const long long ntiles = (long long)tiles_m * tiles_n;
   if (ntiles > (1LL << 30)) return (int)hipErrorInvalidValue;
   const size_t lds = 2 * (size_t)(BM + BN) * ROWB + 2 * BM * sizeof(float);
-  const int grid = nos_grid_for((const void*)gemm_f32_kernel<LN, BM, BN, true>, NT, lds, ntiles);
-  if (grid < ntiles)
-    hipLaunchKernelGGL((gemm_f32_kernel<LN, BM, BN, true>), dim3((unsigned)grid), dim3(NT), lds, st, A, lda, W, ldw,
-                       bias, c1, c2, R, ldr, C, ldc, M, N, K, epi, eps, tiles_m, tiles_n);
-  else
-    hipLaunchKernelGGL((gemm_f32_kernel<LN, BM, BN, false>), dim3((unsigned)ntiles), dim3(NT), lds, st, A, lda, W,
-                       ldw, bias, c1, c2, R, ldr, C, ldc, M, N, K, epi, eps, tiles_m, tiles_n);
-  return (int)hipGetLastError();
+  return nos::launch_items(gemm_f32_kernel<LN, BM, BN, true>, gemm_f32_kernel<LN, BM, BN, false>, NT, lds, ntiles, st,
+                           A, lda, W, ldw, bias, c1, c2, R, ldr, C, ldc, M, N, K, epi, eps, tiles_m, tiles_n);
 }
 
 // Tile policy (nos_gemm_f32_set_policy):

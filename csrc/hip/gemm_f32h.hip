@@ -25,6 +25,7 @@
 
 #include <type_traits>
 
+#include "attn_d64_planes.h"
 #include "common.h"
 #include "epilogue.h"
 #include "lds_pipe.h"
@@ -57,14 +58,7 @@ constexpr int BK = 32;  // K depth of an LDS stage (two 16-deep MFMA steps); K %
 // 16-byte slots
 __device__ __forceinline__ int swz(int row) { return (row >> 2) & 3; }
 
-// the K / V columns (>= qcols) of a fused QKV projection as the h3
-// attention's planes kvs[b][s][K hi, K lo, V hi, V lo][hd], each head on
-// kvsc[0 / 1][head]; rows per batch S, padded to skvp
-struct KvOut {
-  unsigned short* kvs = nullptr;
-  const float* kvsc = nullptr;
-  int qcols = 0, hd = 0, S = 0, skvp = 0;
-};
+using nos::kvp::KvOut;  // the K / V columns of a fused QKV projection as the h3 attention's planes
 
 // the output as the NEXT h3 GEMM's A planes ([2][M][ldp], plane stride
 // pplane) on the static scale sc (the host's bound of this output: fc1's
@@ -495,9 +489,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_h3_kernel(
           ld = po.ldp;
         } else {
           t = (n0 - kv.qcols) >= kv.hd;
-          hi = kv.kvs + ((long long)m0 * 4 + 2 * t) * kv.hd + (n0 - kv.qcols - t * kv.hd);
+          hi = kv.kvs + ((long long)m0 * nos::kvp::H3 + nos::kvp::H3 / 2 * t) * kv.hd + (n0 - kv.qcols - t * kv.hd);
           lo_off = kv.hd;
-          ld = 4 * kv.hd;
+          ld = nos::kvp::H3 * kv.hd;
         }
         // wide: the tile's two planes in LDS (the ring is free: every wave passed the
         // K loop's last barrier), 16-byte chunks XOR-swizzled by row, then each
@@ -623,7 +617,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_h3_kernel(
               const float x = v * kv.kvsc[t * (kv.hd >> 6) + (col >> 6)];
               const _Float16 h0 = (_Float16)x;
               const _Float16 h1 = (_Float16)(x - (float)h0);
-              unsigned short* dst = kv.kvs + (row * 4 + 2 * t) * kv.hd + col;
+              unsigned short* dst = kv.kvs + (row * nos::kvp::H3 + nos::kvp::H3 / 2 * t) * kv.hd + col;
               dst[0] = __builtin_bit_cast(unsigned short, h0);
               dst[kv.hd] = __builtin_bit_cast(unsigned short, h1);
             } else if (po.p != nullptr) {
@@ -691,21 +685,15 @@ int launch_t(const H3Call& c, hipStream_t st) {
   const size_t lds = RS * (size_t)(2 * BM * BK * 2 + 2 * BN * BK * 2);
   constexpr int NT = 64 * WGM * WGN;
   const int epi = !BATCHED && wide_planes_ok(c.kv, c.po) ? c.epi | EPI_WIDE : c.epi;
-  auto launch = [&](auto* kernel, long long grid) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(NT), lds, st, c.a, c.lda, c.aplane, c.rinv, c.rconst, c.w,
-                       c.ldw, c.wplane, c.csc, c.bias, c.R, c.ldr, c.C, c.ldc, c.M, c.N, c.K, epi, tiles_m, tiles_n,
-                       c.kv, c.po, c.bt, c.ln);
-    return (int)hipGetLastError();
-  };
+  auto* plain = gemm_h3_kernel<BM, BN, WGM, WGN, false, RS, MODE, BATCHED>;
   // batched GEMMs always launch one workgroup per tile: their persistent
   // form (a CU slice's capped grid) needs 21 more VGPRs than 256 and spilled
   // to scratch; the CU mask bounds where the tiles run either way
-  if constexpr (!BATCHED) {
-    auto* persistent = gemm_h3_kernel<BM, BN, WGM, WGN, true, RS, MODE, BATCHED>;
-    const int grid = nos_grid_for((const void*)persistent, NT, lds, ntiles);
-    if (grid < ntiles) return launch(persistent, grid);
-  }
-  return launch(gemm_h3_kernel<BM, BN, WGM, WGN, false, RS, MODE, BATCHED>, ntiles);
+  decltype(plain) persistent = nullptr;
+  if constexpr (!BATCHED) persistent = gemm_h3_kernel<BM, BN, WGM, WGN, true, RS, MODE, BATCHED>;
+  return nos::launch_items(persistent, plain, NT, lds, ntiles, st, c.a, c.lda, c.aplane, c.rinv, c.rconst, c.w, c.ldw,
+                           c.wplane, c.csc, c.bias, c.R, c.ldr, c.C, c.ldc, c.M, c.N, c.K, epi, tiles_m, tiles_n, c.kv,
+                           c.po, c.bt, c.ln);
 }
 
 // plain fp32-C GEMMs (no KV / plane output, N % 4 == 0, aligned C / R) through
@@ -1071,7 +1059,8 @@ bool fill_outputs(H3Call& c, void* kvs, int S, int skvp, const float* kvsc, void
                   float psc) {
   const int M = c.M, N = c.N;
   if (kvs != nullptr) {
-    if (!kvsc || N % 3 || (N / 3) % 64 || S <= 0 || M % S || skvp < S || (((uintptr_t)kvs) & 15) || P) return false;
+    if (!kvsc || N % 3 || (N / 3) % 64 || !nos::kvp::skvp_ok(S, skvp) || M % S || (((uintptr_t)kvs) & 15) || P)
+      return false;
     c.kv.kvs = static_cast<unsigned short*>(kvs);
     c.kv.kvsc = kvsc;
     c.kv.hd = N / 3;

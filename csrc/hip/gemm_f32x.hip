@@ -22,6 +22,7 @@
 //    of a 16-deep step are exactly one bf16x8 operand) and issues six
 //    v_mfma_f32_32x32x16_bf16 per 32x32 block and step;
 //  * epilogue and LayerNorm statistics as in gemm_f32.hip.
+#include "attn_d64_planes.h"
 #include "common.h"
 #include "epilogue.h"
 #include "lds_pipe.h"
@@ -51,11 +52,7 @@ using nos::wait_stages;
 // With kvsc (the fp16x3 attention, attention_f32x.hip): four fp16 planes per
 // token instead (K hi, K lo, V hi, V lo: kvs[b][s][plane][hd], split_f16.h),
 // each head's K / V on the power-of-two scale kvsc[0 / 1][head].
-struct KvOut {
-  unsigned short* kvs = nullptr;
-  int qcols = 0, hd = 0, S = 0, skvp = 0;
-  const float* kvsc = nullptr;
-};
+using nos::kvp::KvOut;
 
 __device__ __forceinline__ unsigned short bf16_bits(float x) {
   return __builtin_bit_cast(unsigned short, (__bf16)x);
@@ -373,12 +370,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN > 4 ? 1 : 2) void gemm_f3
               const float x = v * kv.kvsc[t * (kv.hd >> 6) + (col >> 6)];
               const _Float16 h0 = (_Float16)x;
               const _Float16 h1 = (_Float16)(x - (float)h0);
-              unsigned short* dst = kv.kvs + (row * 4 + 2 * t) * kv.hd + col;
+              unsigned short* dst = kv.kvs + (row * nos::kvp::H3 + nos::kvp::H3 / 2 * t) * kv.hd + col;
               dst[0] = __builtin_bit_cast(unsigned short, h0);
               dst[kv.hd] = __builtin_bit_cast(unsigned short, h1);
               continue;
             }
-            unsigned short* dst = kv.kvs + (row * 6 + 3 * t) * kv.hd + col;
+            unsigned short* dst = kv.kvs + (row * nos::kvp::X6 + nos::kvp::X6 / 2 * t) * kv.hd + col;
             const __bf16 p0 = (__bf16)v;
             const float r1 = v - (float)p0;
             const __bf16 p1 = (__bf16)r1;
@@ -400,7 +397,17 @@ int g_pipe = 1;  // software-pipelined K loop on 2-deep rings (nos_gemm_f32x6_se
 template <bool LN, int BM, int BN, int RS, int BK, int WGM, int WGN, bool PIPE>
 int launch_p(const float* A, int lda, const unsigned short* Wp, int ldw, long long wplane, const float* bias,
              const float* c1, const float* c2, const float* R, int ldr, float* C, int ldc, int M, int N, int K,
-             int epi, float eps, hipStream_t st, KvOut kv);
+             int epi, float eps, hipStream_t st, KvOut kv) {
+  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+  const long long ntiles = (long long)tiles_m * tiles_n;
+  if (ntiles > (1LL << 30)) return (int)hipErrorInvalidValue;
+  const size_t ring = RS * (size_t)(BM * Lay<BK>::AROW + 3 * BN * Lay<BK>::WROW);
+  const size_t lds = ring > 2 * BM * sizeof(float) ? ring : 2 * BM * sizeof(float);
+  constexpr int NT = 64 * WGM * WGN;
+  return nos::launch_items(gemm_f32x6_kernel<LN, BM, BN, true, RS, BK, WGM, WGN, PIPE>,
+                           gemm_f32x6_kernel<LN, BM, BN, false, RS, BK, WGM, WGN, PIPE>, NT, lds, ntiles, st, A, lda, Wp,
+                           ldw, wplane, bias, c1, c2, R, ldr, C, ldc, M, N, K, epi, eps, tiles_m, tiles_n, kv);
+}
 
 template <bool LN, int BM, int BN, int RS, int BK, int WGM = 2, int WGN = 2>
 int launch_t(const float* A, int lda, const unsigned short* Wp, int ldw, long long wplane, const float* bias,
@@ -412,29 +419,6 @@ int launch_t(const float* A, int lda, const unsigned short* Wp, int ldw, long lo
   }
   return launch_p<LN, BM, BN, RS, BK, WGM, WGN, false>(A, lda, Wp, ldw, wplane, bias, c1, c2, R, ldr, C, ldc, M, N,
                                                        K, epi, eps, st, kv);
-}
-
-template <bool LN, int BM, int BN, int RS, int BK, int WGM, int WGN, bool PIPE>
-int launch_p(const float* A, int lda, const unsigned short* Wp, int ldw, long long wplane, const float* bias,
-             const float* c1, const float* c2, const float* R, int ldr, float* C, int ldc, int M, int N, int K,
-             int epi, float eps, hipStream_t st, KvOut kv) {
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const long long ntiles = (long long)tiles_m * tiles_n;
-  if (ntiles > (1LL << 30)) return (int)hipErrorInvalidValue;
-  const size_t ring = RS * (size_t)(BM * Lay<BK>::AROW + 3 * BN * Lay<BK>::WROW);
-  const size_t lds = ring > 2 * BM * sizeof(float) ? ring : 2 * BM * sizeof(float);
-  constexpr int NT = 64 * WGM * WGN;
-  const int grid =
-      nos_grid_for((const void*)gemm_f32x6_kernel<LN, BM, BN, true, RS, BK, WGM, WGN, PIPE>, NT, lds, ntiles);
-  if (grid < ntiles)
-    hipLaunchKernelGGL((gemm_f32x6_kernel<LN, BM, BN, true, RS, BK, WGM, WGN, PIPE>), dim3((unsigned)grid), dim3(NT),
-                       lds, st, A, lda, Wp, ldw, wplane, bias, c1, c2, R, ldr, C, ldc, M, N, K, epi, eps, tiles_m,
-                       tiles_n, kv);
-  else
-    hipLaunchKernelGGL((gemm_f32x6_kernel<LN, BM, BN, false, RS, BK, WGM, WGN, PIPE>), dim3((unsigned)ntiles),
-                       dim3(NT), lds, st, A, lda, Wp, ldw, wplane, bias, c1, c2, R, ldr, C, ldc, M, N, K, epi, eps,
-                       tiles_m, tiles_n, kv);
-  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -546,7 +530,7 @@ namespace {
 int qkv_planes(const float* A, int lda, const void* Wp, int ldw, long long wplane, const float* c1, const float* c2,
                float* C, int ldc, int M, int N, int K, int epi, float eps, void* kvs, int S, int skvp,
                const float* kvsc, hipStream_t stream) {
-  if (kvs == nullptr || N % 3 != 0 || S <= 0 || M % S != 0 || skvp < S || (((uintptr_t)kvs) & 15))
+  if (kvs == nullptr || N % 3 != 0 || !nos::kvp::skvp_ok(S, skvp) || M % S != 0 || (((uintptr_t)kvs) & 15))
     return (int)hipErrorInvalidValue;
   if (kvsc != nullptr && (N / 3) % 64 != 0) return (int)hipErrorInvalidValue;
   KvOut kv;

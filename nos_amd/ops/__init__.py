@@ -227,6 +227,15 @@ def _split_rows_h3(x2: torch.Tensor, ln: bool, eps: float = 0.0) -> tuple[torch.
     return planes, rinv
 
 
+def _h3_outputs(kv, planes_out, M: int, N: int) -> tuple:
+    """The trailing output arguments of the h3 GEMM entry points: ``kv`` =
+    (workspace, S, skvp, scales) for the K / V planes of a QKV projection,
+    ``planes_out`` = (planes [2, M, N], scale) for the next GEMM's A planes."""
+    kvs, S, skvp, kvsc = kv if kv is not None else (None, 0, 0, None)
+    pp, psc = planes_out if planes_out is not None else (None, 1.0)
+    return _ptr(kvs), S, skvp, _ptr(kvsc), _ptr(pp), N, M * N, float(psc)
+
+
 def _gemm_h3(ap, rinv, weight, bias, r2, o2, epi, kv=None, rconst: float = 0.0, planes_out=None) -> None:
     """One h3 GEMM on A planes ap [2, M, K] (row scales rinv, or rconst for
     every row) into o2 [M, N] -- or, with ``planes_out`` = (planes [2, M, N],
@@ -234,12 +243,10 @@ def _gemm_h3(ap, rinv, weight, bias, r2, o2, epi, kv=None, rconst: float = 0.0, 
     M, K = ap.shape[1], ap.shape[2]
     N = weight.shape[0]
     wp, csc = split_f32_weight_h3(weight)
-    kvs, S, skvp, kvsc = kv if kv is not None else (None, 0, 0, None)
-    pp, psc = planes_out if planes_out is not None else (None, 1.0)
     rc = _lib.lib().nos_gemm_f32h3(ap.data_ptr(), K, M * K, _ptr(rinv), float(rconst), wp.data_ptr(), K, N * K,
                                    csc.data_ptr(), _ptr(bias), _ptr(r2), r2.stride(0) if r2 is not None else 0,
-                                   _ptr(o2), o2.stride(0) if o2 is not None else N, M, N, K, epi, _ptr(kvs), S, skvp,
-                                   _ptr(kvsc), _ptr(pp), N, M * N, float(psc), _stream())
+                                   _ptr(o2), o2.stride(0) if o2 is not None else N, M, N, K, epi,
+                                   *_h3_outputs(kv, planes_out, M, N), _stream())
     _lib.check(rc, "nos_gemm_f32h3")
 
 
@@ -364,13 +371,11 @@ def _gemm_ln_h3(x2: torch.Tensor, pre, eps: float, wg: torch.Tensor, c2: torch.T
     if _LN_HANDOFF and _lna_ok(x2):
         st = pre if isinstance(pre, RowStats) else _row_stats(x2)
         wp, csc = split_f32_weight_h3(wg)
-        kvs, S, skvp, kvsc = kv if kv is not None else (None, 0, 0, None)
-        pp, psc = planes_out if planes_out is not None else (None, 1.0)
         eln = 14 - math.frexp(math.sqrt(K))[1]
         rc = _lib.lib().nos_gemm_f32h3_lna(x2.data_ptr(), x2.stride(0), st.stats.data_ptr(), st.stats.shape[1], st.pw,
                                            float(eps), eln, wp.data_ptr(), K, N * K, csc.data_ptr(), c2.data_ptr(),
                                            None, 0, _ptr(o2), o2.stride(0) if o2 is not None else N, M, N, K, epi,
-                                           _ptr(kvs), S, skvp, _ptr(kvsc), _ptr(pp), N, M * N, float(psc), _stream())
+                                           *_h3_outputs(kv, planes_out, M, N), _stream())
         _lib.check(rc, "nos_gemm_f32h3_lna")
         return
     ap, rinv = (pre.planes, pre.rinv) if isinstance(pre, H3Planes) else _split_rows_h3(x2, ln=True, eps=eps)
@@ -719,6 +724,14 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
     return out, sum_out
 
 
+def _kv_workspace(B: int, H: int, S: int, device) -> tuple[torch.Tensor, int]:
+    """The head-dim-64 x6 / h3 attention's workspace (K / V planes, then the
+    key-split partials) as a stream-ordered allocation (graph-capture safe),
+    and the planes' padded rows per batch (whole 32-key tiles)."""
+    nbytes = int(_lib.lib().nos_attn_f32x6_workspace(B, H, S, S))
+    return torch.empty(nbytes // 2, dtype=torch.int16, device=device), (S + 31) // 32 * 32
+
+
 def attention_qkv(qkv: torch.Tensor, num_heads: int, out: torch.Tensor | None = None,
                   scale: float | None = None) -> torch.Tensor:
     """Self-attention on a fused projection qkv [B, S, 3*H*64] -> [B, S, H*64]."""
@@ -745,10 +758,8 @@ def attention_qkv(qkv: torch.Tensor, num_heads: int, out: torch.Tensor | None = 
     args = (base, base + hd * es, base + 2 * hd * es, out.data_ptr(), B, num_heads, S, S, qkv.stride(1),
             qkv.stride(0), out.stride(1), out.stride(0), float(scale))
     if qkv.dtype == torch.float32 and _ATTN_F32_VARIANT[:2] in ("x6", "h3"):
-        # the split K/V planes: a stream-ordered allocation (graph-capture safe)
-        nbytes = int(L.nos_attn_f32x6_workspace(B, num_heads, S, S))
-        ws = torch.empty(nbytes // 2, dtype=torch.int16, device=qkv.device)
-        _lib.check(L.nos_attn_fwd_f32x6_d64(*args, ws.data_ptr(), nbytes, _stream()), "nos_attn_fwd_f32x6_d64")
+        ws, _ = _kv_workspace(B, num_heads, S, qkv.device)
+        _lib.check(L.nos_attn_fwd_f32x6_d64(*args, ws.data_ptr(), ws.numel() * 2, _stream()), "nos_attn_fwd_f32x6_d64")
         return out
     fn, name = ((L.nos_attn_fwd_f32_d64, "nos_attn_fwd_f32_d64") if qkv.dtype == torch.float32
                 else (L.nos_attn_fwd_d64, "nos_attn_fwd_d64"))
@@ -776,9 +787,7 @@ def linear_ln_qkv_x6(x: torch.Tensor, wg: torch.Tensor, c1: torch.Tensor, c2: to
     M = x2.shape[0]
     out = torch.empty((B, S, N), dtype=torch.float32, device=x.device)
     L = _lib.lib()
-    nbytes = int(L.nos_attn_f32x6_workspace(B, num_heads, S, S))
-    ws = torch.empty(nbytes // 2, dtype=torch.int16, device=x.device)
-    skvp = (S + 31) // 32 * 32
+    ws, skvp = _kv_workspace(B, num_heads, S, x.device)
     wp = split_f32_weight(wg)
     rc = L.nos_gemm_ln_f32x6_qkv(x2.data_ptr(), x2.stride(0), wp.data_ptr(), wp.stride(1), wp.stride(0),
                                  c1.data_ptr(), c2.data_ptr(), out.data_ptr(), N, M, N, K, 0, float(eps),
@@ -862,9 +871,7 @@ def linear_ln_qkv_h3(x: torch.Tensor, wg: torch.Tensor, c1: torch.Tensor, c2: to
     M = x2.shape[0]
     out = torch.empty((B, S, N), dtype=torch.float32, device=x.device)
     L = _lib.lib()
-    nbytes = int(L.nos_attn_f32x6_workspace(B, num_heads, S, S))
-    ws = torch.empty(nbytes // 2, dtype=torch.int16, device=x.device)
-    skvp = (S + 31) // 32 * 32
+    ws, skvp = _kv_workspace(B, num_heads, S, x.device)
     sc = h3_head_scales(wg, c2, num_heads)
     if _F32_MATH == "h3":
         _gemm_ln_h3(x2, pre, eps, wg, c2, out.view(M, N), EPI_BIAS, kv=(ws, S, skvp, sc))

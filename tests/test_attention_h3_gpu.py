@@ -92,6 +92,32 @@ def test_h3_key_splits_and_tail_tiles(B, S, H, variant):
     assert err < 2e-5 * max(1.0, ref.abs().max().item()), err
 
 
+@pytest.mark.parametrize("variant", ["h3k2", "h3k4"])
+@pytest.mark.parametrize("B,S,H", [(2, 129, 1), (1, 33, 2)])
+def test_h3_plane_output_under_forced_key_splits(B, S, H, variant):
+    """The merge kernel's plane output (the proj GEMM's A planes instead of
+    fp32 O) under a forced key split, at the tolerance of
+    test_h3_key_splits_and_tail_tiles.  (2, 129, 1): a tail tile, five key
+    tiles (four non-empty splits) and a batch stride of the K / V planes (160
+    rows) that differs from S."""
+    x, w, b, gam, bet = _problem(B, S, H, K=32, seed=B * S + H)
+    ref = _ref(x, w, b, gam, bet, H)
+    wg, c1, c2 = ops.fold_layernorm(w, b, gam, bet)
+    ops.set_f32_math("x6")
+    ops.set_attention_f32_variant(variant)
+    try:
+        p = ops.ln_qkv_attention(x, wg, c1, c2, H, planes_out=True)
+        torch.cuda.synchronize()
+    finally:
+        ops.set_f32_math("exact")
+        ops.set_attention_f32_variant("auto")
+    assert p.shape == (B, S, H * 64) and p.rinv is None
+    y = ((p.planes[0].cpu().double() + p.planes[1].cpu().double()) * p.rconst).view(B, S, H * 64)
+    err = (y - ref).abs().max().item()
+    print("plane output error vs fp64:", err)
+    assert err < 2e-5 * max(1.0, ref.abs().max().item()), err
+
+
 def test_h3_planes_padding_rows_never_reach_the_output():
     """fp16 NaN in the planes' padding rows past S of each batch never
     reaches the output (the tail tile re-reads the last key)."""

@@ -51,7 +51,9 @@ DEFECTS = [
     ((BATCHED,), "overlapping batched outputs", dict(sc=(M - 1) * N + N - 1)),
     ((GEMM, LNA), "kvs with N % 3", dict(_KV, N=196, wplane=196 * K, ldr=196, ldc=196)),
     ((GEMM, LNA), "kvs with (N / 3) % 64", dict(_KV, N=288, wplane=288 * K, ldr=288, ldc=288)),
-    ((GEMM, LNA), "kvs with M % S", dict(_KV, S=48, skvp=48)),
+    ((GEMM, LNA), "kvs with M % S", dict(_KV, S=48, skvp=64)),
+    ((GEMM, LNA), "kvs with skvp below the padded key count", dict(_KV, S=16, skvp=16)),  # whole 32-key tiles: 32
+    ((GEMM, LNA), "kvs with skvp above the padded key count", dict(_KV, S=16, skvp=64)),
     ((GEMM, LNA), "kvs together with P", dict(_KV, **_PLANES)),
     ((GEMM, LNA), "psc <= 0", dict(_PLANES, psc=0.0)),
     ((STATS,), "N % 4", dict(N=190)),
