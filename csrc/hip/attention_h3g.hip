@@ -99,8 +99,7 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
   for (int db = 0; db < 2; ++db)
     voff[db] = (4 * hh + tq) * 128 + (((4 * (db ^ vlb)) + 2 * g16 + (tp >> 1)) << 4) + 8 * (tp & 1);
 
-  const int ntiles = (Skv + KVB - 1) / KVB;
-  const int skvp = ntiles * KVB;
+  const int skvp = padded_keys(Skv), ntiles = skvp / KVB;
   const int off = Skv - Sq;  // query i sees keys <= i + off (causal; 0 for self-attention)
   int soff[PPW];
 #pragma unroll
@@ -168,14 +167,7 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
       const float qm = c * nos::pow2i(e);
       fs = nos::pow2i(-e) / ksc;
 #pragma unroll
-      for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-          f16x2_t hi, lo;
-          nos::split2h(f32x2_t{x[ks][j] * qm, x[ks][j + 1] * qm}, hi, lo);
-          qf[ks][0][j] = hi.x; qf[ks][0][j + 1] = hi.y;
-          qf[ks][1][j] = lo.x; qf[ks][1][j + 1] = lo.y;
-        }
+      for (int ks = 0; ks < NKS; ++ks) nos::split8h(x[ks], qm, qf[ks][0], qf[ks][1]);
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
@@ -277,11 +269,7 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
         const f32x2_t e2 = __builtin_elementwise_fma(f32x2_t{s[2 * j2], s[2 * j2 + 1]}, fs2, nm2);
         const f32x2_t x = {__builtin_amdgcn_exp2f(e2.x), __builtin_amdgcn_exp2f(e2.y)};
         ls2[j2 & 1] += x;
-        f16x2_t hi, lo;
-        nos::split2h(x, hi, lo);
-        const int s2 = j2 >> 2, e = 2 * (j2 & 3);
-        pf[s2][0][e] = hi.x; pf[s2][0][e + 1] = hi.y;
-        pf[s2][1][e] = lo.x; pf[s2][1][e + 1] = lo.y;
+        nos::set_pair(pf, j2, x);
       }
       l += (ls2[0].x + ls2[0].y) + (ls2[1].x + ls2[1].y);
 #pragma unroll
@@ -309,12 +297,7 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
         const long long row = part_row(sp, B, b, Sq, qrow);
         float* op = part_o(part, row, ldh, D, h);
 #pragma unroll
-        for (int db = 0; db < 2 * NH; ++db)
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<float4*>(op + 32 * db + 8 * g + 4 * hh) =
-                float4{oacc[db][4 * g + 0] * vinv, oacc[db][4 * g + 1] * vinv, oacc[db][4 * g + 2] * vinv,
-                       oacc[db][4 * g + 3] * vinv};
+        for (int db = 0; db < 2 * NH; ++db) nos::store_acc32(op + 32 * db, oacc[db], vinv, hh);
         if (hh == 0) {
           float* ml = part_ml(part, nsplit, B, Sq, H, ldh, row, h);
           ml[0] = t0 < t1 ? m : -1e30f;
@@ -327,12 +310,7 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
     if (qrow < Sq) {
       float* op = o + b * bso + (long long)qrow * ldo + h * D;
 #pragma unroll
-      for (int db = 0; db < 2 * NH; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<float4*>(op + 32 * db + 8 * g + 4 * hh) =
-              float4{oacc[db][4 * g + 0] * inv, oacc[db][4 * g + 1] * inv, oacc[db][4 * g + 2] * inv,
-                     oacc[db][4 * g + 3] * inv};
+      for (int db = 0; db < 2 * NH; ++db) nos::store_acc32(op + 32 * db, oacc[db], inv, hh);
       // m: the reference in log2 units, lt: the row sum against it; (m + log2 lt) ln 2 with one
       // rounding at the row's magnitude (a backward recomputes P = exp(s - lse) from it)
       if (lse != nullptr && hh == 0)
@@ -344,18 +322,16 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
 
 struct Layout {
   long long planes, absmax, scales, part, total;
-  int nchunk, skvp;
+  int skvp;
 };
 
 Layout layout(int B, int H, int Hkv, int Sq, int Skv, int D) {
   Layout L;
-  L.skvp = (Skv + KVB - 1) / KVB * KVB;
-  L.nchunk = (Skv + ABS_ROWS - 1) / ABS_ROWS;
-  auto al = [](long long x) { return (x + 255) / 256 * 256; };
+  L.skvp = padded_keys(Skv);
   L.planes = 0;
-  L.absmax = al((long long)B * Hkv * L.skvp * 4 * D * 2);
-  L.scales = L.absmax + al((long long)B * Hkv * L.nchunk * 2 * 4);
-  L.part = L.scales + al((long long)B * Hkv * 2 * 4);
+  L.absmax = align256((long long)B * Hkv * L.skvp * 4 * D * 2);
+  L.scales = L.absmax + align256((long long)B * Hkv * abs_chunks(Skv) * 2 * 4);
+  L.part = L.scales + align256((long long)B * Hkv * 2 * 4);
   L.total = L.part + part_bytes(B, H, Sq, D);
   return L;
 }
@@ -366,7 +342,7 @@ int g_kvsplit = 0;  // 0: auto
 
 // Workspace bytes of nos_attn_h3g (K / V planes, scales, key-split partials).
 NOS_API long long nos_attn_h3g_workspace(int B, int H, int Hkv, int Sq, int Skv, int D) {
-  if (B <= 0 || H <= 0 || Hkv <= 0 || Sq <= 0 || Skv <= 0 || (D != 64 && D != 128)) return -1;
+  if (!attn_dims_ok(B, H, Hkv, Sq, Skv, D)) return -1;
   return layout(B, H, Hkv, Sq, Skv, D).total;
 }
 
@@ -379,21 +355,16 @@ NOS_API int nos_attn_h3g_set_kvsplit(int n) {
 namespace {
 
 // the one host path of nos_attn_h3g (lse == nullptr) and nos_attn_h3g_lse
-int attn_h3g_run(const float* q, int ldq, long long bsq, const float* k, int ldk, long long bsk, const float* v, int ldv,
-                 long long bsv, float* o, int ldo, long long bso, int B, int H, int Hkv, int Sq, int Skv, int D,
-                 int causal, float scale, const float* rope_cos, const float* rope_sin, float rope_bound, void* ws,
-                 long long ws_bytes, float* lse, hipStream_t stream) {
-  if (B <= 0 || H <= 0 || Hkv <= 0 || H % Hkv || Sq <= 0 || Skv <= 0 || (D != 64 && D != 128) || !(scale > 0.f))
-    return (int)hipErrorInvalidValue;
-  if (causal && Sq > Skv) return (int)hipErrorInvalidValue;
-  if (ldq < H * D || ldo < H * D || ldk < Hkv * D || ldv < Hkv * D) return (int)hipErrorInvalidValue;
-  if ((ldq | ldk | ldv | ldo) & 3 || (bsq | bsk | bsv | bso) & 3) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15 || ((uintptr_t)ws) & 255)
+int attn_h3g_run(const float* q, int ldq, long long bsq, const Rows& k, const Rows& v, float* o, int ldo, long long bso,
+                 int B, int H, int Hkv, int Sq, int Skv, int D, int causal, float scale, const float* rope_cos,
+                 const float* rope_sin, float rope_bound, void* ws, long long ws_bytes, float* lse,
+                 hipStream_t stream) {
+  if (!attn_call_ok(B, H, Hkv, Sq, Skv, D, causal, scale, ws, ws_bytes, nos_attn_h3g_workspace) ||
+      !Rows{q, ldq, bsq}.ok(H, D) || !Rows{o, ldo, bso}.ok(H, D) || !k.ok(Hkv, D) || !v.ok(Hkv, D))
     return (int)hipErrorInvalidValue;
   if ((rope_cos == nullptr) != (rope_sin == nullptr) || (rope_cos && !(rope_bound > 0.f)))
     return (int)hipErrorInvalidValue;
   const Layout L = layout(B, H, Hkv, Sq, Skv, D);
-  if (ws == nullptr || ws_bytes < L.total) return (int)hipErrorInvalidValue;
   if ((long long)B * H * ((Sq + QB - 1) / QB) * MAX_SPLIT > (1LL << 30) || (long long)B * Hkv * L.skvp * 4 * D > INT_MAX * 8LL)
     return (int)hipErrorInvalidValue;
   auto* base = static_cast<unsigned char*>(ws);
@@ -401,14 +372,7 @@ int attn_h3g_run(const float* q, int ldq, long long bsq, const float* k, int ldk
   auto* absmax = reinterpret_cast<float*>(base + L.absmax);
   auto* kvsc = reinterpret_cast<float*>(base + L.scales);
   auto* part = reinterpret_cast<float*>(base + L.part);
-  const int nbh = B * Hkv;
-  hipLaunchKernelGGL(kv_absmax_kernel, dim3((unsigned)L.nchunk, (unsigned)nbh), dim3(256), 0, stream, k, v, absmax,
-                     Skv, Hkv, D, ldk, bsk, ldv, bsv, L.nchunk);
-  hipLaunchKernelGGL(kv_scale_kernel, dim3((unsigned)((2 * nbh + 255) / 256)), dim3(256), 0, stream, absmax, kvsc,
-                     2 * nbh, L.nchunk, rope_cos ? rope_bound : 1.f);
-  const long long n8 = (long long)nbh * Skv * 2 * (D / 8);
-  hipLaunchKernelGGL(split_kv_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, k, v, kvsc, kvs, Skv,
-                     L.skvp, Hkv, D, ldk, bsk, ldv, bsv, rope_cos, rope_sin, n8);
+  launch_kv_prepass(k, v, absmax, kvsc, kvs, B, Hkv, Skv, D, rope_cos ? rope_bound : 1.f, rope_cos, rope_sin, stream);
   if (int rc = (int)hipGetLastError()) return rc;
   const float c = scale * nos::LOG2E;
   const int nqb = (Sq + QB - 1) / QB;
@@ -452,8 +416,8 @@ NOS_API int nos_attn_h3g(const float* q, int ldq, long long bsq, const float* k,
                          const float* v, int ldv, long long bsv, float* o, int ldo, long long bso, int B, int H, int Hkv,
                          int Sq, int Skv, int D, int causal, float scale, const float* rope_cos, const float* rope_sin,
                          float rope_bound, void* ws, long long ws_bytes, hipStream_t stream) {
-  return attn_h3g_run(q, ldq, bsq, k, ldk, bsk, v, ldv, bsv, o, ldo, bso, B, H, Hkv, Sq, Skv, D, causal, scale, rope_cos,
-                      rope_sin, rope_bound, ws, ws_bytes, nullptr, stream);
+  return attn_h3g_run(q, ldq, bsq, {k, ldk, bsk}, {v, ldv, bsv}, o, ldo, bso, B, H, Hkv, Sq, Skv, D, causal, scale,
+                      rope_cos, rope_sin, rope_bound, ws, ws_bytes, nullptr, stream);
 }
 
 // nos_attn_h3g that also writes lse [B][H][Sq] (contiguous fp32): the natural
@@ -464,6 +428,6 @@ NOS_API int nos_attn_h3g_lse(const float* q, int ldq, long long bsq, const float
                              const float* rope_sin, float rope_bound, void* ws, long long ws_bytes, float* lse,
                              hipStream_t stream) {
   if (lse == nullptr || ((uintptr_t)lse & 3)) return (int)hipErrorInvalidValue;
-  return attn_h3g_run(q, ldq, bsq, k, ldk, bsk, v, ldv, bsv, o, ldo, bso, B, H, Hkv, Sq, Skv, D, causal, scale, rope_cos,
-                      rope_sin, rope_bound, ws, ws_bytes, lse, stream);
+  return attn_h3g_run(q, ldq, bsq, {k, ldk, bsk}, {v, ldv, bsv}, o, ldo, bso, B, H, Hkv, Sq, Skv, D, causal, scale,
+                      rope_cos, rope_sin, rope_bound, ws, ws_bytes, lse, stream);
 }

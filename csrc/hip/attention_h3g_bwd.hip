@@ -118,7 +118,6 @@ __global__ __launch_bounds__(256) void bwd_rows_kernel(const float* __restrict__
                                                        const float* __restrict__ lse, const float* __restrict__ grp,
                                                        _Float16* __restrict__ qrows, float4* __restrict__ rinfo,
                                                        int H, int Hkv, int Sq, int sqp, float c, long long nrows) {
-  typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
   constexpr int TPR = D / 8;
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long row = gid / TPR;
@@ -158,20 +157,14 @@ __global__ __launch_bounds__(256) void bwd_rows_kernel(const float* __restrict__
   const int e = nos::h3_scale_exp(mx * c);   // the forward's Q scale
   const float qm = c * nos::pow2i(e);
   const float dosc = grp[((long long)b * Hkv + h / (H / Hkv)) * GRP + G_DOSC];
-  f16x8 qh, ql, dh, dlo;
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) {
-    f16x2_t h2, l2;
-    nos::split2h(f32x2_t{x[j] * qm, x[j + 1] * qm}, h2, l2);
-    qh[j] = h2.x; qh[j + 1] = h2.y; ql[j] = l2.x; ql[j + 1] = l2.y;
-    nos::split2h(f32x2_t{z[j] * dosc, z[j + 1] * dosc}, h2, l2);
-    dh[j] = h2.x; dh[j + 1] = h2.y; dlo[j] = l2.x; dlo[j + 1] = l2.y;
-  }
+  f16x8_t qh, ql, dh, dlo;
+  nos::split8h(x, qm, qh, ql);
+  nos::split8h(z, dosc, dh, dlo);
   _Float16* dst = qrows + rw * 4 * D + ch * 8;
-  *reinterpret_cast<f16x8*>(dst) = qh;
-  *reinterpret_cast<f16x8*>(dst + D) = ql;
-  *reinterpret_cast<f16x8*>(dst + 2 * D) = dh;
-  *reinterpret_cast<f16x8*>(dst + 3 * D) = dlo;
+  *reinterpret_cast<f16x8_t*>(dst) = qh;
+  *reinterpret_cast<f16x8_t*>(dst + D) = ql;
+  *reinterpret_cast<f16x8_t*>(dst + 2 * D) = dh;
+  *reinterpret_cast<f16x8_t*>(dst + 3 * D) = dlo;
   if (ch == 0) {
     float4 ri = {1.f, 0.f, P_EXP, 0.f};
     if (real) {
@@ -193,7 +186,6 @@ __global__ __launch_bounds__(256) void bwd_tsplit_kernel(const float* __restrict
                                                          const float* __restrict__ scl, int sdiv, int sstride,
                                                          int soff, _Float16* __restrict__ tp, int np, int p0, int S,
                                                          int nt, int Hx, int D, long long n) {
-  typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int d = (int)(i % D);
@@ -209,29 +201,35 @@ __global__ __launch_bounds__(256) void bwd_tsplit_kernel(const float* __restrict
   float v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] = s0 + j < S ? src[(long long)(s0 + j) * ld] * sc : 0.f;
-  f16x8 hi, lo;
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) {
-    f16x2_t h2, l2;
-    nos::split2h(f32x2_t{v[j], v[j + 1]}, h2, l2);
-    hi[j] = h2.x; hi[j + 1] = h2.y; lo[j] = l2.x; lo[j + 1] = l2.y;
-  }
+  f16x8_t hi, lo;
+  nos::split8h(v, 1.f, hi, lo);
   _Float16* dst = tp + ((((long long)bh * nt + tile) * np + p0) * D + d) * 32 + cq * 8;
-  *reinterpret_cast<f16x8*>(dst) = hi;
-  *reinterpret_cast<f16x8*>(dst + (long long)D * 32) = lo;
+  *reinterpret_cast<f16x8_t*>(dst) = hi;
+  *reinterpret_cast<f16x8_t*>(dst + (long long)D * 32) = lo;
 }
 
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;   // a 16-byte chunk in flight
+
 // LDS images (bytes): row planes [plane][32 rows][D + 8], transposed planes
-// [plane][D][TP], the tile's per-row constants
+// [plane][D][TP], the tile's per-row constants.  A tile is staged as 16-byte
+// chunks, chunk tid + 256 i in register i of the 256 threads; row_off / t_off
+// place a chunk in the image (the stores stay in the kernels: docs/status.md)
 template <int D>
 struct Img {
   static constexpr int RS = (D + 8) * 2;       // row stride of a row plane
   static constexpr int ROWS = 4 * 32 * RS;     // four row planes
   static constexpr int TS = TP * 2;            // row stride of a transposed plane
   static constexpr int NR = D / 16;            // 16-byte chunks per thread: four row planes of a tile
-};
 
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;   // a 16-byte chunk in flight
+  // chunk cidx of a tile's four row planes ([row][plane][D] in global memory)
+  static __device__ __forceinline__ int row_off(int cidx) {
+    const int row = cidx / (D / 2), within = cidx % (D / 2);      // 4 D / 8 chunks per row
+    const int plane = within / (D / 8), ch = within % (D / 8);
+    return (plane * 32 + row) * RS + ch * 16;
+  }
+  // chunk cidx of a tile's transposed planes, from the first plane's start
+  static __device__ __forceinline__ int t_off(int cidx) { return (cidx >> 2) * TS + (cidx & 3) * 16; }
+};
 
 __device__ __forceinline__ f16x8_t lds16(const unsigned char* p) { return *reinterpret_cast<const f16x8_t*>(p); }
 
@@ -266,7 +264,7 @@ __global__ __launch_bounds__(64 * BW, 1) void attn_h3g_bwd_dkdv_kernel(
   unsigned char* const vlds = smem + VOFF + wid * VWAVE + lane * 16;   // wave-private: no barrier
   const int g = H / Hkv;
   const int ntq = (Sq + 31) / 32, sqp = ntq * 32;
-  const int skvp = (Skv + KVB - 1) / KVB * KVB;
+  const int skvp = padded_keys(Skv);
   const int off = Skv - Sq;
   const nos::XcdChunk chunk = nos::xcd_chunk(blockIdx.x, gridDim.x, B * Hkv * nkb * nsplit);
 
@@ -337,20 +335,12 @@ __global__ __launch_bounds__(64 * BW, 1) void attn_h3g_bwd_dkdv_kernel(
     };
     auto store_rows = [&]() {
 #pragma unroll
-      for (int i = 0; i < NR; ++i) {
-        const int cidx = tid + 256 * i;
-        const int row = cidx / (D / 2), within = cidx % (D / 2);      // 4 D / 8 chunks per row
-        const int plane = within / (D / 8), ch = within % (D / 8);
-        *reinterpret_cast<u32x4_t*>(smem + (plane * 32 + row) * L::RS + ch * 16) = rr[i];
-      }
+      for (int i = 0; i < NR; ++i) *reinterpret_cast<u32x4_t*>(smem + L::row_off(tid + 256 * i)) = rr[i];
       if (tid < 32) *reinterpret_cast<f32x4_t*>(smem + IOFF + tid * 16) = inf;
     };
     auto store_t = [&]() {
 #pragma unroll
-      for (int i = 0; i < NR; ++i) {
-        const int cidx = tid + 256 * i;
-        *reinterpret_cast<u32x4_t*>(smem + TOFF + (cidx >> 2) * L::TS + (cidx & 3) * 16) = rr[i];
-      }
+      for (int i = 0; i < NR; ++i) *reinterpret_cast<u32x4_t*>(smem + TOFF + L::t_off(tid + 256 * i)) = rr[i];
     };
 
     if (n0 < n1) {
@@ -396,11 +386,7 @@ __global__ __launch_bounds__(64 * BW, 1) void attn_h3g_bwd_dkdv_kernel(
             p2[u] = ok ? __builtin_amdgcn_exp2f(x) : 0.f;
             s[i] = p2[u];
           }
-          f16x2_t hi, lo;
-          const int s2 = j2 >> 2, e = 2 * (j2 & 3);
-          nos::split2h(f32x2_t{p2[0], p2[1]}, hi, lo);
-          pf[s2][0][e] = hi.x; pf[s2][0][e + 1] = hi.y;
-          pf[s2][1][e] = lo.x; pf[s2][1][e + 1] = lo.y;
+          nos::set_pair(pf, j2, f32x2_t{p2[0], p2[1]});
         }
         f32x16_t dp;
 #pragma unroll
@@ -422,11 +408,7 @@ __global__ __launch_bounds__(64 * BW, 1) void attn_h3g_bwd_dkdv_kernel(
             const float delta = *reinterpret_cast<const float*>(smem + IOFF + qloc * 16 + 12);
             d2[u] = s[i] * fmaf(dp[i], a1, -delta * a2);
           }
-          f16x2_t hi, lo;
-          const int s2 = j2 >> 2, e = 2 * (j2 & 3);
-          nos::split2h(f32x2_t{d2[0], d2[1]}, hi, lo);
-          sf[s2][0][e] = hi.x; sf[s2][0][e + 1] = hi.y;
-          sf[s2][1][e] = lo.x; sf[s2][1][e + 1] = lo.y;
+          nos::set_pair(sf, j2, f32x2_t{d2[0], d2[1]});
         }
       }
       __syncthreads();   // every wave is past the row planes of tile n
@@ -459,6 +441,7 @@ __global__ __launch_bounds__(64 * BW, 1) void attn_h3g_bwd_dkdv_kernel(
         pk = part + ((((long long)sp * B + b) * Skv + key) * Hkv + hk) * 2 * D;
         pv = pk + D;
       }
+      // not nos::store_acc32: dK's four stores of a block before dV's reorders the epilogue (docs/status.md)
 #pragma unroll
       for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -514,7 +497,7 @@ __global__ __launch_bounds__(64 * BW, 1) void attn_h3g_bwd_dq_kernel(
   const int lane = tid & 63, r = lane & 31, hh = lane >> 5;
   const int g = H / Hkv;
   const int sqp = (Sq + 31) / 32 * 32;
-  const int ntk = (Skv + KVB - 1) / KVB, skvp = ntk * KVB;
+  const int skvp = padded_keys(Skv), ntk = skvp / KVB;
   const int off = Skv - Sq;
   const nos::XcdChunk chunk = nos::xcd_chunk(blockIdx.x, gridDim.x, B * H * nqb);
 
@@ -569,17 +552,9 @@ __global__ __launch_bounds__(64 * BW, 1) void attn_h3g_bwd_dq_kernel(
     };
     auto store = [&]() {
 #pragma unroll
-      for (int i = 0; i < NR; ++i) {
-        const int cidx = tid + 256 * i;
-        const int row = cidx / (D / 2), within = cidx % (D / 2);
-        const int plane = within / (D / 8), ch = within % (D / 8);
-        *reinterpret_cast<u32x4_t*>(smem + (plane * 32 + row) * L::RS + ch * 16) = rr[i];
-      }
+      for (int i = 0; i < NR; ++i) *reinterpret_cast<u32x4_t*>(smem + L::row_off(tid + 256 * i)) = rr[i];
 #pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        const int cidx = tid + 256 * i;
-        *reinterpret_cast<u32x4_t*>(smem + TOFF + (cidx >> 2) * L::TS + (cidx & 3) * 16) = tt[i];
-      }
+      for (int i = 0; i < NT; ++i) *reinterpret_cast<u32x4_t*>(smem + TOFF + L::t_off(tid + 256 * i)) = tt[i];
     };
 
     fetch(0);
@@ -613,11 +588,7 @@ __global__ __launch_bounds__(64 * BW, 1) void attn_h3g_bwd_dq_kernel(
             const float p = ok ? __builtin_amdgcn_exp2f(x) : 0.f;
             d2[u] = p * fmaf(dp[i], a1, -da2);
           }
-          f16x2_t hi, lo;
-          const int s2 = j2 >> 2, e = 2 * (j2 & 3);
-          nos::split2h(f32x2_t{d2[0], d2[1]}, hi, lo);
-          sf[s2][0][e] = hi.x; sf[s2][0][e + 1] = hi.y;
-          sf[s2][1][e] = lo.x; sf[s2][1][e + 1] = lo.y;
+          nos::set_pair(sf, j2, f32x2_t{d2[0], d2[1]});
         }
 #pragma unroll
         for (int db = 0; db < NDB; ++db)
@@ -637,69 +608,70 @@ __global__ __launch_bounds__(64 * BW, 1) void attn_h3g_bwd_dq_kernel(
     if (qrow < Sq) {
       float* p = dq + b * bsdq + (long long)qrow * lddq + h * D;
 #pragma unroll
-      for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq)
-          *reinterpret_cast<float4*>(p + 32 * db + 8 * gq + 4 * hh) =
-              float4{dqacc[db][4 * gq] * dqf, dqacc[db][4 * gq + 1] * dqf, dqacc[db][4 * gq + 2] * dqf,
-                     dqacc[db][4 * gq + 3] * dqf};
+      for (int db = 0; db < NDB; ++db) nos::store_acc32(p + 32 * db, dqacc[db], dqf, hh);
     }
   }  // items
 }
 
 struct Layout {
   long long kvs, kT, qrows, qT, rinfo, kvabs, qabs, kvsc, grp, part, total;
-  int nck, ncq, skvp, sqp;
+  int skvp, sqp;
 };
 
 Layout layout(int B, int H, int Hkv, int Sq, int Skv, int D) {
   Layout L;
-  L.skvp = (Skv + KVB - 1) / KVB * KVB;
+  L.skvp = padded_keys(Skv);
   L.sqp = (Sq + 31) / 32 * 32;
-  L.nck = (Skv + ABS_ROWS - 1) / ABS_ROWS;
-  L.ncq = (Sq + ABS_ROWS - 1) / ABS_ROWS;
-  auto al = [](long long x) { return (x + 255) / 256 * 256; };
   L.kvs = 0;
-  L.kT = al((long long)B * Hkv * L.skvp * 4 * D * 2);
-  L.qrows = L.kT + al((long long)B * Hkv * L.skvp * 2 * D * 2);
-  L.qT = L.qrows + al((long long)B * H * L.sqp * 4 * D * 2);
-  L.rinfo = L.qT + al((long long)B * H * L.sqp * 4 * D * 2);
-  L.kvabs = L.rinfo + al((long long)B * H * L.sqp * 16);
-  L.qabs = L.kvabs + al((long long)B * Hkv * L.nck * 2 * 4);
-  L.kvsc = L.qabs + al((long long)B * H * L.ncq * 2 * 4);
-  L.grp = L.kvsc + al((long long)B * Hkv * 2 * 4);
-  L.part = L.grp + al((long long)B * Hkv * GRP * 4);
+  L.kT = align256((long long)B * Hkv * L.skvp * 4 * D * 2);
+  L.qrows = L.kT + align256((long long)B * Hkv * L.skvp * 2 * D * 2);
+  L.qT = L.qrows + align256((long long)B * H * L.sqp * 4 * D * 2);
+  L.rinfo = L.qT + align256((long long)B * H * L.sqp * 4 * D * 2);
+  L.kvabs = L.rinfo + align256((long long)B * H * L.sqp * 16);
+  L.qabs = L.kvabs + align256((long long)B * Hkv * abs_chunks(Skv) * 2 * 4);
+  L.kvsc = L.qabs + align256((long long)B * H * abs_chunks(Sq) * 2 * 4);
+  L.grp = L.kvsc + align256((long long)B * Hkv * 2 * 4);
+  L.part = L.grp + align256((long long)B * Hkv * GRP * 4);
   L.total = L.part + (long long)MAX_QSPLIT * B * Skv * Hkv * 2 * D * 4;
   return L;
 }
 
+// what the main launches take: the workspace sections, the gradients, the shape
+struct BwdCall {
+  const _Float16 *kvs, *kT, *qrows, *qT;
+  const float4* rinfo;
+  const float* grp;
+  float *dq, *dk, *dv, *part;
+  int lddq, lddk, lddv;
+  long long bsdq, bsdk, bsdv;
+  int B, H, Hkv, Sq, Skv;
+};
+
 template <int D, bool CAUSAL>
-int launch_main(const _Float16* kvs, const _Float16* kT, const _Float16* qrows, const _Float16* qT,
-                const float4* rinfo, const float* grp, float* dq, int lddq, long long bsdq, float* dk, int lddk,
-                long long bsdk, float* dv, int lddv, long long bsdv, float* part, int B, int H, int Hkv, int Sq,
-                int Skv, hipStream_t stream) {
-  const int nkb = (Skv + BLK - 1) / BLK, nqb = (Sq + BLK - 1) / BLK;
-  const long long items1 = (long long)B * Hkv * nkb;
+int launch_main(const BwdCall& c, hipStream_t stream) {
+  const int nkb = (c.Skv + BLK - 1) / BLK, nqb = (c.Sq + BLK - 1) / BLK;
+  const long long items1 = (long long)c.B * c.Hkv * nkb;
   // ranges of the query sweep while the grid leaves CUs idle (each range keeps at least ~4 tiles)
   const long long slots = nos_effective_cus();
   int nsplit = items1 >= slots ? 1 : (int)(slots / items1);
-  const int ntot = (H / Hkv) * ((Sq + 31) / 32);
+  const int ntot = (c.H / c.Hkv) * ((c.Sq + 31) / 32);
   nsplit = nsplit > MAX_QSPLIT ? MAX_QSPLIT : nsplit;
   while (nsplit > 1 && ntot / nsplit < 4) --nsplit;
   const long long items = items1 * nsplit;
   const int grid = nos_grid_for((const void*)attn_h3g_bwd_dkdv_kernel<D, CAUSAL>, 64 * BW, 0, items);
-  hipLaunchKernelGGL((attn_h3g_bwd_dkdv_kernel<D, CAUSAL>), dim3((unsigned)grid), dim3(64 * BW), 0, stream, kvs, qrows,
-                     qT, rinfo, grp, dk, lddk, bsdk, dv, lddv, bsdv, part, B, H, Hkv, Sq, Skv, nkb, nsplit);
+  hipLaunchKernelGGL((attn_h3g_bwd_dkdv_kernel<D, CAUSAL>), dim3((unsigned)grid), dim3(64 * BW), 0, stream, c.kvs,
+                     c.qrows, c.qT, c.rinfo, c.grp, c.dk, c.lddk, c.bsdk, c.dv, c.lddv, c.bsdv, c.part, c.B, c.H, c.Hkv,
+                     c.Sq, c.Skv, nkb, nsplit);
   if (int rc = (int)hipGetLastError()) return rc;
   if (nsplit > 1) {
-    const long long n4 = (long long)B * Skv * Hkv * 2 * D / 4;
-    hipLaunchKernelGGL(bwd_merge_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, part, dk, lddk, bsdk,
-                       dv, lddv, bsdv, B, Hkv, Skv, D, nsplit, n4);
+    const long long n4 = (long long)c.B * c.Skv * c.Hkv * 2 * D / 4;
+    hipLaunchKernelGGL(bwd_merge_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, c.part, c.dk, c.lddk,
+                       c.bsdk, c.dv, c.lddv, c.bsdv, c.B, c.Hkv, c.Skv, D, nsplit, n4);
   }
-  const long long qitems = (long long)B * H * nqb;
+  const long long qitems = (long long)c.B * c.H * nqb;
   const int qgrid = nos_grid_for((const void*)attn_h3g_bwd_dq_kernel<D, CAUSAL>, 64 * BW, 0, qitems);
-  hipLaunchKernelGGL((attn_h3g_bwd_dq_kernel<D, CAUSAL>), dim3((unsigned)qgrid), dim3(64 * BW), 0, stream, kvs, kT,
-                     qrows, rinfo, grp, dq, lddq, bsdq, B, H, Hkv, Sq, Skv, nqb);
+  hipLaunchKernelGGL((attn_h3g_bwd_dq_kernel<D, CAUSAL>), dim3((unsigned)qgrid), dim3(64 * BW), 0, stream, c.kvs, c.kT,
+                     c.qrows, c.rinfo, c.grp, c.dq, c.lddq, c.bsdq, c.B, c.H, c.Hkv, c.Sq, c.Skv, nqb);
   return (int)hipGetLastError();
 }
 
@@ -707,7 +679,7 @@ int launch_main(const _Float16* kvs, const _Float16* kT, const _Float16* qrows, 
 
 // Workspace bytes of nos_attn_h3g_bwd (planes, constants, partial dK / dV of a split sweep).
 NOS_API long long nos_attn_h3g_bwd_workspace(int B, int H, int Hkv, int Sq, int Skv, int D) {
-  if (B <= 0 || H <= 0 || Hkv <= 0 || H % Hkv || Sq <= 0 || Skv <= 0 || (D != 64 && D != 128)) return -1;
+  if (!attn_dims_ok(B, H, Hkv, Sq, Skv, D) || H % Hkv) return -1;
   return layout(B, H, Hkv, Sq, Skv, D).total;
 }
 
@@ -725,22 +697,13 @@ NOS_API int nos_attn_h3g_bwd(const float* q, int ldq, long long bsq, const float
                              long long bsdq, float* dk, int lddk, long long bsdk, float* dv, int lddv, long long bsdv,
                              int B, int H, int Hkv, int Sq, int Skv, int D, int causal, float scale, void* ws,
                              long long ws_bytes, hipStream_t stream) {
-  if (B <= 0 || H <= 0 || Hkv <= 0 || H % Hkv || Sq <= 0 || Skv <= 0 || (D != 64 && D != 128) || !(scale > 0.f))
+  const Rows Q{q, ldq, bsq}, K{k, ldk, bsk}, V{v, ldv, bsv}, O{o, ldo, bso}, DO{dout, lddo, bsdo};
+  if (!attn_call_ok(B, H, Hkv, Sq, Skv, D, causal, scale, ws, ws_bytes, nos_attn_h3g_bwd_workspace) ||
+      !Q.ok(H, D) || !O.ok(H, D) || !DO.ok(H, D) || !Rows{dq, lddq, bsdq}.ok(H, D) || !K.ok(Hkv, D) ||
+      !V.ok(Hkv, D) || !Rows{dk, lddk, bsdk}.ok(Hkv, D) || !Rows{dv, lddv, bsdv}.ok(Hkv, D))
     return (int)hipErrorInvalidValue;
-  if (causal && Sq > Skv) return (int)hipErrorInvalidValue;
-  if (ldq < H * D || ldo < H * D || lddo < H * D || lddq < H * D || ldk < Hkv * D || ldv < Hkv * D ||
-      lddk < Hkv * D || lddv < Hkv * D)
-    return (int)hipErrorInvalidValue;
-  if ((ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 3 || (bsq | bsk | bsv | bso | bsdo | bsdq | bsdk | bsdv) & 3)
-    return (int)hipErrorInvalidValue;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk |
-       (uintptr_t)dv) & 15 || lse == nullptr || ((uintptr_t)lse & 3) || ((uintptr_t)ws) & 255)
-    return (int)hipErrorInvalidValue;
-  if (q == nullptr || k == nullptr || v == nullptr || o == nullptr || dout == nullptr || dq == nullptr ||
-      dk == nullptr || dv == nullptr)
-    return (int)hipErrorInvalidValue;
+  if (lse == nullptr || ((uintptr_t)lse & 3)) return (int)hipErrorInvalidValue;
   const Layout L = layout(B, H, Hkv, Sq, Skv, D);
-  if (ws == nullptr || ws_bytes < L.total) return (int)hipErrorInvalidValue;
   if ((long long)B * H * L.sqp * 4 * D > INT_MAX * 8LL || (long long)B * Hkv * L.skvp * 4 * D > INT_MAX * 8LL ||
       (long long)B * H * ((Sq + 31) / 32 + (Skv + 31) / 32) * MAX_QSPLIT > (1LL << 30))
     return (int)hipErrorInvalidValue;
@@ -754,29 +717,19 @@ NOS_API int nos_attn_h3g_bwd(const float* q, int ldq, long long bsq, const float
   auto* qabs = reinterpret_cast<float*>(base + L.qabs);
   auto* kvsc = reinterpret_cast<float*>(base + L.kvsc);
   auto* grp = reinterpret_cast<float*>(base + L.grp);
-  auto* part = reinterpret_cast<float*>(base + L.part);
   const int nbk = B * Hkv, nbq = B * H, g = H / Hkv;
   const float c = scale * nos::LOG2E;
   auto blocks = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
 
   // K / V as the forward sees them; Q / dO maxima through the same kernel (H heads of Sq rows)
-  hipLaunchKernelGGL(kv_absmax_kernel, dim3((unsigned)L.nck, (unsigned)nbk), dim3(256), 0, stream, k, v, kvabs, Skv,
-                     Hkv, D, ldk, bsk, ldv, bsv, L.nck);
-  hipLaunchKernelGGL(kv_absmax_kernel, dim3((unsigned)L.ncq, (unsigned)nbq), dim3(256), 0, stream, q, dout, qabs, Sq, H,
-                     D, ldq, bsq, lddo, bsdo, L.ncq);
-  hipLaunchKernelGGL(kv_scale_kernel, blocks(2 * nbk), dim3(256), 0, stream, kvabs, kvsc, 2 * nbk, L.nck, 1.f);
-  hipLaunchKernelGGL(bwd_scale_kernel, blocks(nbk), dim3(256), 0, stream, kvabs, qabs, grp, nbk, Hkv, g, L.nck, L.ncq,
-                     scale, D);
-  const long long n8 = (long long)nbk * Skv * 2 * (D / 8);
-  hipLaunchKernelGGL(split_kv_kernel, blocks(n8), dim3(256), 0, stream, k, v, kvsc, kvs, Skv, L.skvp, Hkv, D, ldk, bsk,
-                     ldv, bsv, (const float*)nullptr, (const float*)nullptr, n8);
+  launch_kv_prepass(K, V, kvabs, kvsc, kvs, B, Hkv, Skv, D, 1.f, nullptr, nullptr, stream);
+  launch_absmax(Q, DO, qabs, nbq, Sq, H, D, stream);
+  hipLaunchKernelGGL(bwd_scale_kernel, blocks(nbk), dim3(256), 0, stream, kvabs, qabs, grp, nbk, Hkv, g,
+                     abs_chunks(Skv), abs_chunks(Sq), scale, D);
   const long long nrows = (long long)nbq * L.sqp;
-  if (D == 64)
-    hipLaunchKernelGGL(bwd_rows_kernel<64>, blocks(nrows * 8), dim3(256), 0, stream, q, ldq, bsq, o, ldo, bso, dout,
-                       lddo, bsdo, lse, grp, qrows, rinfo, H, Hkv, Sq, L.sqp, c, nrows);
-  else
-    hipLaunchKernelGGL(bwd_rows_kernel<128>, blocks(nrows * 16), dim3(256), 0, stream, q, ldq, bsq, o, ldo, bso, dout,
-                       lddo, bsdo, lse, grp, qrows, rinfo, H, Hkv, Sq, L.sqp, c, nrows);
+  hipLaunchKernelGGL(D == 64 ? bwd_rows_kernel<64> : bwd_rows_kernel<128>, blocks(nrows * (D / 8)), dim3(256), 0,
+                     stream, q, ldq, bsq, o, ldo, bso, dout, lddo, bsdo, lse, grp, qrows, rinfo, H, Hkv, Sq, L.sqp, c,
+                     nrows);
   const int ntk = L.skvp / 32, ntq = L.sqp / 32;
   const long long nk = (long long)nbk * ntk * 4 * D, nq = (long long)nbq * ntq * 4 * D;
   hipLaunchKernelGGL(bwd_tsplit_kernel, blocks(nk), dim3(256), 0, stream, k, ldk, bsk, kvsc, 1, 2, 0, kT, 2, 0, Skv, ntk,
@@ -786,13 +739,9 @@ NOS_API int nos_attn_h3g_bwd(const float* q, int ldq, long long bsq, const float
   hipLaunchKernelGGL(bwd_tsplit_kernel, blocks(nq), dim3(256), 0, stream, dout, lddo, bsdo, grp, g, GRP, (int)G_DOSC, qT,
                      4, 2, Sq, ntq, H, D, nq);
   if (int rc = (int)hipGetLastError()) return rc;
-  if (D == 64)
-    return causal ? launch_main<64, true>(kvs, kT, qrows, qT, rinfo, grp, dq, lddq, bsdq, dk, lddk, bsdk, dv, lddv, bsdv,
-                                          part, B, H, Hkv, Sq, Skv, stream)
-                  : launch_main<64, false>(kvs, kT, qrows, qT, rinfo, grp, dq, lddq, bsdq, dk, lddk, bsdk, dv, lddv,
-                                           bsdv, part, B, H, Hkv, Sq, Skv, stream);
-  return causal ? launch_main<128, true>(kvs, kT, qrows, qT, rinfo, grp, dq, lddq, bsdq, dk, lddk, bsdk, dv, lddv, bsdv,
-                                         part, B, H, Hkv, Sq, Skv, stream)
-                : launch_main<128, false>(kvs, kT, qrows, qT, rinfo, grp, dq, lddq, bsdq, dk, lddk, bsdk, dv, lddv,
-                                          bsdv, part, B, H, Hkv, Sq, Skv, stream);
+  const BwdCall call{kvs, kT, qrows, qT, rinfo, grp, dq, dk, dv, reinterpret_cast<float*>(base + L.part), lddq, lddk,
+                     lddv, bsdq, bsdk, bsdv, B, H, Hkv, Sq, Skv};
+  const auto run = D == 64 ? (causal ? launch_main<64, true> : launch_main<64, false>)
+                           : (causal ? launch_main<128, true> : launch_main<128, false>);
+  return run(call, stream);
 }

@@ -9,6 +9,9 @@
 //     (for rotated keys: the host's bound max|cos| + max|sin| on top);
 //  3. split_kv: K (rotated on the fly) and V as four fp16 planes per token,
 //     [b][kv head][token][K hi, K lo, V hi, V lo][D], 16-byte stores.
+//
+// Below the kernels: what the two host paths share -- the padded sizes, the
+// launches of the pre-pass and the argument checks of the entry points.
 #pragma once
 #include "common.h"
 #include "split_f16.h"
@@ -17,6 +20,10 @@ namespace {
 
 constexpr int KVB = 32;                 // keys per tile
 constexpr int ABS_ROWS = 256;           // rows per absmax chunk
+
+__host__ __device__ constexpr int padded_keys(int Skv) { return (Skv + KVB - 1) / KVB * KVB; }  // whole tiles
+constexpr int abs_chunks(int S) { return (S + ABS_ROWS - 1) / ABS_ROWS; }
+constexpr long long align256(long long x) { return (x + 255) / 256 * 256; }  // workspace sections
 
 __device__ __forceinline__ float xor32_max(float v) {
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
@@ -81,7 +88,6 @@ __global__ __launch_bounds__(256) void split_kv_kernel(const float* __restrict__
                                                        int S, int skvp, int Hkv, int D, int ldk, long long bsk,
                                                        int ldv, long long bsv, const float* __restrict__ rc,
                                                        const float* __restrict__ rs, long long n8) {
-  typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n8) return;
   const int c8 = D / 8;
@@ -111,18 +117,54 @@ __global__ __launch_bounds__(256) void split_kv_kernel(const float* __restrict__
 #pragma unroll
     for (int j = 0; j < 8; ++j) x[j] = lo ? fmaf(x[j], cr[j], -p[j] * sr[j]) : fmaf(x[j], cr[j], p[j] * sr[j]);
   }
-  const float sc = kvsc[bh * 2 + t];
-  f16x8 hi, lo;
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) {
-    f16x2_t h2, l2;
-    nos::split2h(f32x2_t{x[j] * sc, x[j + 1] * sc}, h2, l2);
-    hi[j] = h2.x; hi[j + 1] = h2.y;
-    lo[j] = l2.x; lo[j + 1] = l2.y;
-  }
+  f16x8_t hi, lo;
+  nos::split8h(x, kvsc[bh * 2 + t], hi, lo);
   _Float16* dst = kvs + (((long long)bh * skvp + s) * 4 + 2 * t) * D + ch * 8;
-  *reinterpret_cast<f16x8*>(dst) = hi;
-  *reinterpret_cast<f16x8*>(dst + D) = lo;
+  *reinterpret_cast<f16x8_t*>(dst) = hi;
+  *reinterpret_cast<f16x8_t*>(dst + D) = lo;
+}
+
+// ---------------------------------------------------------------- host
+// a [B, S, heads, D] fp32 operand: token row stride ld, batch stride bs (floats)
+struct Rows {
+  const float* p;
+  int ld;
+  long long bs;
+  bool ok(int heads, int D) const {
+    return p != nullptr && ((uintptr_t)p & 15) == 0 && ld >= heads * D && (ld & 3) == 0 && (bs & 3) == 0;
+  }
+};
+
+// the absmax launch: a / b [nb / heads, S, heads, D] -> part[nb][abs_chunks(S)][2]
+inline void launch_absmax(const Rows& a, const Rows& b, float* part, int nb, int S, int heads, int D,
+                          hipStream_t stream) {
+  const int nchunk = abs_chunks(S);
+  hipLaunchKernelGGL(kv_absmax_kernel, dim3((unsigned)nchunk, (unsigned)nb), dim3(256), 0, stream, a.p, b.p, part, S,
+                     heads, D, a.ld, a.bs, b.ld, b.bs, nchunk);
+}
+
+// the three launches: k / v [B, Skv, Hkv, D] -> absmax partials, scales kvsc
+// [B * Hkv][2] and planes kvs (padded_keys(Skv) rows per head); rc / rs: the
+// rotary tables of K (or null) under the bound kbound
+inline void launch_kv_prepass(const Rows& k, const Rows& v, float* absmax, float* kvsc, _Float16* kvs, int B, int Hkv,
+                              int Skv, int D, float kbound, const float* rc, const float* rs, hipStream_t stream) {
+  const int nbh = B * Hkv;
+  launch_absmax(k, v, absmax, nbh, Skv, Hkv, D, stream);
+  hipLaunchKernelGGL(kv_scale_kernel, dim3((unsigned)((2 * nbh + 255) / 256)), dim3(256), 0, stream, absmax, kvsc,
+                     2 * nbh, abs_chunks(Skv), kbound);
+  const long long n8 = (long long)nbh * Skv * 2 * (D / 8);
+  hipLaunchKernelGGL(split_kv_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, k.p, v.p, kvsc, kvs, Skv,
+                     padded_keys(Skv), Hkv, D, k.ld, k.bs, v.ld, v.bs, rc, rs, n8);
+}
+
+// the checks every entry point makes; need: its workspace function (-1 for bad dims)
+inline bool attn_dims_ok(int B, int H, int Hkv, int Sq, int Skv, int D) {
+  return B > 0 && H > 0 && Hkv > 0 && Sq > 0 && Skv > 0 && (D == 64 || D == 128);
+}
+inline bool attn_call_ok(int B, int H, int Hkv, int Sq, int Skv, int D, int causal, float scale, const void* ws,
+                         long long ws_bytes, long long (*need)(int, int, int, int, int, int)) {
+  return attn_dims_ok(B, H, Hkv, Sq, Skv, D) && H % Hkv == 0 && scale > 0.f && !(causal && Sq > Skv) &&
+         ws != nullptr && ((uintptr_t)ws & 255) == 0 && ws_bytes >= need(B, H, Hkv, Sq, Skv, D);
 }
 
 }  // namespace

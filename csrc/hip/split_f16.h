@@ -40,6 +40,36 @@ __device__ __forceinline__ void split2h(f32x2_t x, f16x2_t& hi, f16x2_t& lo) {
   lo = __builtin_bit_cast(f16x2_t, lb);
 }
 
+// eight floats times a scale -> the hi / lo pieces of eight operand elements
+__device__ __forceinline__ void split8h(const float (&x)[8], float sc, f16x8_t& hi, f16x8_t& lo) {
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) {
+    f16x2_t h2, l2;
+    split2h(f32x2_t{x[j] * sc, x[j + 1] * sc}, h2, l2);
+    hi[j] = h2.x; hi[j + 1] = h2.y;
+    lo[j] = l2.x; lo[j + 1] = l2.y;
+  }
+}
+
+// values 2 j2, 2 j2 + 1 of a lane's 32x32 accumulator as B-operand pieces of
+// the next product: f[16-row step][hi, lo], in the order the lane holds them
+__device__ __forceinline__ void set_pair(f16x8_t (&f)[2][2], int j2, f32x2_t v) {
+  f16x2_t hi, lo;
+  split2h(v, hi, lo);
+  const int s2 = j2 >> 2, e = 2 * (j2 & 3);
+  f[s2][0][e] = hi.x; f[s2][0][e + 1] = hi.y;
+  f[s2][1][e] = lo.x; f[s2][1][e + 1] = lo.y;
+}
+
+// a lane's 32 dims of a transposed 32x32 accumulator (acc[4 g + j]: dim
+// 8 g + 4 hh + j, hh = lane >> 5) times f to row p, 16-byte stores
+__device__ __forceinline__ void store_acc32(float* p, const f32x16_t& acc, float f, int hh) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+    *reinterpret_cast<float4*>(p + 8 * g + 4 * hh) =
+        float4{acc[4 * g] * f, acc[4 * g + 1] * f, acc[4 * g + 2] * f, acc[4 * g + 3] * f};
+}
+
 // acc += a.b as the three piece products, smallest first (a: A operand)
 __device__ __forceinline__ f32x16_t mma3h(const f16x8_t (&a)[2], const f16x8_t (&b)[2], f32x16_t acc) {
   acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], acc, 0, 0, 0);

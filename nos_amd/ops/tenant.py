@@ -274,13 +274,25 @@ def softmax(x: torch.Tensor) -> torch.Tensor:
     return out.view(x.shape)
 
 
-def _rows_view(x: torch.Tensor) -> tuple[int, int]:
-    """(token row stride, batch stride) of x [B, S, H, D] whose heads are
-    contiguous per token (e.g. a slice of a fused projection)."""
-    B, S, H, D = x.shape
-    if x.stride(-1) != 1 or x.stride(-2) != D:
-        raise ValueError("x needs contiguous heads per token")
-    return x.stride(1), x.stride(0)
+def _rows(x: torch.Tensor, aligned: bool = False) -> tuple[torch.Tensor, int, int]:
+    """x [B, S, H, D] as the kernels take it: (x or a copy, token row stride,
+    batch stride), copied only when its heads are not contiguous per token
+    (a slice of a fused projection is taken as it is).  ``aligned`` (the h3
+    attention): in fp32, and also copied when a stride is no multiple of 4
+    floats or the pointer not 16-byte aligned."""
+    if aligned:
+        x = _f32(x)
+    if x.stride(-1) != 1 or x.stride(-2) != x.shape[-1]:
+        x = x.contiguous()
+    if aligned and (x.stride(1) % 4 or x.stride(0) % 4 or x.data_ptr() % 16):
+        x = x.clone(memory_format=torch.contiguous_format)
+    return x, x.stride(1), x.stride(0)
+
+
+def _workspace(nbytes: int, device) -> tuple[torch.Tensor, int]:
+    """nbytes of device scratch: (the tensor that owns it, its 256-byte aligned pointer)."""
+    ws = torch.empty((nbytes + 256,), dtype=torch.uint8, device=device)
+    return ws, (ws.data_ptr() + 255) // 256 * 256
 
 
 def rotary(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
@@ -288,9 +300,7 @@ def rotary(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tenso
     if not x.is_cuda:
         return rope_ref(x, cos, sin)
     B, S, H, D = x.shape
-    if x.stride(-1) != 1 or x.stride(-2) != D:
-        x = x.contiguous()
-    ld, bs = _rows_view(x)
+    x, ld, bs = _rows(x)
     c, s = cos.float().contiguous(), sin.float().contiguous()
     if c.shape[0] < S or c.shape[1] != D:
         raise ValueError(f"rotary tables must be [>= {S}, {D}]")
@@ -538,36 +548,27 @@ def _rope_bound(cos: torch.Tensor, sin: torch.Tensor) -> float:
     return b
 
 
-def sdpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False, scale: float | None = None,
-         rope: tuple | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
-    """softmax(scale q k^T [causal]) v: q [B, Sq, H, D], k / v [B, Skv, Hkv, D]
-    (heads contiguous per token; any token / batch strides, e.g. slices of a
-    fused QKV projection), D = 64 or 128, H % Hkv == 0.  ``rope`` = (cos, sin)
-    fp32 tables [Skv, D]: q and k are rotated first (inside the kernels)."""
-    if not q.is_cuda:
-        return sdpa_ref(q, k, v, causal, scale, rope)
-    dt = q.dtype
+def _check_attn_shapes(what: str, q, k, v) -> None:
+    B, Sq, H, D = q.shape
+    Hkv = k.shape[2]
+    if D not in (64, 128) or H % Hkv or v.shape != k.shape or k.shape[0] != B or k.shape[3] != D:
+        raise ValueError(f"native {what}: head_dim 64/128, H % Hkv == 0; got q {tuple(q.shape)}, k {tuple(k.shape)}")
+
+
+def _sdpa_fwd(what: str, q, k, v, causal, scale, rope=None, out=None, lse: bool = False):
+    """The forward of :func:`sdpa` and :func:`sdpa_lse` on CUDA tensors:
+    (o, the rows' log-sum-exp or None)."""
+    _check_attn_shapes(what, q, k, v)
     B, Sq, H, D = q.shape
     Skv, Hkv = k.shape[1], k.shape[2]
-    if D not in (64, 128) or H % Hkv or v.shape != k.shape or k.shape[0] != B or k.shape[3] != D:
-        raise ValueError(f"native sdpa: head_dim 64/128, H % Hkv == 0; got q {tuple(q.shape)}, k {tuple(k.shape)}")
-    qf, kf, vf = (_f32(t) for t in (q, k, v))
-    try:
-        (ldq, bsq), (ldk, bsk), (ldv, bsv) = _rows_view(qf), _rows_view(kf), _rows_view(vf)
-    except ValueError:
-        qf, kf, vf = qf.contiguous(), kf.contiguous(), vf.contiguous()
-        (ldq, bsq), (ldk, bsk), (ldv, bsv) = _rows_view(qf), _rows_view(kf), _rows_view(vf)
-    if any(s % 4 for s in (ldq, bsq, ldk, bsk, ldv, bsv)) or any(t.data_ptr() % 16 for t in (qf, kf, vf)):
-        qf, kf, vf = qf.contiguous(), kf.contiguous(), vf.contiguous()
-        (ldq, bsq), (ldk, bsk), (ldv, bsv) = _rows_view(qf), _rows_view(kf), _rows_view(vf)
+    (qf, ldq, bsq), (kf, ldk, bsk), (vf, ldv, bsv) = (_rows(t, aligned=True) for t in (q, k, v))
     if out is None or out.dtype != torch.float32:
         o = torch.empty((B, Sq, H, D), dtype=torch.float32, device=q.device)
     else:
         o = out
     L = _lib.lib()
     nbytes = int(L.nos_attn_h3g_workspace(B, H, Hkv, Sq, Skv, D))
-    ws = torch.empty((nbytes + 256,), dtype=torch.uint8, device=q.device)
-    wptr = (ws.data_ptr() + 255) // 256 * 256
+    ws, wptr = _workspace(nbytes, q.device)
     rc_, rs_, rb = None, None, 0.0
     if rope is not None:
         rc_, rs_ = rope[0], rope[1]
@@ -575,14 +576,30 @@ def sdpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False
             raise ValueError(f"rope tables must be contiguous fp32 [{Skv}, {D}]")
         rb = _rope_bound(rc_, rs_)
     sc = scale if scale is not None else 1.0 / math.sqrt(D)
-    rc = L.nos_attn_h3g(qf.data_ptr(), ldq, bsq, kf.data_ptr(), ldk, bsk, vf.data_ptr(), ldv, bsv, o.data_ptr(),
-                        o.stride(1), o.stride(0), B, H, Hkv, Sq, Skv, D, int(bool(causal)), float(sc), _ptr(rc_),
-                        _ptr(rs_), float(rb), wptr, nbytes, _stream())
-    _lib.check(rc, "nos_attn_h3g")
+    args = (qf.data_ptr(), ldq, bsq, kf.data_ptr(), ldk, bsk, vf.data_ptr(), ldv, bsv, o.data_ptr(), o.stride(1),
+            o.stride(0), B, H, Hkv, Sq, Skv, D, int(bool(causal)), float(sc), _ptr(rc_), _ptr(rs_), float(rb), wptr,
+            nbytes)
+    ls = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device) if lse else None
+    if lse:
+        _lib.check(L.nos_attn_h3g_lse(*args, ls.data_ptr(), _stream()), "nos_attn_h3g_lse")
+    else:
+        _lib.check(L.nos_attn_h3g(*args, _stream()), "nos_attn_h3g")
     if out is not None and out is not o:
         out.copy_(o)
-        return out
-    return o if dt == torch.float32 else o.to(dt)
+        return out, ls
+    return (o if q.dtype == torch.float32 else o.to(q.dtype)), ls
+
+
+def sdpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False, scale: float | None = None,
+         rope: tuple | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """softmax(scale q k^T [causal]) v: q [B, Sq, H, D], k / v [B, Skv, Hkv, D]
+    (heads contiguous per token; any token / batch strides, e.g. slices of a
+    fused QKV projection), D = 64 or 128, H % Hkv == 0.  ``rope`` = (cos, sin)
+    fp32 tables [Skv, D]: q and k are rotated first (inside the kernels).
+    ``out``: the tensor to fill (a non-fp32 one by copy)."""
+    if not q.is_cuda:
+        return sdpa_ref(q, k, v, causal, scale, rope)
+    return _sdpa_fwd("sdpa", q, k, v, causal, scale, rope, out)[0]
 
 
 # ------------------------------------------------------------------ training attention (attention_h3g_bwd.hip)
@@ -608,51 +625,13 @@ def sdpa_bwd_workspace_bytes(B: int, H: int, Hkv: int, Sq: int, Skv: int, D: int
             + BWD_MAX_QSPLIT * B * Skv * Hkv * 2 * D * 4)           # partial dK / dV of a split sweep
 
 
-def _train_rows(t: torch.Tensor) -> tuple[torch.Tensor, int, int]:
-    """fp32 t [B, S, H, D] as the kernels take it (heads contiguous per token,
-    16-byte aligned, strides in multiples of 4 floats), copied only if it is not."""
-    t = _f32(t)
-    try:
-        ld, bs = _rows_view(t)
-    except ValueError:
-        t = t.contiguous()
-        ld, bs = _rows_view(t)
-    if ld % 4 or bs % 4 or t.data_ptr() % 16:
-        t = t.clone(memory_format=torch.contiguous_format)
-        ld, bs = _rows_view(t)
-    return t, ld, bs
-
-
-def _check_attn_shapes(what: str, q, k, v) -> None:
-    B, Sq, H, D = q.shape
-    Hkv = k.shape[2]
-    if D not in (64, 128) or H % Hkv or v.shape != k.shape or k.shape[0] != B or k.shape[3] != D:
-        raise ValueError(f"native {what}: head_dim 64/128, H % Hkv == 0; got q {tuple(q.shape)}, k {tuple(k.shape)}")
-
-
 def sdpa_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False, scale: float | None = None):
     """:func:`sdpa` (no rotary) that also returns the rows' log-sum-exp for
     :func:`sdpa_bwd`: (o [B, Sq, H, D], lse fp32 [B, H, Sq]); the same O bits
     as :func:`sdpa` (``nos_attn_h3g_lse``)."""
     if not q.is_cuda:
         return sdpa_lse_ref(q, k, v, causal, scale)
-    _check_attn_shapes("sdpa_lse", q, k, v)
-    dt = q.dtype
-    B, Sq, H, D = q.shape
-    Skv, Hkv = k.shape[1], k.shape[2]
-    (qf, ldq, bsq), (kf, ldk, bsk), (vf, ldv, bsv) = _train_rows(q), _train_rows(k), _train_rows(v)
-    o = torch.empty((B, Sq, H, D), dtype=torch.float32, device=q.device)
-    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
-    L = _lib.lib()
-    nbytes = int(L.nos_attn_h3g_workspace(B, H, Hkv, Sq, Skv, D))
-    ws = torch.empty((nbytes + 256,), dtype=torch.uint8, device=q.device)
-    wptr = (ws.data_ptr() + 255) // 256 * 256
-    sc = scale if scale is not None else 1.0 / math.sqrt(D)
-    rc = L.nos_attn_h3g_lse(qf.data_ptr(), ldq, bsq, kf.data_ptr(), ldk, bsk, vf.data_ptr(), ldv, bsv, o.data_ptr(),
-                            o.stride(1), o.stride(0), B, H, Hkv, Sq, Skv, D, int(bool(causal)), float(sc), None, None,
-                            0.0, wptr, nbytes, lse.data_ptr(), _stream())
-    _lib.check(rc, "nos_attn_h3g_lse")
-    return (o if dt == torch.float32 else o.to(dt)), lse
+    return _sdpa_fwd("sdpa_lse", q, k, v, causal, scale, lse=True)
 
 
 def sdpa_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, lse: torch.Tensor, do: torch.Tensor,
@@ -670,22 +649,20 @@ def sdpa_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor,
     Skv, Hkv = k.shape[1], k.shape[2]
     if o.shape != q.shape or do.shape != q.shape or lse.shape != (B, H, Sq):
         raise ValueError(f"sdpa_bwd: o / do must be {tuple(q.shape)} and lse {(B, H, Sq)}")
-    (qf, ldq, bsq), (kf, ldk, bsk), (vf, ldv, bsv) = _train_rows(q), _train_rows(k), _train_rows(v)
-    (of, ldo, bso), (dof, lddo, bsdo) = _train_rows(o), _train_rows(do)
+    (qf, ldq, bsq), (kf, ldk, bsk), (vf, ldv, bsv), (of, ldo, bso), (dof, lddo, bsdo) = (
+        _rows(t, aligned=True) for t in (q, k, v, o, do))
     lf = lse.float().contiguous()
     if out is not None:
         dq, dk, dv = out
         for t, ref in ((dq, q), (dk, k), (dv, k)):
-            if t.shape != ref.shape or t.dtype != torch.float32 or not t.is_cuda or t.data_ptr() % 16 \
-                    or any(x % 4 for x in _rows_view(t)):
+            if t.shape != ref.shape or t.dtype != torch.float32 or not t.is_cuda or _rows(t, aligned=True)[0] is not t:
                 raise ValueError("sdpa_bwd: out must be aligned fp32 CUDA tensors in the shapes of q, k, v")
     else:
         dq = torch.empty((B, Sq, H, D), dtype=torch.float32, device=q.device)
         dk = torch.empty((B, Skv, Hkv, D), dtype=torch.float32, device=q.device)
         dv = torch.empty((B, Skv, Hkv, D), dtype=torch.float32, device=q.device)
     nbytes = sdpa_bwd_workspace_bytes(B, H, Hkv, Sq, Skv, D)
-    ws = torch.empty((nbytes + 256,), dtype=torch.uint8, device=q.device)
-    wptr = (ws.data_ptr() + 255) // 256 * 256
+    ws, wptr = _workspace(nbytes, q.device)
     sc = scale if scale is not None else 1.0 / math.sqrt(D)
     rc = _lib.lib().nos_attn_h3g_bwd(qf.data_ptr(), ldq, bsq, kf.data_ptr(), ldk, bsk, vf.data_ptr(), ldv, bsv,
                                      of.data_ptr(), ldo, bso, dof.data_ptr(), lddo, bsdo, lf.data_ptr(),
@@ -721,11 +698,7 @@ def kv_write(cache: torch.Tensor, x: torch.Tensor, pos: torch.Tensor, rope: tupl
     S = x.shape[1]
     if x.shape[0] != B or x.shape[2:] != cache.shape[2:] or not cache.is_contiguous():
         raise ValueError(f"kv_write: x {tuple(x.shape)} does not fit the cache {tuple(cache.shape)}")
-    try:
-        ldx, bsx = _rows_view(x)
-    except ValueError:
-        x = x.contiguous()
-        ldx, bsx = _rows_view(x)
+    x, ldx, bsx = _rows(x)
     c = s_ = None
     R = 0
     if rope is not None:
@@ -737,11 +710,7 @@ def kv_write(cache: torch.Tensor, x: torch.Tensor, pos: torch.Tensor, rope: tupl
         if c2.shape != cache.shape or c2.dtype != cache.dtype or x2.shape != x.shape or x2.dtype != x.dtype \
                 or not c2.is_contiguous():
             raise ValueError("kv_write: the second write must match the first's shapes and dtypes")
-        try:
-            ld2, bs2 = _rows_view(x2)
-        except ValueError:
-            x2 = x2.contiguous()
-            ld2, bs2 = _rows_view(x2)
+        x2, ld2, bs2 = _rows(x2)
         x2p, c2p = x2.data_ptr(), c2.data_ptr()
     _lib.check(_lib.lib().nos_kv_write(x.data_ptr(), _bf(x), ldx, bsx, cache.data_ptr(), _bf(cache),
                                        _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R, B, S, H, D, L, x2p, ld2, bs2,
@@ -756,11 +725,7 @@ def rotary_at(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.
     if not x.is_cuda:
         return rotary_at_ref(x, cos, sin, pos)
     B, S, H, D = x.shape
-    try:
-        ldx, bsx = _rows_view(x)
-    except ValueError:
-        x = x.contiguous()
-        ldx, bsx = _rows_view(x)
+    x, ldx, bsx = _rows(x)
     c, s_ = cos.float().contiguous(), sin.float().contiguous()
     if c.shape[1] != D or s_.shape != c.shape:
         raise ValueError(f"rotary tables must be [positions, {D}]")
@@ -808,11 +773,7 @@ def sdpa_cache(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: torch.T
     if (kc.shape != vc.shape or kc.dtype != vc.dtype or kc.shape[0] != B or kc.shape[3] != D or H % Hkv
             or D not in (64, 128) or not kc.is_contiguous() or not vc.is_contiguous()):
         raise ValueError(f"sdpa_cache: q {tuple(q.shape)} vs caches {tuple(kc.shape)}")
-    try:
-        ldq, bsq = _rows_view(q)
-    except ValueError:
-        q = q.contiguous()
-        ldq, bsq = _rows_view(q)
+    q, ldq, bsq = _rows(q)
     c = s_ = None
     R = 0
     if rope is not None:
@@ -829,16 +790,7 @@ def sdpa_cache(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: torch.T
         kn, vn = fresh
         if kn.shape != (B, Sq, Hkv, D) or vn.shape != kn.shape or kn.dtype != vn.dtype:
             raise ValueError(f"sdpa_cache: fresh K / V {tuple(kn.shape)} for q {tuple(q.shape)}")
-        try:
-            ldk, bsk = _rows_view(kn)
-        except ValueError:
-            kn = kn.contiguous()
-            ldk, bsk = _rows_view(kn)
-        try:
-            ldv, bsv = _rows_view(vn)
-        except ValueError:
-            vn = vn.contiguous()
-            ldv, bsv = _rows_view(vn)
+        (kn, ldk, bsk), (vn, ldv, bsv) = _rows(kn), _rows(vn)
         nbf = _bf(kn)
     if sync is not None and (not sync.is_cuda or sync.dtype != torch.int32 or not sync.is_contiguous()
                              or sync.numel() < B * Hkv):

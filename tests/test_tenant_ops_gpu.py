@@ -150,6 +150,23 @@ def test_sdpa_reads_strided_slices_of_a_fused_projection():
     _close_to_fp64(got, ref64, T.sdpa_ref(q, k, v))
 
 
+@pytest.mark.parametrize("D,causal,Sq,Skv", [(64, False, 33, 33), (128, True, 40, 72)])
+def test_sdpa_copies_contiguous_views_that_are_not_16_byte_aligned(D, causal, Sq, Skv):
+    """q, k, v as contiguous views one float into their storage: sdpa aligns
+    them by copy (it used to hand them to the kernel, which refused them) and
+    gives the bits it gives for the same values in fresh tensors."""
+    g = torch.Generator(device="cuda").manual_seed(6)
+
+    def off_by_one(*shape):
+        t = torch.randn(math.prod(shape) + 1, device="cuda", generator=g)[1:].view(shape)
+        assert t.is_contiguous() and t.data_ptr() % 16 == 4
+        return t
+
+    q, k, v = off_by_one(1, Sq, 2, D), off_by_one(1, Skv, 1, D), off_by_one(1, Skv, 1, D)
+    got = T.sdpa(q, k, v, causal=causal)
+    assert torch.equal(got, T.sdpa(q.clone(), k.clone(), v.clone(), causal=causal))
+
+
 def test_linear_rms_matches_fp64():
     g = torch.Generator(device="cuda").manual_seed(6)
     x = torch.randn(3, 70, 256, device="cuda", generator=g) * 5
