@@ -364,6 +364,8 @@ int attn_h3g_run(const float* q, int ldq, long long bsq, const Rows& k, const Ro
     return (int)hipErrorInvalidValue;
   if ((rope_cos == nullptr) != (rope_sin == nullptr) || (rope_cos && !(rope_bound > 0.f)))
     return (int)hipErrorInvalidValue;
+  // query row i is rotated at table row i + Skv - Sq: with more queries than keys the first rows have none
+  if (rope_cos && Sq > Skv) return (int)hipErrorInvalidValue;
   const Layout L = layout(B, H, Hkv, Sq, Skv, D);
   if ((long long)B * H * ((Sq + QB - 1) / QB) * MAX_SPLIT > (1LL << 30) || (long long)B * Hkv * L.skvp * 4 * D > INT_MAX * 8LL)
     return (int)hipErrorInvalidValue;
@@ -410,7 +412,8 @@ int attn_h3g_run(const float* q, int ldq, long long bsq, const Rows& k, const Ro
 // (ldo, bso).  D = 64 or 128.  causal: query i attends keys <= i + Skv - Sq.
 // rope_cos / rope_sin (fp32 [Skv][D], or null): rotate Q (rows i + Skv - Sq)
 // and K (rows = key positions) by rotate_half first; rope_bound >=
-// max |cos| + max |sin| of the tables (bounds the rotated keys).  ws: at
+// max |cos| + max |sin| of the tables (bounds the rotated keys); refused
+// with Sq > Skv, causal or not (no table row for the first queries).  ws: at
 // least nos_attn_h3g_workspace() bytes, 256-byte aligned.
 NOS_API int nos_attn_h3g(const float* q, int ldq, long long bsq, const float* k, int ldk, long long bsk,
                          const float* v, int ldv, long long bsv, float* o, int ldo, long long bso, int B, int H, int Hkv,

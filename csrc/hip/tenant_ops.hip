@@ -70,8 +70,10 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const void* __restrict__ x
 
 // ------------------------------------------------------------------ softmax
 // softmax over the last dim: one wave per row, an online (max, sum) per lane
-// merged across the wave, then one write pass.  Rows of -inf give NaN, as
-// torch.softmax does.
+// merged across the wave, then one write pass.  -inf is a masked column: it
+// adds nothing to the sum (a lane that has so far seen only -inf keeps s = 0)
+// and comes out exactly 0.  A row of nothing but -inf gives NaN, and so does a
+// row that holds a NaN or +inf, as torch.softmax does.
 __global__ __launch_bounds__(256) void softmax_kernel(const void* __restrict__ x, void* __restrict__ y, int rows, int L,
                                                       int ldx, int ldy, int bf16) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -84,12 +86,12 @@ __global__ __launch_bounds__(256) void softmax_kernel(const void* __restrict__ x
     if (v > m) {
       s = s * __expf(m - v) + 1.f;
       m = v;
-    } else {
+    } else if (v != -INFINITY) {  // -inf - -inf would be NaN; a NaN v still gets here
       s += __expf(v - m);
     }
   }
   const float M = nos::wave_max(m);
-  s = (m == -INFINITY) ? 0.f : s * __expf(m - M);
+  if (m != -INFINITY) s *= __expf(m - M);  // else s is 0, or NaN where the lane met a NaN
   const float inv = 1.f / nos::wave_sum(s);
   for (int d = lane; d < L; d += 64) st_from_f32(y, yo + d, __expf(ld_as_f32(x, xo + d, bf16) - M) * inv, bf16);
 }

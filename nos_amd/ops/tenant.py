@@ -66,6 +66,12 @@ def _bf(t: torch.Tensor) -> int:
 
 
 # ------------------------------------------------------------------ references
+def _ref_dtype(t: torch.Tensor) -> torch.dtype:
+    """The dtype a reference computes in: fp32, or fp64 for fp64 inputs (a
+    test's high-precision reference must not be rounded to fp32 on the way)."""
+    return torch.float64 if t.dtype == torch.float64 else torch.float32
+
+
 def conv2d_ref(x, w, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), act=None, residual=None,
                residual_first: bool = False, groups: int = 1):
     y = F.conv2d(x.float(), w.float(), None if bias is None else bias.float(), stride, padding, dilation, groups)
@@ -80,18 +86,20 @@ def conv2d_ref(x, w, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), 
 def rope_ref(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: int = 0) -> torch.Tensor:
     """rotate_half rotary on x [B, S, H, D] with tables [>= pos0 + S, D]."""
     S, D = x.shape[1], x.shape[-1]
-    c = cos[pos0:pos0 + S].float()[None, :, None, :]
-    s = sin[pos0:pos0 + S].float()[None, :, None, :]
-    xf = x.float()
+    ct = _ref_dtype(x)
+    c = cos[pos0:pos0 + S].to(ct)[None, :, None, :]
+    s = sin[pos0:pos0 + S].to(ct)[None, :, None, :]
+    xf = x.to(ct)
     rot = torch.cat([-xf[..., D // 2:], xf[..., :D // 2]], dim=-1)
     return (xf * c + rot * s).to(x.dtype)
 
 
 def sdpa_ref(q, k, v, causal: bool = False, scale: float | None = None, rope=None) -> torch.Tensor:
-    """q [B, Sq, H, D], k / v [B, Skv, Hkv, D] -> [B, Sq, H, D] in fp32 math."""
+    """q [B, Sq, H, D], k / v [B, Skv, Hkv, D] -> [B, Sq, H, D] in fp32 math (fp64 inputs: fp64 math)."""
     B, Sq, H, D = q.shape
     Skv, Hkv = k.shape[1], k.shape[2]
-    qf, kf, vf = q.float(), k.float(), v.float()
+    ct = _ref_dtype(q)
+    qf, kf, vf = q.to(ct), k.to(ct), v.to(ct)
     if rope is not None:
         cos, sin = rope[0], rope[1]
         qf = rope_ref(qf, cos, sin, Skv - Sq)
@@ -120,15 +128,11 @@ def _train_scores(q, k, causal: bool, scale: float):
     return s
 
 
-def _train_dtype(t: torch.Tensor) -> torch.dtype:
-    return t.dtype if t.dtype in (torch.float32, torch.float64) else torch.float32
-
-
 def sdpa_lse_ref(q, k, v, causal: bool = False, scale: float | None = None):
     """(o, lse) of :func:`sdpa_lse` in plain torch math in the input dtype
     (fp64 stays fp64): lse [B, H, Sq] = log sum_j exp(scale q_i . k_j) over
     the keys row i sees, o = exp(s - lse) v."""
-    ct = _train_dtype(q)
+    ct = _ref_dtype(q)
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     qf, kf, vf = q.to(ct), k.to(ct), v.to(ct)
     s = _train_scores(qf, kf, causal, scale)
@@ -144,7 +148,7 @@ def sdpa_bwd_ref(q, k, v, o, lse, do, causal: bool = False, scale: float | None 
     formulas the kernel implements (no autograd): P = exp(s - lse),
     dV = P^T dO, dP = dO V^T, delta = rowsum(dO . O), dS = scale P (dP - delta),
     dQ = dS K, dK = dS^T Q; the heads of a group sum into their K / V head."""
-    ct = _train_dtype(q)
+    ct = _ref_dtype(q)
     B, Sq, H, D = q.shape
     Skv, Hkv = k.shape[1], k.shape[2]
     g = H // Hkv
@@ -161,16 +165,18 @@ def sdpa_bwd_ref(q, k, v, o, lse, do, causal: bool = False, scale: float | None 
 
 
 def rmsnorm_ref(x, weight, eps=1e-6):
-    xf = x.float()
+    ct = _ref_dtype(x)
+    xf = x.to(ct)
     y = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
-    return (weight.float() * y.to(x.dtype).float()).to(x.dtype)
+    return (weight.to(ct) * y.to(x.dtype).to(ct)).to(x.dtype)
 
 
 def linear_rms_ref(x, wg, bias=None, act=None, eps=1e-6):
-    xf = x.float()
-    y = (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)) @ wg.float().t()
+    ct = _ref_dtype(x)
+    xf = x.to(ct)
+    y = (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)) @ wg.to(ct).t()
     if bias is not None:
-        y = y + bias.float()
+        y = y + bias.to(ct)
     return _act(y, act).to(x.dtype)
 
 
@@ -561,6 +567,8 @@ def _sdpa_fwd(what: str, q, k, v, causal, scale, rope=None, out=None, lse: bool 
     _check_attn_shapes(what, q, k, v)
     B, Sq, H, D = q.shape
     Skv, Hkv = k.shape[1], k.shape[2]
+    if rope is not None and Sq > Skv:   # query i is rotated at position i + Skv - Sq: negative for the first rows
+        raise ValueError(f"native {what}: rope needs Sq <= Skv, got Sq {Sq}, Skv {Skv}")
     (qf, ldq, bsq), (kf, ldk, bsk), (vf, ldv, bsv) = (_rows(t, aligned=True) for t in (q, k, v))
     if out is None or out.dtype != torch.float32:
         o = torch.empty((B, Sq, H, D), dtype=torch.float32, device=q.device)
@@ -595,7 +603,8 @@ def sdpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False
     """softmax(scale q k^T [causal]) v: q [B, Sq, H, D], k / v [B, Skv, Hkv, D]
     (heads contiguous per token; any token / batch strides, e.g. slices of a
     fused QKV projection), D = 64 or 128, H % Hkv == 0.  ``rope`` = (cos, sin)
-    fp32 tables [Skv, D]: q and k are rotated first (inside the kernels).
+    fp32 tables [Skv, D]: q (row i at position i + Skv - Sq, so Sq <= Skv) and
+    k are rotated first (inside the kernels).
     ``out``: the tensor to fill (a non-fp32 one by copy)."""
     if not q.is_cuda:
         return sdpa_ref(q, k, v, causal, scale, rope)

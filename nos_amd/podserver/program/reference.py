@@ -137,17 +137,18 @@ def kv_write_ref(cache, x, pos):
 
 def sdpa_cache_ref(q, kc, vc, pos, scale=None):
     """Query i of sequence b at position pos[b] + i attends the cached keys
-    0 .. min(pos[b] + i, L - 1) (fp32 math; grouped-query K / V heads)."""
+    0 .. min(pos[b] + i, L - 1) (fp32 math, fp64 for an fp64 q; grouped-query K / V heads)."""
     import math
 
     import torch
 
     B, Sq, H, D = q.shape
     L, Hkv = kc.shape[1], kc.shape[2]
-    kf = kc.float().repeat_interleave(H // Hkv, dim=2)
-    vf = vc.float().repeat_interleave(H // Hkv, dim=2)
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32   # an fp64 reference stays fp64
+    kf = kc.to(ct).repeat_interleave(H // Hkv, dim=2)
+    vf = vc.to(ct).repeat_interleave(H // Hkv, dim=2)
     sc = scale if scale is not None else 1.0 / math.sqrt(D)
-    s = torch.einsum("bqhd,bkhd->bhqk", q.float(), kf) * sc
+    s = torch.einsum("bqhd,bkhd->bhqk", q.to(ct), kf) * sc
     qpos = pos.to(torch.long).view(B, 1) + torch.arange(Sq).view(1, Sq)            # [B, Sq]
     keep = torch.arange(L).view(1, 1, L) <= qpos.clamp(max=L - 1).view(B, Sq, 1)    # [B, Sq, L]
     s = s.masked_fill(~keep[:, None], float("-inf"))

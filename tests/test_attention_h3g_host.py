@@ -63,6 +63,7 @@ DEFECTS = [
     (ALL, "workspace one byte short", dict(ws_bytes=-1)),
     (FWDS, "cos table without sin", dict(rope_cos=_p(11), rope_bound=2.0)),
     (FWDS, "tables with rope_bound = 0", dict(rope_cos=_p(11), rope_sin=_p(12), rope_bound=0.0)),
+    (FWDS, "rope with Sq > Skv", dict(rope_cos=_p(11), rope_sin=_p(12), rope_bound=2.0, Sq=S + 1, ws_bytes=BIG)),
     (TRAIN, "lse null", dict(lse=None)),
     (TRAIN, "lse not 4-byte aligned", dict(lse=_p(10) + 2)),
     (FWDS, "q null [new]", dict(q=None)),
