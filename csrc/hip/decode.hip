@@ -21,6 +21,8 @@
 //    nos_attn_decode_combine merges the splits (log-sum-exp);
 //  * nos_pos_update -- pos += n / pos = n;
 //  * nos_argmax -- greedy next tokens, one wave per row;
+//  * nos_sample -- sampled next tokens (temperature, top-k, top-p, seed read
+//    from device memory; Gumbel-max over Philox keyed on the position);
 //  * nos_gemv -- y = act(r x W^T + b) + R for M <= 8 rows (a decode step's
 //    every GEMM): weight-streaming, each wave two output columns, lanes over
 //    K with 16-byte weight loads, x rows in LDS (optionally RMS-normalised in
@@ -485,6 +487,297 @@ __global__ __launch_bounds__(NT) void argmax_kernel(const void* __restrict__ x, 
   }
 }
 
+// ------------------------------------------------------------------ sampling (temperature, top-k, top-p)
+// u32 key of a logit, ordered as the floats are (-0 and +0, equal as floats, share a key)
+__device__ __forceinline__ unsigned ord_key(float v) {
+  if (v == 0.f) v = 0.f;
+  const unsigned u = __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned h0 = __umulhi(0xD2511F53u, c.x), l0 = 0xD2511F53u * c.x;
+    const unsigned h1 = __umulhi(0xCD9E8D57u, c.z), l1 = 0xCD9E8D57u * c.z;
+    c = uint4{h1 ^ c.y ^ k0, l1, h0 ^ c.w ^ k1, l0};
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return c;
+}
+
+// One token per row drawn from softmax(x / T) restricted by top-k, then top-p
+// (ctl = [T bits, top_k, top_p bits, seed], read here: one captured graph serves
+// every request; all zero = greedy, exactly argmax_kernel's result).  One
+// workgroup per row; the first pass copies the row (as fp32) into LDS where it
+// fits (lds_row: 128 KB at vocab 32000 of the CU's 160 KB) and the later passes
+// read it there (top-k with top-p makes 13 of them); a longer row, or any row
+// where a workgroup's LDS limit is 64 KB, is re-read from L2:
+//  1. the row maximum m and its index (am_better's rules);
+//  2. top-k: the k-th largest logit by radix select on ord_key, 8-bit digits, an
+//     integer LDS histogram per digit (ties at the k-th value all stay);
+//  3. top-p: the smallest key whose mass of larger kept logits is < p Z, by a
+//     descent over the same keys, 4-bit digits: 16 register sums per thread,
+//     reduced by wave shuffles and then over the waves in wave order (no float
+//     atomics: the sums, and so the token, repeat bit for bit);
+//  4. the draw, Gumbel-max: score = (x - m) / T - log(-log(u)), u from word i & 3
+//     of Philox4x32-10 at key (seed, row), counter (i >> 2, pos[row], 0, 0) -- the
+//     position BEFORE this launch's pos_n advance -- the largest score wins, the
+//     lower index on a tie.
+template <int NT>
+__global__ __launch_bounds__(NT) void sample_kernel(const void* __restrict__ x, int bf, int rows, int L, int ldx,
+                                                    int* __restrict__ out, int* __restrict__ pos, int pos_n,
+                                                    const int* __restrict__ ctl, int lds_row) {
+  constexpr int NW = NT / 64;
+  static_assert(NT >= 256, "the histogram scan takes 256 threads");
+  extern __shared__ float rowc[];   // lds_row: the row, L floats
+  __shared__ float sv[NW];
+  __shared__ int si[NW];
+  __shared__ float s_m;
+  __shared__ int s_i, s_p;
+  __shared__ int hist[256];
+  __shared__ int wsum[4];
+  __shared__ int s_d, s_k;
+  __shared__ float part[NW][16];
+  __shared__ float tot[16];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const long long base = (long long)row * ldx;
+  const float T = __int_as_float(ctl[0]), top_p = __int_as_float(ctl[2]);
+  const int top_k = ctl[1];
+  const unsigned seed = (unsigned)ctl[3];
+  lds_row = lds_row && T > 0.f;   // greedy makes one pass
+  // every lane of a wave makes the same trips (f sees in = j < L): f may vote across the wave
+  // 8 loads in flight per thread
+  auto walk = [&](auto&& f, bool first = false) {
+    for (int b = wid * 64; b < L; b += 8 * NT) {
+      float v[8];
+      if (lds_row && !first) {   // the choice outside the batch: its loads issue together
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int j = b + u * NT + lane;
+          const float r = rowc[j < L ? j : L - 1];
+          v[u] = j < L ? r : -INFINITY;
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int j = b + u * NT + lane;
+          v[u] = j < L ? ldf(x, base + j, bf) : -INFINITY;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int j = b + u * NT + lane;
+        f(v[u], j, j < L);
+      }
+    }
+  };
+  // (value, index) of the workgroup's best under `better`, in thread 0
+  auto best_of = [&](float& best, int& bi, auto&& better) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (better(ob, oi, best, bi)) {
+        best = ob;
+        bi = oi;
+      }
+    }
+    if (lane == 0) {
+      sv[wid] = best;
+      si[wid] = bi;
+    }
+    __syncthreads();
+    if (tid == 0)
+      for (int w = 1; w < NW; ++w)
+        if (better(sv[w], si[w], best, bi)) {
+          best = sv[w];
+          bi = si[w];
+        }
+  };
+
+  // 1. the maximum
+  float best = -INFINITY;
+  int bi = INT_MAX;
+  walk([&](float v, int j, bool in) {
+    if (in && lds_row) rowc[j] = v;
+    if (in && am_better(v, j, best, bi)) {
+      best = v;
+      bi = j;
+    }
+  }, true);
+  best_of(best, bi, [](float bv, int bj, float av, int aj) { return am_better(bv, bj, av, aj); });
+  if (tid == 0) {
+    s_m = best;
+    s_i = bi >= L ? 0 : bi;                  // an all -inf row: index 0
+    s_p = pos != nullptr ? pos[row] : 0;     // the counter before this launch's advance (written below, by this thread)
+  }
+  __syncthreads();
+  const float m = s_m;
+  const int p0 = s_p;
+  if (!(T > 0.f) || !(fabsf(m) < INFINITY)) {   // greedy; a NaN or infinite maximum
+    if (tid == 0) {
+      out[row] = s_i;
+      if (pos != nullptr) pos[row] = p0 + pos_n;
+    }
+    return;
+  }
+
+  // 2. top-k: kept iff ord_key >= thr
+  unsigned thr = 0;
+  if (top_k > 0 && top_k < L) {
+    unsigned prefix = 0;
+    int kr = top_k;   // the kr-th largest of the keys under the prefix
+    for (int r = 0; r < 4; ++r) {
+      const int shift = 24 - 8 * r;
+      if (tid < 256) hist[tid] = 0;
+      __syncthreads();
+      walk([&](float v, int j, bool in) {
+        const unsigned key = ord_key(v);
+        const int d = (int)((key >> shift) & 255u);
+        if (r == 0) {
+          // logits share a few top bytes: one add per distinct digit of the wave, not 64
+          // serialised ones on the same counter (still the dearest pass: docs/kernels.md)
+          unsigned long long act = __ballot(in);
+          while (act) {
+            const int ld = __ffsll((long long)act) - 1;
+            const int dl = __builtin_amdgcn_readlane(d, ld);   // ld is wave-uniform: no trip through LDS
+            const unsigned long long same = __ballot(in && d == dl);
+            if (lane == ld) atomicAdd(&hist[dl], __popcll(same));
+            act &= ~same;
+          }
+        } else if (in && (key >> (shift + 8)) == prefix) {
+          atomicAdd(&hist[d], 1);
+        }
+      });
+      __syncthreads();
+      // s = keys of digit >= tid: thread tid, whose digit the kr-th largest has, says so
+      int h = 0, s = 0;
+      if (tid < 256) {
+        h = s = hist[tid];
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const int t = __shfl_down(s, o, 64);
+          if (lane + o < 64) s += t;
+        }
+        if (lane == 0) wsum[wid] = s;
+      }
+      __syncthreads();
+      if (tid < 256) {
+        for (int w = wid + 1; w < 4; ++w) s += wsum[w];
+        if (s - h < kr && s >= kr) {
+          s_d = tid;
+          s_k = kr - (s - h);
+        }
+      }
+      __syncthreads();
+      prefix = (prefix << 8) | (unsigned)s_d;
+      kr = s_k;
+    }
+    thr = prefix;
+  }
+
+  // 3. top-p over the top-k set: kept iff ord_key >= the smallest key t with mass(key > t) < p Z
+  if (top_p > 0.f && top_p < 1.f) {
+    unsigned prefix = 0;
+    float above = 0.f, pz = 0.f;   // mass of the keys over the prefix's range
+    for (int r = 0; r < 8; ++r) {
+      const int shift = 28 - 4 * r;
+      float a[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) a[q] = 0.f;
+      walk([&](float v, int j, bool in) {
+        const unsigned key = ord_key(v);
+        if (in && key >= thr && (r == 0 || (key >> (shift + 4)) == prefix)) {
+          const float w = expf((v - m) / T);
+          const int d = (int)((key >> shift) & 15u);
+#pragma unroll
+          for (int q = 0; q < 16; ++q) a[q] += d == q ? w : 0.f;
+        }
+      });
+      // lanes trade halves of the 16 sums four times (8 + 4 + 2 + 1 shuffles): each then holds
+      // one digit's sum over its 16 lanes; two more steps give the wave's
+#pragma unroll
+      for (int st = 0; st < 4; ++st) {
+        const int w = 8 >> st;
+        const bool hi = (lane >> st) & 1;
+#pragma unroll
+        for (int q = 0; q < w; ++q) {
+          const float send = hi ? a[q] : a[q + w];
+          const float keep = hi ? a[q + w] : a[q];
+          a[q] = keep + __shfl_xor(send, 1 << st, 64);
+        }
+      }
+      a[0] += __shfl_xor(a[0], 16, 64);
+      a[0] += __shfl_xor(a[0], 32, 64);
+      if (lane < 16) part[wid][((lane & 1) << 3) | ((lane & 2) << 1) | ((lane & 4) >> 1) | ((lane & 8) >> 3)] = a[0];
+      __syncthreads();
+      if (tid < 16) {
+        float t = 0.f;
+        for (int w = 0; w < NW; ++w) t += part[w][tid];   // in wave order
+        tot[tid] = t;
+      }
+      __syncthreads();
+      float t[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) t[q] = tot[q];
+      if (r == 0) {
+        float Z = 0.f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) Z += t[q];
+        pz = top_p * Z;
+      }
+      // the lowest digit whose keys still have less than p Z above them (the top one always has)
+      int d0 = 15;
+      float g = above, g0 = above;
+      bool on = true;
+#pragma unroll
+      for (int d = 15; d >= 0; --d) {
+        on = on && g < pz;
+        d0 = on ? d : d0;
+        g0 = on ? g : g0;
+        g += t[d];
+      }
+      prefix = (prefix << 4) | (unsigned)d0;
+      above = g0;
+    }
+    thr = prefix > thr ? prefix : thr;
+  }
+
+  // 4. the draw: 4 consecutive candidates share one Philox call
+  best = -INFINITY;
+  bi = INT_MAX;
+  for (int g = tid; g < (L + 3) / 4; g += NT) {
+    float v[4];
+    bool keep[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = 4 * g + u;
+      v[u] = j >= L ? -INFINITY : lds_row ? rowc[j] : ldf(x, base + j, bf);
+      keep[u] = j < L && ord_key(v[u]) >= thr;
+    }
+    if (!(keep[0] || keep[1] || keep[2] || keep[3])) continue;
+    const uint4 rnd = philox4x32_10(uint4{(unsigned)g, (unsigned)p0, 0u, 0u}, seed, (unsigned)row);
+    const unsigned word[4] = {rnd.x, rnd.y, rnd.z, rnd.w};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float un = ((float)(word[u] >> 9) + 0.5f) * 1.1920928955078125e-07f;   // 2^-23: exact, in (0, 1)
+      const float sc = (v[u] - m) / T - logf(-logf(un));
+      const int j = 4 * g + u;
+      if (keep[u] && (sc > best || (sc == best && j < bi))) {
+        best = sc;
+        bi = j;
+      }
+    }
+  }
+  best_of(best, bi, [](float bv, int bj, float av, int aj) { return bv > av || (bv == av && bj < aj); });
+  if (tid == 0) {
+    out[row] = bi >= L ? s_i : bi;
+    if (pos != nullptr) pos[row] = p0 + pos_n;
+  }
+}
+
 // ------------------------------------------------------------------ GEMV (M <= 8)
 // x given as the decode attention's split partials (ws != null): x row m = sequence m's
 // single query token, x[m][h * D + d] combined from the NS splits of (m, h / G) exactly as
@@ -773,6 +1066,42 @@ NOS_API int nos_argmax(const void* x, int bf16, int rows, int L, int ldx, int* o
   else
     hipLaunchKernelGGL(argmax_kernel<256>, dim3((unsigned)rows), dim3(256), 0, stream, x, bf16, rows, L, ldx, out,
                        pos, pos_n);
+  return (int)hipGetLastError();
+}
+
+// one token per row drawn under ctl = [temperature fp32 bits, top_k, top_p fp32 bits, seed]
+// (4 i32 in device memory; all zero: nos_argmax's result); pos as in nos_argmax, and the
+// draw's Philox counter is pos[row] before the advance (0 without pos)
+static int sample_lds_limit() {
+  static int lds_limit = -1;
+  if (lds_limit < 0) {
+    int dev = 0, v = 0;
+    lds_limit = hipGetDevice(&dev) == hipSuccess &&
+                        hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess
+                    ? v
+                    : 0;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_kernel<1024>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit > 4096 ? lds_limit - 4096 : 0);
+    (void)hipGetLastError();
+  }
+  return lds_limit;
+}
+
+// whether nos_sample keeps a row of L logits in LDS (beside the kernel's 4 KB of static LDS)
+NOS_API int nos_sample_row_in_lds(int L) { return (long long)L * 4 + 4096 <= sample_lds_limit(); }
+
+NOS_API int nos_sample(const void* x, int bf16, int rows, int L, int ldx, int* out, int* pos, int pos_n,
+                       const int* ctl, hipStream_t stream) {
+  if (!x || !out || !ctl || rows <= 0 || L <= 0 || ldx < L || (bf16 != 0 && bf16 != 1) || pos_n < 0)
+    return (int)hipErrorInvalidValue;
+  const int lds_row = nos_sample_row_in_lds(L);
+  const size_t lds = lds_row ? (size_t)L * 4 : 0;
+  if (L >= 4096)
+    hipLaunchKernelGGL(sample_kernel<1024>, dim3((unsigned)rows), dim3(1024), lds, stream, x, bf16, rows, L, ldx, out,
+                       pos, pos_n, ctl, lds_row);
+  else
+    hipLaunchKernelGGL(sample_kernel<256>, dim3((unsigned)rows), dim3(256), lds, stream, x, bf16, rows, L, ldx, out,
+                       pos, pos_n, ctl, lds_row);
   return (int)hipGetLastError();
 }
 

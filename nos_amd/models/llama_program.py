@@ -108,7 +108,7 @@ def llama_program(model, seq: int, batch: int = 1, dtype: str = "fp32",
 
 
 def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, dtype: str = "fp32",
-                          extend: tuple[int, ...] = ()) -> tuple[list[dict], bytes]:
+                          extend: tuple[int, ...] = (), sampling: bool = False) -> tuple[list[dict], bytes]:
     """A STATEFUL generation tenant: ``[prefill, decode, *extends]`` programs
     over one weight payload and one state -- per layer a K and a V cache
     ``[batch, max_len, kv_heads, head_dim]`` plus the position counter
@@ -128,7 +128,15 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     Every program outputs the last token's logits ``[batch, 1, vocab]`` and
     the greedy next ids ``[batch, 1]`` (i32, ``argmax``), so a client's
     generation loop sends back one id per step.  The caches' bytes count
-    against the slice at registration; a replay never allocates state."""
+    against the slice at registration; a replay never allocates state.
+
+    ``sampling``: the programs also declare the control state ``sampling``
+    (i32 [4], filled by the server from each request's ``"sampling"`` field)
+    and end in ``sample`` instead of ``argmax``: the next ids are drawn under
+    the request's temperature / top-k / top-p / seed, keyed on the position
+    before the step's advance (the prefill draws at counter 0, the decode
+    steps at ``prompt_len``, ``prompt_len`` + 1, ...); a request without
+    sampling parameters stays greedy."""
     if not 0 < prompt_len <= max_len:
         raise ValueError(f"prompt_len must be in [1, {max_len}]")
     cfg = model.config
@@ -149,6 +157,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
         P = lambda k: b.param(k, sd[k], dtype)  # noqa: E731
         rc, rs = b.param("rope.cos", cos, "fp32"), b.param("rope.sin", sin, "fp32")
         b.state("pos", [batch], "i32")
+        ctl = b.state("sampling", [4], "i32") if sampling else None
         caches = [(b.state(f"kc{i}", [batch, max_len, nkv, hd], cache_dt),
                    b.state(f"vc{i}", [batch, max_len, nkv, hd], cache_dt)) for i in range(cfg.num_hidden_layers)]
         p = b.op("pos_set", "pos", value=0) if reset else "pos"
@@ -172,7 +181,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
             h = b.op("slice", h, dim=1, start=seq - 1, end=seq)
         h = b.op("rmsnorm", h, P("model.norm.weight"), eps=eps)
         logits = b.op("linear", h, P(head), out="logits")
-        nxt = b.op("argmax", logits, out="next_ids")
+        nxt = b.op("sample", logits, ctl, p, out="next_ids") if sampling else b.op("argmax", logits, out="next_ids")
         b.op("pos_add", p, n=seq)
         prog, w = b.build([logits, nxt])
         progs.append(prog)

@@ -111,6 +111,8 @@ _SIGS = {
                         c_void_p, c_void_p, c_int, c_int, c_ll, c_int, c_ll, c_int, c_void_p, c_ll, c_int, c_void_p],
     "nos_pos_update": [c_void_p, c_int, c_int, c_int, c_void_p],
     "nos_argmax": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    "nos_sample_row_in_lds": [c_int],
+    "nos_sample": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "nos_gemv": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                  c_int, c_int, c_int, c_float, c_void_p],
     "nos_gemv_partials": [c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,

@@ -27,6 +27,7 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -846,8 +847,137 @@ def argmax(x: torch.Tensor, pos: torch.Tensor | None = None, pos_n: int = 0) -> 
     return out
 
 
+# ------------------------------------------------------------------ sampling
+def philox4x32(counter, key) -> np.ndarray:
+    """Philox4x32-10 (Salmon et al., Random123): ``counter`` [..., 4] and
+    ``key`` [..., 2] as uint32 (broadcast against each other) -> uint32 [..., 4]."""
+    c = np.asarray(counter, dtype=np.uint64)
+    k = np.asarray(key, dtype=np.uint64)
+    c0, c1, c2, c3 = (c[..., i] for i in range(4))
+    k0, k1 = k[..., 0], k[..., 1]
+    m32 = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return np.stack(np.broadcast_arrays(c0, c1, c2, c3), axis=-1).astype(np.uint32)
+
+
+def sampling_ctl(temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> np.ndarray:
+    """The four i32 control words :func:`sample` reads from device memory:
+    ``[temperature as fp32 bits, top_k, top_p as fp32 bits, seed]``.
+    Temperature 0 is greedy whatever the rest (the defaults pack to four
+    zeros but for top_p's 1.0); top_k 0 and top_p 1 switch those filters off."""
+    def number(v, what, integer=False):
+        ok = isinstance(v, int) if integer else isinstance(v, (int, float))
+        if not ok or isinstance(v, bool):
+            raise ValueError(f"sampling: {what} must be {'an int' if integer else 'a number'}, got {v!r}")
+        return v
+
+    t, p = float(number(temperature, "temperature")), float(number(top_p, "top_p"))
+    k, s = number(top_k, "top_k", True), number(seed, "seed", True)
+    if not math.isfinite(t) or t < 0:
+        raise ValueError(f"sampling: temperature must be finite and >= 0, got {temperature!r}")
+    if k < 0 or k >= 1 << 31:
+        raise ValueError(f"sampling: top_k must be in [0, 2^31), got {top_k!r}")
+    if not 0 < p <= 1:
+        raise ValueError(f"sampling: top_p must be in (0, 1], got {top_p!r}")
+    if not 0 <= s < 1 << 31:
+        raise ValueError(f"sampling: seed must be in [0, 2^31), got {seed!r}")
+    words = np.array([t, p], dtype=np.float32).view(np.int32)
+    return np.array([words[0], k, words[1], s], dtype=np.int32)
+
+
+def sample_row_ref(x: np.ndarray, ctl, row: int = 0, pos: int = 0) -> dict:
+    """One row of :func:`sample` on the host, scores and masses in fp64 --
+    the reference the kernel is compared with, and its contract:
+
+    * greedy (``token`` = the first index of the maximum, NaN winning, 0 for
+      an all ``-inf`` row) when the temperature is <= 0 or the maximum ``m``
+      is NaN or infinite;
+    * else ``z = (x - m) / T``, ``w = exp(z)``; top-k (0 < k < L) keeps
+      ``x >= `` the k-th largest logit, ties and all; top-p (0 < p < 1), after
+      it, keeps token i iff the w-mass of kept tokens with a LARGER logit is
+      ``< p Z`` (Z: the kept mass), so equal logits stay or go together;
+    * the draw is Gumbel-max: ``u = ((word >> 9) + 0.5) 2^-23`` from word
+      ``i & 3`` of Philox4x32-10 at key ``(seed, row)``, counter
+      ``(i >> 2, pos, 0, 0)``; the largest ``z - log(-log(u))`` of the kept
+      tokens wins, the lower index on a tie.
+
+    Returns ``token`` and, for the tests' exclusion rules, ``keep`` (bool
+    [L]), ``gap`` (best minus second-best score; inf when greedy) and
+    ``p_margin`` (the least ``|mass above / Z - p|`` over the top-k set; inf
+    without top-p)."""
+    x = np.asarray(x, dtype=np.float32).astype(np.float64)
+    L = x.shape[0]
+    c = np.asarray(ctl, dtype=np.int32).reshape(4)
+    T, p = (float(v) for v in c[[0, 2]].view(np.float32))
+    k, seed = int(c[1]), int(c[3])
+    nan = np.isnan(x)
+    idx = int(np.argmax(nan)) if nan.any() else int(np.argmax(x))
+    m = x[idx]
+    res = {"token": idx, "keep": None, "gap": math.inf, "p_margin": math.inf}
+    if not T > 0 or not np.isfinite(m):
+        return res
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        z = (x - m) / T
+        w = np.exp(z)
+        keep = np.ones(L, dtype=bool)
+        if 0 < k < L:
+            keep = x >= np.partition(x, L - k)[L - k]
+        if 0 < p < 1:
+            vals, inv = np.unique(x[keep], return_inverse=True)            # ascending
+            mass = np.bincount(inv, weights=w[keep], minlength=len(vals))
+            above = np.concatenate([np.cumsum(mass[::-1])[::-1][1:], [0.0]])   # mass of the larger logits
+            Z = mass[::-1].sum()
+            res["p_margin"] = float(np.abs(above / Z - p).min())
+            kept = np.zeros(L, dtype=bool)
+            kept[np.flatnonzero(keep)] = (above < p * Z)[inv]
+            keep = kept
+        i = np.arange(L, dtype=np.uint32)
+        words = philox4x32(np.stack([i[::4] >> 2, np.full_like(i[::4], np.uint32(pos & 0xFFFFFFFF)),
+                                     np.zeros_like(i[::4]), np.zeros_like(i[::4])], axis=-1),
+                           np.array([seed & 0xFFFFFFFF, row & 0xFFFFFFFF], dtype=np.uint32)).reshape(-1)[:L]
+        u = ((words >> np.uint32(9)).astype(np.float64) + 0.5) * 2.0 ** -23
+        score = np.where(keep, z - np.log(-np.log(u)), -np.inf)
+    tok = int(np.argmax(score))
+    rest = np.delete(score, tok)
+    res.update(token=tok, keep=keep, gap=float(score[tok] - rest.max()) if L > 1 else math.inf)
+    return res
+
+
+def sample(x: torch.Tensor, ctl: torch.Tensor, pos: torch.Tensor | None = None, pos_n: int = 0) -> torch.Tensor:
+    """One token per row of logits (the last dim), i32: drawn from
+    ``softmax(x / temperature)`` restricted by top-k, then top-p, as the
+    control words ``ctl`` (:func:`sampling_ctl`: 4 i32 on x's device, read
+    when the kernel runs) say; all zero: exactly :func:`argmax`.  The
+    contract is :func:`sample_row_ref`'s, which CPU tensors run.  ``pos``
+    (i32, one counter per row): its value before this call keys the draw
+    (0 without it), and it is advanced by ``pos_n`` in the same launch."""
+    L = x.shape[-1]
+    x2 = x.reshape(-1, L)
+    if (ctl.dtype != torch.int32 or ctl.numel() != 4 or not ctl.is_contiguous() or ctl.device != x.device):
+        raise ValueError("sample: ctl must be 4 contiguous i32 control words on x's device")
+    if pos is not None and (pos.numel() != x2.shape[0] or pos.dtype != torch.int32 or not pos.is_contiguous()):
+        raise ValueError(f"sample: pos needs one i32 counter per row ({x2.shape[0]})")
+    if not x.is_cuda:
+        xs, c = x2.float().numpy(), ctl.numpy()
+        ps = pos.reshape(-1).tolist() if pos is not None else [0] * x2.shape[0]
+        out = torch.tensor([sample_row_ref(xs[r], c, r, ps[r])["token"] for r in range(x2.shape[0])],
+                           dtype=torch.int32).reshape(x.shape[:-1])
+        if pos is not None:
+            pos.add_(pos_n)
+        return out
+    if x2.stride(-1) != 1:
+        x2 = x2.contiguous()
+    out = torch.empty(x.shape[:-1], dtype=torch.int32, device=x.device)
+    _lib.check(_lib.lib().nos_sample(x2.data_ptr(), _bf(x2), x2.shape[0], L, x2.stride(0), out.data_ptr(), _ptr(pos),
+                                     int(pos_n), ctl.data_ptr(), _stream()), "nos_sample")
+    return out
+
+
 GEMV_MAX_ROWS = 8
-EPI_SILU = 64  # csrc/hip/epilogue.h; decode.hip's GEMV: SiLU epilogue
+EPI_SILU = 64 # csrc/hip/epilogue.h; decode.hip's GEMV: SiLU epilogue
 EPI_GLU = 256  # decode.hip's GEMV: W = [gate; up], y = silu(gate) * up
 
 
@@ -912,7 +1042,8 @@ def set_attention_h3g_kvsplit(n: int) -> None:
     _lib.check(_lib.lib().nos_attn_h3g_set_kvsplit(int(n)), "nos_attn_h3g_set_kvsplit")
 
 
-__all__ = ["glu", "kv_write", "rotary_at", "sdpa_cache", "pos_update", "argmax", "gemv", "gemv_ok", "gemv_partials",
+__all__ = ["glu", "kv_write", "rotary_at", "sdpa_cache", "pos_update", "argmax", "sample", "sample_row_ref",
+           "sampling_ctl", "philox4x32", "gemv", "gemv_ok", "gemv_partials",
            "DecodePartials", "conv2d", "matmul", "sdpa", "linear_rms", "embedding", "rmsnorm", "softmax", "rotary", "conv2d_ref",
            "sdpa_ref", "rope_ref", "rmsnorm_ref", "linear_rms_ref", "set_attention_h3g_kvsplit", "EPI_BIAS_ROW",
            "sdpa_lse", "sdpa_bwd", "sdpa_lse_ref", "sdpa_bwd_ref", "sdpa_bwd_workspace_bytes"]

@@ -28,6 +28,9 @@ from ..api.constants import ENV_MEMORY_LIMIT_GB, ENV_POD_CU_MASK, ENV_POD_SERVER
 from . import protocol as P
 
 
+_GREEDY = {"temperature": 0.0, "top_k": 0, "top_p": 1.0, "seed": 0}   # the sampling defaults: not sent
+
+
 class PodServerError(RuntimeError):
     pass
 
@@ -149,13 +152,19 @@ class PodClient:
                 time.sleep(0.2)
         raise PodServerGone(f"pod server did not come back within {self.reconnect_s} s: {last}")
 
-    def infer(self, x: np.ndarray | None = None, outputs: bool | list = False) -> tuple[list[np.ndarray], dict]:
+    def infer(self, x: np.ndarray | None = None, outputs: bool | list = False,
+              sampling: dict | None = None) -> tuple[list[np.ndarray], dict]:
         """One inference on the pod's model; ``x`` replaces the resident input
         (one of the registered input shapes; without ``x`` the primary
         shape's resident input runs).  ``outputs``: return every output
         (True), none, or those of the listed indices.  A stateful tenant's
-        reply carries its counters (``rep["state"]``, e.g. the position)."""
+        reply carries its counters (``rep["state"]``, e.g. the position).
+        ``sampling``: ``{"temperature", "top_k", "top_p", "seed"}`` (any
+        subset) for a tenant whose programs end in ``sample``; without it the
+        request is greedy."""
         req = {"op": "infer", "outputs": outputs}
+        if sampling:
+            req["sampling"] = dict(sampling)
         if x is None:
             payload = b""
         else:
@@ -178,22 +187,31 @@ class PodClient:
         return self._call({"op": "reset"})[0]
 
     def generate(self, prompt: np.ndarray, max_new_tokens: int, next_output: int = -1,
-                 server_loop: bool = True) -> tuple[np.ndarray, dict]:
-        """Greedy generation on a stateful decoder tenant
+                 server_loop: bool = True, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
+                 seed: int = 0) -> tuple[np.ndarray, dict]:
+        """Generation on a stateful decoder tenant
         (models/llama_program.llama_decode_programs): the prompt ids [B, P]
         go to the prefill variant, then the decode variant runs once per new
         token, fed the program's next-ids output (``next_output``).
         ``server_loop``: the decode steps run as ONE ``generate`` request --
         the server replays the decode graph back to back, feeding the ids on
         the device, and returns every token at the end (no host round trip
-        per token); otherwise one [B, 1] request per token.  Returns (ids [B,
+        per token); otherwise one [B, 1] request per token.  ``temperature``
+        (0: greedy), ``top_k`` (0: off), ``top_p`` (1: off) and ``seed`` go
+        with every request of the generation when they differ from these
+        defaults, for a tenant registered with sampling programs
+        (``llama_decode_programs(..., sampling=True)``): the ids are then
+        drawn on the device, the same ones on either path and on every
+        repeat of the sequence with the same seed.  Returns (ids [B,
         max_new_tokens], timings: the prefill's round trip, every decode
         step's (server loop: the loop's time / steps), the server's final
         counters)."""
         prompt = np.asarray(prompt)
         B = prompt.shape[0]
+        given = {"temperature": temperature, "top_k": top_k, "top_p": top_p, "seed": seed}
+        sampling = {k: v for k, v in given.items() if v != _GREEDY[k]}   # older servers keep serving greedy clients
         t0 = time.monotonic()
-        outs, rep = self.infer(prompt, outputs=[next_output])
+        outs, rep = self.infer(prompt, outputs=[next_output], sampling=sampling)
         t1 = time.monotonic()
         tok = outs[0].reshape(B, -1)[:, -1].astype(np.int32)
         toks, steps = [tok], []
@@ -202,6 +220,8 @@ class PodClient:
             wire = _wire(tok.reshape(B, 1), self.input_dtype, "input")
             req = {"op": "generate", "steps": n, "output": next_output, "shape": [B, 1],
                    "dtype": "i32" if wire.dtype == np.int32 else "f32"}
+            if sampling:
+                req["sampling"] = sampling
             s0 = time.monotonic()
             rep, data = self._call(req, wire.tobytes())
             dt = time.monotonic() - s0
@@ -211,7 +231,7 @@ class PodClient:
         else:
             for _ in range(n):
                 s0 = time.monotonic()
-                outs, rep = self.infer(tok.reshape(B, 1), outputs=[next_output])
+                outs, rep = self.infer(tok.reshape(B, 1), outputs=[next_output], sampling=sampling)
                 steps.append(time.monotonic() - s0)
                 tok = outs[0].reshape(B, -1)[:, -1].astype(np.int32)
                 toks.append(tok)

@@ -75,7 +75,8 @@ class Lowered:
                 steps = self._fuse_kv_write_attention(steps)
             if os.environ.get("NOS_AMD_FOLD_DECODE_COMBINE", "0") == "1":   # opt-in (A/B: slower alone)
                 self._fold_decode_combines(steps)
-            steps = self._fuse_argmax_pos(steps)
+            if "argmax_pos" not in skip:
+                steps = self._fuse_argmax_pos(steps)
             steps = self._fuse_gemv_glu(steps)
             if "combine_gemv" not in skip:
                 steps = self._fold_combine_into_gemv(steps)
@@ -1111,28 +1112,32 @@ class Lowered:
         return [t for t in steps if id(t) not in drop]
 
     def _fuse_argmax_pos(self, steps: list[_Step]) -> list[_Step]:
-        """GPU: a step's closing ``pos_add`` folds into the ``argmax`` right
-        before it when argmax has one row per counter and nothing between
-        them reads the counter (the decode step's last two launches become
-        one; argmax reads no position)."""
+        """GPU: a step's closing ``pos_add`` folds into the ``argmax`` or
+        ``sample`` right before it when that has one row per counter and
+        nothing between them reads the counter (the decode step's last two
+        launches become one; argmax reads no position, and ``sample`` reads
+        the counter the ``pos_add`` advances before the fold writes it)."""
         if not self.gpu:
             return steps
+        self.stats["pos_add_into_argmax"] = 0
+        if any(s.kind == "sample" for s in steps):
+            self.stats["pos_add_into_sample"] = 0
         uses = self._consumers(steps, self.outputs)
         for k, p in enumerate(steps):
             if p.kind != "pos_add" or k == 0:
                 continue
             a = steps[k - 1]
-            shp = tuple(self._shape(a.inputs[0])) if a.kind == "argmax" else ()
+            shp = tuple(self._shape(a.inputs[0])) if a.kind in ("argmax", "sample") else ()
             pshape = tuple(self._shape(p.inputs[0]))
-            if (a.kind != "argmax" or a.attrs.get("pos_out") or len(pshape) != 1 or not shp
+            if (not shp or a.attrs.get("pos_out") or len(pshape) != 1
                     or math.prod(shp[:-1]) != pshape[0] or uses.get(p.output, 0) != 0
-                    or self._dtype(p.inputs[0]) != "i32"):
+                    or self._dtype(p.inputs[0]) != "i32" or (a.kind == "sample" and a.inputs[2] != p.inputs[0])):
                 continue
-            a.inputs = a.inputs + [p.inputs[0]]
+            if a.kind == "argmax":
+                a.inputs = a.inputs + [p.inputs[0]]
             a.attrs = {**a.attrs, "pos_out": p.output, "pos_n": int(p.attrs["n"])}
-            self.stats["pos_add_into_argmax"] = 1
+            self.stats["pos_add_into_" + a.kind] = 1
             return steps[:k] + steps[k + 1:]
-        self.stats["pos_add_into_argmax"] = 0
         return steps
 
     def _prep_conv_weights(self, steps: list[_Step]) -> None:

@@ -143,6 +143,10 @@ class CompiledProgram(Lowered):
                 env[s.attrs["pos_out"]] = a[1]
             elif k == "argmax":
                 y = T.argmax(a[0])
+            elif k == "sample":   # pos_out: the step's pos_add folded in (the draw reads the counter first)
+                y = T.sample(a[0], a[1], pos=a[2], pos_n=int(s.attrs.get("pos_n", 0)))
+                if s.attrs.get("pos_out"):
+                    env[s.attrs["pos_out"]] = a[2]
             elif k == "cat_buffer":  # its GEMM part was written in place; the constant parts at build
                 y = self.aux[s.attrs["buf"]]
                 if env.pop(s.inputs[0] + "::lnp", None) is not None:

@@ -63,6 +63,7 @@ class Program:
     payload: bytes | memoryview = b""
     state: dict[str, Value] = field(default_factory=dict)        # persistent buffers (K / V caches, positions)
     state_root: dict[str, str] = field(default_factory=dict)     # a state's in-place versions -> the state
+    sampling_state: str | None = None    # the i32 [4] state its ``sample`` nodes read (the server fills it per request)
 
     # ------------------------------------------------------------ accounting
     @property

@@ -115,7 +115,7 @@ OPS = ("linear", "layernorm", "attention", *BINARY, *UNARY, "cat", "slice", "res
 # tenant's requests (a K / V cache, a position counter).  STATE_WRITERS update
 # their first input IN PLACE and return its new version (the validator makes
 # the old version dead from then on, so in-place equals SSA semantics)
-STATE_OPS = ("kv_write", "sdpa_cache", "rotary_at", "pos_add", "pos_set", "argmax")
+STATE_OPS = ("kv_write", "sdpa_cache", "rotary_at", "pos_add", "pos_set", "argmax", "sample")
 STATE_WRITERS = ("kv_write", "pos_add", "pos_set")
 STATE_DTYPES = ("fp32", "bf16", "i32")
 MAX_STATE = 1024
@@ -124,7 +124,7 @@ NEVER_FOLD = ("attention", "sdpa", *STATE_OPS)
 # step kinds that run a gfx950 kernel of libnos_hip.so (CompiledProgram.stats["kernels"])
 NATIVE_KINDS = ("linear", "linear_ln", "linear_rms", "ln_qkv_attention", "attention", "layernorm", "conv2d", "matmul",
                 "softmax", "embedding", "rmsnorm", "rotary", "sdpa", "patches", "unary", "kv_write", "sdpa_cache",
-                "rotary_at", "pos_add", "pos_set", "argmax", "glu")
+                "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu")
 GEMM_OPS = ("linear", "conv2d")
 
 

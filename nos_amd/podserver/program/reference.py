@@ -121,6 +121,8 @@ def _eager(op: str, args: list, attrs: dict, ref: bool = False):
         return args[0].fill_(int(attrs["value"]))
     if op == "argmax":
         return args[0].float().argmax(dim=-1).to(torch.int32)
+    if op == "sample":
+        return T.sample(args[0], args[1], args[2].reshape(-1))
     raise ProgramError(f"op {op!r}")
 
 

@@ -318,6 +318,18 @@ def _infer(node: Node, ins: list[Value], gpu: bool) -> tuple[tuple[int, ...], st
              f"{what}: argmax runs over the last dim")
         _req(ins[0].dtype in FLOAT_DTYPES, f"{what}: takes a float tensor")
         return ins[0].shape[:-1], "i32"
+    if op == "sample":
+        # one token per row of logits, drawn as the tenant's control words say (ops.tenant.sample);
+        # pos keys the draw and is only read
+        only()
+        arity(3, 3)
+        x, ctl, p = ins
+        _req(len(x.shape) >= 1 and x.dtype in FLOAT_DTYPES, f"{what}: takes a float tensor (last dim: the logits)")
+        _req(ctl.kind == "state" and ctl.dtype == "i32" and ctl.shape == (4,),
+             f"{what}: the control words must be an i32 [4] state, got {ctl.kind} {ctl.name!r} {ctl.dtype} "
+             f"{list(ctl.shape)}")
+        _pos_vector(p, math.prod(x.shape[:-1]), what)
+        return x.shape[:-1], "i32"
     raise ProgramError(f"{what}: op {op!r} is not one the pod server runs (whitelist: {' '.join(OPS)})")
 
 
@@ -347,6 +359,7 @@ def parse_variants(objs: list, payload: bytes | memoryview = b"", gpu: bool = Fa
              f"variant {p.name!r} declares other state than {p0.name!r}: variants share one state")
         _req(p.inputs[0].shape not in seen, f"two variants take the input shape {list(p.inputs[0].shape)}")
         seen.add(p.inputs[0].shape)
+    _req(len({p.sampling_state for p in progs} - {None}) <= 1, "variants must share one sampling control state")
     return progs
 
 
@@ -410,6 +423,7 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     current = {k: k for k in state}
     root_of = {k: k for k in state}
     dead: set[str] = set()
+    sampling = None   # the control state of the program's sample nodes
     ns = obj.get("nodes")
     _req(isinstance(ns, list) and 0 < len(ns) <= MAX_NODES, f"nodes must be a list of 1..{MAX_NODES}")
     nodes = []
@@ -435,6 +449,10 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
             dead.add(tgt)
             root_of[n.output] = root_of[tgt]
             current[root_of[tgt]] = n.output
+        if op == "sample":
+            _req(sampling in (None, refs[1]), f"node {n.output!r} (sample): a program has one control state; "
+                 f"{sampling!r} and {refs[1]!r} are two")
+            sampling = refs[1]
         define(Value(n.output, shape, dt, "node"))
         nodes.append(n)
     outs = obj.get("outputs")
@@ -442,5 +460,5 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
          "outputs must name defined values")
     _req(not any(o in root_of for o in outs), "a state (or a version of one) cannot be an output: it is mutable")
     return Program(name, inputs, params, layout, nodes, list(outs), values, payload, state=state,
-                   state_root={k: v for k, v in root_of.items() if k != v})
+                   state_root={k: v for k, v in root_of.items() if k != v}, sampling_state=sampling)
 

@@ -115,6 +115,7 @@ class Tenant:
     state: dict = field(default_factory=dict)       # persistent buffers (K / V caches, positions), every variant's
     pos_limits: dict = field(default_factory=dict)  # position state -> rows of the caches written at it
     host: dict = field(default_factory=dict)        # pinned staging buffers (input, outputs, counters)
+    sampling_state: str | None = None               # the control state of its programs' ``sample`` nodes
 
 
 @dataclass
@@ -148,6 +149,7 @@ class _Job:
     outputs: list = field(default_factory=list)
     error: str | None = None
     state: dict | None = None      # the tenant's counters after the run (stateful tenants)
+    ctl: np.ndarray | None = None  # the sampling control words written before the run (sampling tenants)
 
 
 class AdmissionError(RuntimeError):
@@ -157,6 +159,24 @@ class AdmissionError(RuntimeError):
 def _wire_dtype(x) -> str:
     """The element type a tenant's input travels as: "i32" (token ids) or "f32"."""
     return "i32" if str(getattr(x, "dtype", "")) == "torch.int32" else "f32"
+
+
+def _sampling_words(req: dict, tenant: Tenant) -> np.ndarray | None:
+    """The control words a request's optional ``"sampling"`` object asks for
+    (``ops.tenant.sampling_ctl`` checks the values).  A sampling tenant's
+    request without one gets zeros: greedy, whatever the request before it
+    set.  None for a tenant whose programs draw nothing."""
+    s = req.get("sampling")
+    if s is None:
+        return np.zeros(4, dtype=np.int32) if tenant.sampling_state else None
+    if not tenant.sampling_state:
+        raise ValueError("sampling: the tenant's programs have no sample node (they are greedy)")
+    keys = ("temperature", "top_k", "top_p", "seed")
+    if not isinstance(s, dict) or set(s) - set(keys):
+        raise ValueError(f"sampling must be an object with keys among {list(keys)}")
+    from ..ops.tenant import sampling_ctl
+
+    return sampling_ctl(**s)
 
 
 def _pos_limits(progs) -> dict:
@@ -170,6 +190,11 @@ def _pos_limits(progs) -> dict:
                 rows = p.values[n.inputs[0]].shape[1]
                 lim[root] = min(lim.get(root, rows), rows)
     return lim
+
+
+def _sampling_state(progs) -> str | None:
+    """The control state the programs' ``sample`` nodes read (variants share one)."""
+    return next((p.sampling_state for p in progs if p.sampling_state), None)
 
 
 def _target_wire(trainer) -> str:
@@ -582,7 +607,7 @@ class PodServer:
                                 raise ValueError("outputs must be true / false or a list of output indices")
                         else:
                             want = bool(want)
-                        job = _Job(tenant, payload, want, shp)
+                        job = _Job(tenant, payload, want, shp, ctl=_sampling_words(req, tenant))
                         self._jobs.put(job, hi=tenant.latency)
                         job.done.wait()
                         if job.error:
@@ -605,7 +630,8 @@ class PodServer:
                         shp = req.get("shape")
                         shp = tuple(int(d) for d in shp) if isinstance(shp, list) and len(shp) <= 8 else None
                         _check_wire_dtype(req.get("dtype"), _wire_dtype(tenant.x), "input")
-                        job = _Job(tenant, payload, [feed], shp, kind="generate", steps=n, feed=feed)
+                        job = _Job(tenant, payload, [feed], shp, kind="generate", steps=n, feed=feed,
+                                   ctl=_sampling_words(req, tenant))
                         self._jobs.put(job, hi=tenant.latency)
                         job.done.wait()
                         if job.error:
@@ -829,7 +855,7 @@ class PodServer:
             m, x = built[0]
             return Tenant(tid, pod, limit, dtype, m, x, program=prog.name, compile_stats=dict(m.stats), cu_mask=mask,
                           id_bound=prog.id_bound(), alts={tuple(xv.shape): _Variant(mv, xv) for mv, xv in built[1:]},
-                          state=state, pos_limits=_pos_limits(progs))
+                          state=state, pos_limits=_pos_limits(progs), sampling_state=_sampling_state(progs))
         base = torch.cuda.memory_allocated()
         torch.cuda.reset_peak_memory_stats()
         stream = None
@@ -875,7 +901,8 @@ class PodServer:
                    outputs=v0.outputs, footprint_gb=round(peak, 3), cu_mask=mask,
                    solo_graph=v0.solo_graph, solo_outputs=v0.solo_outputs,
                    program=prog.name, compile_stats={**v0.model.stats, **times}, id_bound=prog.id_bound(),
-                   alts={tuple(v.x.shape): v for v in variants[1:]}, state=state, pos_limits=_pos_limits(progs))
+                   alts={tuple(v.x.shape): v for v in variants[1:]}, state=state, pos_limits=_pos_limits(progs),
+                   sampling_state=_sampling_state(progs))
         if limit and peak > limit:
             self._free(t)
             raise AdmissionError(f"tenant needs {peak:.2f} GB, its slice has {limit} GB")
@@ -1122,6 +1149,8 @@ class PodServer:
 
         with torch.no_grad():
             if not self.gpu:
+                if job.ctl is not None:
+                    t.state[t.sampling_state].copy_(torch.from_numpy(job.ctl))
                 if x_in is not None:
                     v.x.copy_(torch.from_numpy(x_in.copy()).view(v.x.shape))
                 v.outputs = outs = v.model(v.x)
@@ -1138,6 +1167,11 @@ class PodServer:
             else:
                 s = t.stream.torch if t.stream is not None else lane
                 with torch.cuda.stream(s):
+                    if job.ctl is not None:   # this request's sampling words, in stream order before its graph
+                        ctl = t.state[t.sampling_state]
+                        hb = _pinned(t.host, "sampling", ctl.shape, ctl.dtype)
+                        hb.numpy()[:] = job.ctl
+                        ctl.copy_(hb, non_blocking=True)
                     if x_in is not None:
                         if str(v.x.dtype)[6:] == str(x_in.dtype):
                             # through a pinned buffer: an in-stream copy, no blocking pageable one
@@ -1199,7 +1233,7 @@ class PodServer:
         import torch
 
         return {k: [int(v) for v in st.cpu().tolist()] for k, st in t.state.items()
-                if st.dtype == torch.int32 and st.numel() <= 64}
+                if st.dtype == torch.int32 and st.numel() <= 64 and k != t.sampling_state}
 
     def _counters_start(self, t: Tenant):
         """``_counters`` behind the lane's one synchronisation: the copies are
@@ -1209,7 +1243,7 @@ class PodServer:
 
         bufs = {}
         for k, st in t.state.items():
-            if st.dtype == torch.int32 and st.numel() <= 64:
+            if st.dtype == torch.int32 and st.numel() <= 64 and k != t.sampling_state:
                 hb = bufs[k] = _pinned(t.host, ("state", k), st.shape, st.dtype)
                 hb.copy_(st, non_blocking=True)
         return lambda: {k: [int(v) for v in hb.tolist()] for k, hb in bufs.items()}
