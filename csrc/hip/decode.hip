@@ -811,6 +811,32 @@ __device__ __forceinline__ float4 parts_x4(const Parts& pt, int m, int k) {
   return den > 0.f ? float4{n0 / den, n1 / den, n2 / den, n3 / den} : float4{0.f, 0.f, 0.f, 0.f};
 }
 
+// four x values of row m at column k as a GEMV stages them: read, or combined from the partials
+__device__ __forceinline__ float4 gemv_x4(const Parts& pt, const void* x, int xbf, int ldx, int m, int k) {
+  return pt.ws ? parts_x4(pt, m, k) : ld4(x, (long long)m * ldx + k, xbf);
+}
+
+// one finished output (m, n) of a GEMV: v = the scaled product; bias in bbf's dtype, y / R in xbf's
+__device__ __forceinline__ void gemv_finish(float v, int m, int n, int epi, const void* bias, int bbf, const void* res,
+                                            int ldr, void* y, int ldy, int xbf) {
+  if (epi & EPI_BIAS) v += ldf(bias, n, bbf);
+  if (epi & EPI_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
+  if (epi & EPI_RELU) v = fmaxf(v, 0.f);
+  if (epi & EPI_SILU) v = v / (1.f + __expf(-v));
+  if (epi & EPI_RESID) v += ldf(res, (long long)m * ldr + n, xbf);
+  stf(y, (long long)m * ldy + n, v, xbf);
+}
+
+// EPI_GLU: output (m, n) = silu(gate) * up of the scaled products g (row n) and u (row n + Nh)
+__device__ __forceinline__ void gemv_finish_glu(float g, float u, int m, int n, int Nh, int epi, const void* bias,
+                                                int bbf, void* y, int ldy, int xbf) {
+  if (epi & EPI_BIAS) {
+    g += ldf(bias, n, bbf);
+    u += ldf(bias, n + Nh, bbf);
+  }
+  stf(y, (long long)m * ldy + n, g / (1.f + __expf(-g)) * u, xbf);
+}
+
 template <int M, int WBF, int KU>
 __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ x, int xbf, int ldx,
                                                    const void* __restrict__ w, int /*wbf = WBF*/, int ldw,
@@ -851,7 +877,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ x, i
   }
   for (int e = tid * 4; e < M * K; e += 1024) {
     const int m = e / K, k = e % K;
-    *reinterpret_cast<float4*>(&xs[e]) = pt.ws ? parts_x4(pt, m, k) : ld4(x, (long long)m * ldx + k, xbf);
+    *reinterpret_cast<float4*>(&xs[e]) = gemv_x4(pt, x, xbf, ldx, m, k);
   }
   __syncthreads();
   if (rms_eps > 0.f) {  // RMSNorm of each row, gamma folded into W
@@ -909,14 +935,8 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ x, i
     if (glu) {  // lane m finishes output (m, n0): silu(gate) * up
 #pragma unroll
       for (int m = 0; m < M; ++m)
-        if (lane == m && n0 < Nh) {
-          float g = acc[0][m] * rsc[m], u = acc[1][m] * rsc[m];
-          if (epi & EPI_BIAS) {
-            g += ldf(bias, n0, wbf);
-            u += ldf(bias, n0 + Nh, wbf);
-          }
-          stf(y, (long long)m * ldy + n0, g / (1.f + __expf(-g)) * u, xbf);
-        }
+        if (lane == m && n0 < Nh)
+          gemv_finish_glu(acc[0][m] * rsc[m], acc[1][m] * rsc[m], m, n0, Nh, epi, bias, wbf, y, ldy, xbf);
       continue;
     }
     // lane (c * M + m) finishes output (m, n0 + c)
@@ -925,16 +945,211 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ x, i
 #pragma unroll
       for (int m = 0; m < M; ++m) {
         const int n = n0 + c;
-        if (lane == c * M + m && n < N) {
-          float v = acc[c][m] * rsc[m];
-          if (epi & EPI_BIAS) v += ldf(bias, n, wbf);
-          if (epi & EPI_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
-          if (epi & EPI_RELU) v = fmaxf(v, 0.f);
-          if (epi & EPI_SILU) v = v / (1.f + __expf(-v));
-          if (epi & EPI_RESID) v += ldf(res, (long long)m * ldr + n, xbf);
-          stf(y, (long long)m * ldy + n, v, xbf);
+        if (lane == c * M + m && n < N)
+          gemv_finish(acc[c][m] * rsc[m], m, n, epi, bias, wbf, res, ldr, y, ldy, xbf);
+      }
+  }
+}
+
+// ------------------------------------------------------------------ int8 weight-only GEMV (M <= 8)
+// W = q [N, K] int8 with one fp32 scale per row (a storage format: the product is that of the
+// dequantized fp32 weight): acc = sum_k x[m][k] (float)q[n][k] in fp32 FMAs, then
+// y = act(acc * wscale[n] * rsc[m] + bias) + R.  A lane's 16-byte load is 16 consecutive k of one
+// row, and a wave streams Q8_R rows (Q8_R x KU loads in flight per lane).  x sits in LDS as fp32,
+// PERMUTED: in the natural layout a lane's four float4 of x for those 16 k lie 64 bytes from the
+// next lane's, a 4-way conflict in every 16-lane group of ds_read_b128; here the four are, over the
+// wave, four contiguous runs (16-byte lane stride, conflict-free):
+//   k = 1024 b + 16 l + 4 j + e  ->  1024 b + 4 nl j + 4 l + e,  nl = min(64, (K - 1024 b) / 16)
+// (nl: the lanes block b has work for; K % 16 == 0).  RMSNorm prologue: the statistics of the raw x
+// rows are summed from the registers that stage them, and gamma (a pointer: per-row weight scales
+// leave no room to fold it into W) multiplies x on its way into LDS.
+constexpr int Q8_R = 4;   // weight rows per wave: 16 per workgroup pass (GLU: 8 gate + 8 up)
+
+__device__ __forceinline__ float4 q8_cvt4(unsigned v) {
+  return float4{(float)(int)(signed char)(v & 255u), (float)(int)(signed char)((v >> 8) & 255u),
+                (float)(int)(signed char)((v >> 16) & 255u), (float)(int)(signed char)(v >> 24)};
+}
+
+template <int M, int KU>
+__global__ __launch_bounds__(256) void gemv_q8_kernel(const float* __restrict__ x, int ldx,
+                                                      const signed char* __restrict__ w, int ldw,
+                                                      const float* __restrict__ wscale,
+                                                      const float* __restrict__ gamma, const float* __restrict__ bias,
+                                                      const float* __restrict__ res, int ldr, float* __restrict__ y,
+                                                      int ldy, int N, int K, int epi, float rms_eps, Parts pt) {
+  static_assert(Q8_R == 4, "the 4 x 4 word table below and the GLU pairing are written for four rows");
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // [M][K] fp32, each row permuted as above
+  __shared__ float rsc[M];
+  __shared__ float sqp[4][M];   // the waves' sums of squares of each x row
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const bool glu = (epi & EPI_GLU) != 0;
+  const int Nh = N / 2;
+  const int ngrp = glu ? (Nh + 7) / 8 : (N + 15) / 16;
+  // the wave's Q8_R weight rows of column group grp; GLU: gates n0, n0 + 1, then their ups
+  auto rows_of = [&](int grp, int& n0, long long (&wr)[Q8_R]) {
+    n0 = glu ? grp * 8 + wid * 2 : grp * 16 + wid * Q8_R;
+#pragma unroll
+    for (int c = 0; c < Q8_R; ++c) {
+      const int n = glu ? min(n0 + (c & 1), Nh - 1) + (c >> 1) * Nh : min(n0 + c, N - 1);
+      wr[c] = (long long)n * ldw;
+    }
+  };
+  auto load_chunk = [&](const long long (&wr)[Q8_R], int kb, uint4 (&a)[Q8_R][KU]) {
+#pragma unroll
+    for (int u = 0; u < KU; ++u) {
+      const int k = kb + 1024 * u + lane * 16;
+#pragma unroll
+      for (int c = 0; c < Q8_R; ++c)
+        a[c][u] = k < K ? *reinterpret_cast<const uint4*>(w + wr[c] + k) : uint4{0u, 0u, 0u, 0u};
+    }
+  };
+  // the first group's first K chunk of weights in flight while x is staged (as gemv_kernel); later
+  // groups' while the one before is computed
+  uint4 pa[Q8_R][KU];
+  if ((int)blockIdx.x < ngrp) {
+    int n0;
+    long long wr[Q8_R];
+    rows_of(blockIdx.x, n0, wr);
+    load_chunk(wr, 0, pa);
+  }
+  float sq[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) sq[m] = 0.f;
+  // p: the LDS position, its k from the permutation; a thread's loads go out four at a time (a
+  // 2816-wide row is three per thread: one memory round trip, not three one after the other)
+  constexpr int SU = 4;
+  for (int p0 = tid * 4; p0 < M * K; p0 += 1024 * SU) {
+    float4 v[SU], g[SU];
+    int ms[SU];
+#pragma unroll
+    for (int s = 0; s < SU; ++s) {
+      const int p = p0 + 1024 * s;
+      if (p < M * K) {
+        const int m = p / K, pk = p % K;
+        const int b = pk >> 10, o = pk & 1023;
+        const int nl = min(64, (K - (b << 10)) >> 4);
+        const int k = (b << 10) + 16 * ((o % (4 * nl)) >> 2) + 4 * (o / (4 * nl));
+        ms[s] = m;
+        v[s] = gemv_x4(pt, x, 0, ldx, m, k);
+        g[s] = gamma != nullptr ? *reinterpret_cast<const float4*>(gamma + k) : float4{1.f, 1.f, 1.f, 1.f};
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < SU; ++s) {
+      const int p = p0 + 1024 * s;
+      if (p < M * K) {
+        float4 t = v[s];
+        if (rms_eps > 0.f) {
+          const float q = fmaf(t.x, t.x, fmaf(t.y, t.y, fmaf(t.z, t.z, t.w * t.w)));
+#pragma unroll
+          for (int mm = 0; mm < M; ++mm) sq[mm] += mm == ms[s] ? q : 0.f;
+          t = float4{t.x * g[s].x, t.y * g[s].y, t.z * g[s].z, t.w * g[s].w};
+        }
+        *reinterpret_cast<float4*>(&xs[p]) = t;
+      }
+    }
+  }
+  if (rms_eps > 0.f) {
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      const float t = nos::wave_sum(sq[m]);
+      if (lane == 0) sqp[wid][m] = t;
+    }
+  }
+  __syncthreads();
+  if (tid < M)
+    rsc[tid] = rms_eps > 0.f
+                   ? rsqrtf(((sqp[0][tid] + sqp[1][tid]) + (sqp[2][tid] + sqp[3][tid])) / (float)K + rms_eps)
+                   : 1.f;
+  __syncthreads();
+  for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    int n0;
+    long long wr[Q8_R];
+    rows_of(grp, n0, wr);
+    float acc[Q8_R][M];
+#pragma unroll
+    for (int c = 0; c < Q8_R; ++c)
+#pragma unroll
+      for (int m = 0; m < M; ++m) acc[c][m] = 0.f;
+    for (int kb = 0; kb < K; kb += 1024 * KU) {
+      uint4 ra[Q8_R][KU];
+      if (kb == 0) {   // prefetched; the workgroup's next group's first chunk goes out before this one's math
+#pragma unroll
+        for (int c = 0; c < Q8_R; ++c)
+#pragma unroll
+          for (int u = 0; u < KU; ++u) ra[c][u] = pa[c][u];
+        if (grp + (int)gridDim.x < ngrp) {
+          int nn;
+          long long wn[Q8_R];
+          rows_of(grp + gridDim.x, nn, wn);
+          load_chunk(wn, 0, pa);
+        }
+      } else {
+        load_chunk(wr, kb, ra);
+      }
+#pragma unroll
+      for (int u = 0; u < KU; ++u) {
+        const int k0 = kb + 1024 * u;               // block k0 / 1024 of the row
+        if (k0 + lane * 16 < K) {
+          const int nl = min(64, (K - k0) >> 4);
+          const unsigned wd[Q8_R][4] = {{ra[0][u].x, ra[0][u].y, ra[0][u].z, ra[0][u].w},
+                                        {ra[1][u].x, ra[1][u].y, ra[1][u].z, ra[1][u].w},
+                                        {ra[2][u].x, ra[2][u].y, ra[2][u].z, ra[2][u].w},
+                                        {ra[3][u].x, ra[3][u].y, ra[3][u].z, ra[3][u].w}};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float4 wf[Q8_R];
+#pragma unroll
+            for (int c = 0; c < Q8_R; ++c) wf[c] = q8_cvt4(wd[c][j]);
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+              const float4 xv = *reinterpret_cast<const float4*>(&xs[m * K + k0 + 4 * nl * j + 4 * lane]);
+#pragma unroll
+              for (int c = 0; c < Q8_R; ++c)
+                acc[c][m] = fmaf(wf[c].x, xv.x, fmaf(wf[c].y, xv.y, fmaf(wf[c].z, xv.z, fmaf(wf[c].w, xv.w, acc[c][m]))));
+            }
+          }
         }
       }
+    }
+#pragma unroll
+    for (int c = 0; c < Q8_R; ++c)
+#pragma unroll
+      for (int m = 0; m < M; ++m) acc[c][m] = nos::wave_sum(acc[c][m]);
+    if (glu) {  // lane (c * M + m), c < 2, finishes output (m, n0 + c) from gate row c and up row c + 2
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+          const int n = n0 + c;
+          if (lane == c * M + m && n < Nh)
+            gemv_finish_glu(acc[c][m] * wscale[n] * rsc[m], acc[c + 2][m] * wscale[n + Nh] * rsc[m], m, n, Nh, epi,
+                            bias, 0, y, ldy, 0);
+        }
+      continue;
+    }
+    // lane (c * M + m) finishes output (m, n0 + c)
+#pragma unroll
+    for (int c = 0; c < Q8_R; ++c)
+#pragma unroll
+      for (int m = 0; m < M; ++m) {
+        const int n = n0 + c;
+        if (lane == c * M + m && n < N)
+          gemv_finish(acc[c][m] * wscale[n] * rsc[m], m, n, epi, bias, 0, res, ldr, y, ldy, 0);
+      }
+  }
+}
+
+// out [N, K] fp32 = (float)q * wscale[n], one rounding: 4 weights per thread (a 4-byte load, a 16-byte store)
+__global__ __launch_bounds__(256) void dequant_q8_kernel(const signed char* __restrict__ w, int ldw,
+                                                         const float* __restrict__ wscale, float* __restrict__ out,
+                                                         int ldo, int N, int K) {
+  const long long total = (long long)N * (K / 4);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int n = (int)(i / (K / 4)), k = (int)(i % (K / 4)) * 4;
+    const float4 q = q8_cvt4(*reinterpret_cast<const unsigned*>(w + (long long)n * ldw + k));
+    const float s = wscale[n];
+    *reinterpret_cast<float4*>(out + (long long)n * ldo + k) = float4{q.x * s, q.y * s, q.z * s, q.w * s};
   }
 }
 
@@ -1185,5 +1400,92 @@ static int gemv_launch(const void* x, int xbf, int ldx, const void* w, int wbf, 
   }
 #undef NOS_GEMV
 #undef NOS_GEMV_KU
+  return (int)hipGetLastError();
+}
+
+// y [M, N] fp32 = act(rms(x) gamma x [M, K] . (q [N, K] int8 * wscale [N])^T + bias) + res, M <= 8: the
+// decode step of an int8 weight-only tenant (gemv_q8_kernel).  K % 16 == 0, ldw % 16 == 0, q 16-byte
+// aligned, M x K x 4 <= 64 KiB; gamma (or null: ones) only with rms_eps > 0.  grid: up to 3 workgroups
+// per CU walk the N / 16 column groups.
+static int gemv_q8_launch(const float* x, int ldx, const void* wq, int ldw, const float* wscale, const float* gamma,
+                          const float* bias, const float* res, int ldr, float* y, int ldy, int M, int N, int K,
+                          int epi, float rms_eps, Parts pt, hipStream_t stream) {
+  if (!wq || !wscale || !y || M <= 0 || M > 8 || N <= 0 || K <= 0 || (K % 16) || ldw < K || (ldw % 16) ||
+      ((uintptr_t)wq & 15) || (long long)M * K * 4 > 65536 || ((epi & EPI_BIAS) && !bias) ||
+      ((epi & EPI_RESID) && (!res || ldr < N)) || ldy < ((epi & EPI_GLU) ? N / 2 : N) ||
+      (gamma && (!(rms_eps > 0.f) || ((uintptr_t)gamma & 15))))
+    return (int)hipErrorInvalidValue;
+  if ((epi & EPI_GLU) && ((N % 2) || (epi & (EPI_RESID | EPI_GELU | EPI_RELU | EPI_SILU))))
+    return (int)hipErrorInvalidValue;
+  const int ngrp = (epi & EPI_GLU) ? (N / 2 + 7) / 8 : (N + 15) / 16;
+  // a vocabulary head (2000 groups): the workgroups a CU holds at once (3 at M = 1) each walk a few
+  // groups, the next one's weights prefetched, and stage x once
+  const int cap = 3 * nos_effective_cus();
+  const unsigned grid = (unsigned)(ngrp < cap ? ngrp : cap);
+  const size_t lds = (size_t)M * K * 4;
+#define NOS_GEMV_Q8_KU(m, ku)                                                                                  \
+  hipLaunchKernelGGL((gemv_q8_kernel<m, ku>), dim3(grid), dim3(256), lds, stream, x, ldx,                      \
+                     static_cast<const signed char*>(wq), ldw, wscale, gamma, bias, res, ldr, y, ldy, N, K, epi, \
+                     rms_eps, pt)
+  // K <= 1024: the whole row in one batch of Q8_R loads per lane; longer rows (a down projection's
+  // 2816) in batches of 3 x Q8_R
+#define NOS_GEMV_Q8(m)      \
+  if (K > 1024)             \
+    NOS_GEMV_Q8_KU(m, 3);   \
+  else                      \
+    NOS_GEMV_Q8_KU(m, 1)
+  switch (M) {
+    case 1: NOS_GEMV_Q8(1); break;
+    case 2: NOS_GEMV_Q8(2); break;
+    case 3: NOS_GEMV_Q8(3); break;
+    case 4: NOS_GEMV_Q8(4); break;
+    case 5: NOS_GEMV_Q8(5); break;
+    case 6: NOS_GEMV_Q8(6); break;
+    case 7: NOS_GEMV_Q8(7); break;
+    default: NOS_GEMV_Q8(8); break;
+  }
+#undef NOS_GEMV_Q8
+#undef NOS_GEMV_Q8_KU
+  return (int)hipGetLastError();
+}
+
+NOS_API int nos_gemv_q8(const float* x, int ldx, const void* wq, int ldw, const float* wscale, const float* gamma,
+                        const float* bias, const float* res, int ldr, float* y, int ldy, int M, int N, int K, int epi,
+                        float rms_eps, hipStream_t stream) {
+  if (!x || ldx < K || (ldx % 4) || ((uintptr_t)x & 15)) return (int)hipErrorInvalidValue;
+  return gemv_q8_launch(x, ldx, wq, ldw, wscale, gamma, bias, res, ldr, y, ldy, M, N, K, epi, rms_eps, Parts{},
+                        stream);
+}
+
+// nos_gemv_q8 with x = the decode attention's split partials (as nos_gemv_partials): the combine
+// launch folded into an int8 O-projection
+NOS_API int nos_gemv_q8_partials(const float* ws, long long ws_n, int NS, int R, int G, int Hkv, int D, const void* wq,
+                                 int ldw, const float* wscale, const float* bias, const float* res, int ldr, float* y,
+                                 int ldy, int M, int N, int K, int epi, hipStream_t stream) {
+  if (!ws || NS <= 0 || G <= 0 || Hkv <= 0 || (D != 64 && D != 128) || R != G || K != Hkv * G * D || M <= 0 ||
+      M > 8 || ws_n < (long long)M * Hkv * NS * R * (D + 2) || (epi & EPI_GLU))
+    return (int)hipErrorInvalidValue;
+  Parts pt;
+  pt.ws = ws;
+  pt.NS = NS;
+  pt.R = R;
+  pt.G = G;
+  pt.Hkv = Hkv;
+  pt.D = D;
+  return gemv_q8_launch(nullptr, K, wq, ldw, wscale, nullptr, bias, res, ldr, y, ldy, M, N, K, epi, 0.f, pt, stream);
+}
+
+// out [N, K] fp32 (row stride ldo) = (float)q [N, K] int8 * wscale [N], bit-exact: the weight of an
+// int8 linear at more than 8 rows, for the h3 product.  K, ldw % 4 == 0, ldo % 4 == 0, out 16-byte aligned.
+NOS_API int nos_dequant_q8(const void* wq, int ldw, const float* wscale, float* out, int ldo, int N, int K,
+                           hipStream_t stream) {
+  if (!wq || !wscale || !out || N <= 0 || K <= 0 || (K % 4) || ldw < K || (ldw % 4) || ldo < K || (ldo % 4) ||
+      ((uintptr_t)wq & 3) || ((uintptr_t)out & 15))
+    return (int)hipErrorInvalidValue;
+  const long long total = (long long)N * (K / 4);
+  const long long cap = 32LL * nos_effective_cus();
+  const long long blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(dequant_q8_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, stream,
+                     static_cast<const signed char*>(wq), ldw, wscale, out, ldo, N, K);
   return (int)hipGetLastError();
 }

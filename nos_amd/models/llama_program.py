@@ -22,7 +22,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..podserver.program import Builder
+from ..podserver.program import Builder, dequantize_rows_q8, quantize_rows_q8
+
+# the HF Llama linears an int8 tenant stores quantized (every weight but the embedding table and the norms)
+_Q8_LINEARS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
 
 
 def llama_config(small: bool = True, **kw):
@@ -108,7 +111,8 @@ def llama_program(model, seq: int, batch: int = 1, dtype: str = "fp32",
 
 
 def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, dtype: str = "fp32",
-                          extend: tuple[int, ...] = (), sampling: bool = False) -> tuple[list[dict], bytes]:
+                          extend: tuple[int, ...] = (), sampling: bool = False,
+                          weights: str = "fp32") -> tuple[list[dict], bytes]:
     """A STATEFUL generation tenant: ``[prefill, decode, *extends]`` programs
     over one weight payload and one state -- per layer a K and a V cache
     ``[batch, max_len, kv_heads, head_dim]`` plus the position counter
@@ -136,9 +140,22 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     the request's temperature / top-k / top-p / seed, keyed on the position
     before the step's advance (the prefill draws at counter 0, the decode
     steps at ``prompt_len``, ``prompt_len`` + 1, ...); a request without
-    sampling parameters stays greedy."""
+    sampling parameters stays greedy.
+
+    ``weights="int8"`` (fp32 tenants): every linear's weight is stored as int8
+    rows with one fp32 scale per output row (``Builder.param_q8``) and read by
+    ``linear_q8`` nodes -- q / k / v merged into one weight, o, gate / up
+    merged, down and the LM head (its own quantized copy when the head is
+    tied; the embedding table stays fp32).  Quantization is a storage format:
+    the server computes, in fp32, exactly the model
+    :func:`dequantized_llama` returns."""
     if not 0 < prompt_len <= max_len:
         raise ValueError(f"prompt_len must be in [1, {max_len}]")
+    if weights not in ("fp32", "int8"):
+        raise ValueError(f"weights must be 'fp32' or 'int8', got {weights!r}")
+    if weights == "int8" and dtype != "fp32":
+        raise ValueError("int8 weights are an fp32 tenant's storage format: dtype must be 'fp32'")
+    q8 = weights == "int8"
     cfg = model.config
     sd = {k: v.detach().float().cpu().numpy() for k, v in model.state_dict().items()}
     d, nh = cfg.hidden_size, cfg.num_attention_heads
@@ -150,11 +167,22 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     cache_dt = "bf16" if dtype == "bf16" else "fp32"
     progs = []
     chunks = [(prompt_len, True), (1, False)] + [(n, False) for n in extend]
-    weights = b""
+    payload = b""
     for seq, reset in chunks:
-        b = Builder(f"llama-h{d}-l{cfg.num_hidden_layers}-{dtype}-{'prefill' if reset else 'step'}{seq}")
+        b = Builder(f"llama-h{d}-l{cfg.num_hidden_layers}-{dtype}{'-q8' if q8 else ''}-"
+                    f"{'prefill' if reset else 'step'}{seq}")
         ids = b.input("input_ids", [batch, seq], "i32")
         P = lambda k: b.param(k, sd[k], dtype)  # noqa: E731
+
+        def lin(x, name, *keys, out=None):
+            """x @ W^T: a ``linear`` over the weight ``name``; for int8 weights a ``linear_q8`` over
+            the rows of ``keys``' weights (default: ``name``'s), merged and then quantized -- with a
+            scale per row that equals quantizing each and merging, so no compiler pass has to merge."""
+            if not q8:
+                return b.op("linear", x, P(name), out=out)
+            wq, sc = b.param_q8(name, np.concatenate([sd[k] for k in keys or (name,)], axis=0))
+            return b.op("linear_q8", x, wq, sc, out=out)
+
         rc, rs = b.param("rope.cos", cos, "fp32"), b.param("rope.sin", sin, "fp32")
         b.state("pos", [batch], "i32")
         ctl = b.state("sampling", [4], "i32") if sampling else None
@@ -165,28 +193,64 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
         for i in range(cfg.num_hidden_layers):
             pf = f"model.layers.{i}."
             y = b.op("rmsnorm", h, P(pf + "input_layernorm.weight"), eps=eps)
-            q = b.op("reshape", b.op("linear", y, P(pf + "self_attn.q_proj.weight")), shape=[batch, seq, nh, hd])
-            k = b.op("reshape", b.op("linear", y, P(pf + "self_attn.k_proj.weight")), shape=[batch, seq, nkv, hd])
-            v = b.op("reshape", b.op("linear", y, P(pf + "self_attn.v_proj.weight")), shape=[batch, seq, nkv, hd])
+            if q8:
+                qkv = lin(y, pf + "self_attn.qkv_proj.weight", *(pf + f"self_attn.{t}_proj.weight" for t in "qkv"))
+                ends = (0, nh * hd, (nh + nkv) * hd, (nh + 2 * nkv) * hd)
+                proj = lambda t: b.op("slice", qkv, dim=-1, start=ends[t], end=ends[t + 1])  # noqa: E731
+            else:
+                proj = lambda t: b.op("linear", y, P(pf + f"self_attn.{'qkv'[t]}_proj.weight"))  # noqa: E731
+            q = b.op("reshape", proj(0), shape=[batch, seq, nh, hd])
+            k = b.op("reshape", proj(1), shape=[batch, seq, nkv, hd])
+            v = b.op("reshape", proj(2), shape=[batch, seq, nkv, hd])
             q, k = b.op("rotary_at", q, rc, rs, p), b.op("rotary_at", k, rc, rs, p)
             kc = b.op("kv_write", caches[i][0], k, p)
             vc = b.op("kv_write", caches[i][1], v, p)
             o = b.op("reshape", b.op("sdpa_cache", q, kc, vc, p), shape=[batch, seq, nh * hd])
-            h = b.op("add", b.op("linear", o, P(pf + "self_attn.o_proj.weight")), h)
+            h = b.op("add", lin(o, pf + "self_attn.o_proj.weight"), h)
             y = b.op("rmsnorm", h, P(pf + "post_attention_layernorm.weight"), eps=eps)
-            g = b.op("linear", y, P(pf + "mlp.gate_proj.weight"))
-            u = b.op("linear", y, P(pf + "mlp.up_proj.weight"))
-            h = b.op("add", b.op("linear", b.op("mul", b.op("silu", g), u), P(pf + "mlp.down_proj.weight")), h)
+            if q8:
+                gu = lin(y, pf + "mlp.gate_up_proj.weight", pf + "mlp.gate_proj.weight", pf + "mlp.up_proj.weight")
+                inter = sd[pf + "mlp.gate_proj.weight"].shape[0]
+                g = b.op("slice", gu, dim=-1, start=0, end=inter)
+                u = b.op("slice", gu, dim=-1, start=inter, end=2 * inter)
+            else:
+                g = b.op("linear", y, P(pf + "mlp.gate_proj.weight"))
+                u = b.op("linear", y, P(pf + "mlp.up_proj.weight"))
+            h = b.op("add", lin(b.op("mul", b.op("silu", g), u), pf + "mlp.down_proj.weight"), h)
         if seq > 1:   # only the last token's logits: the LM head runs on one row
             h = b.op("slice", h, dim=1, start=seq - 1, end=seq)
         h = b.op("rmsnorm", h, P("model.norm.weight"), eps=eps)
-        logits = b.op("linear", h, P(head), out="logits")
+        # a tied head reads the embedding table: quantized, it is a copy of its own (the table stays fp32)
+        logits = lin(h, "lm_head.weight", head, out="logits") if q8 else lin(h, head, out="logits")
         nxt = b.op("sample", logits, ctl, p, out="next_ids") if sampling else b.op("argmax", logits, out="next_ids")
         b.op("pos_add", p, n=seq)
         prog, w = b.build([logits, nxt])
         progs.append(prog)
-        weights = w
-    return progs, weights
+        payload = w
+    return progs, payload
+
+
+def dequantized_llama(model):
+    """A deep copy of the HF model whose linear weights (attention and MLP
+    projections, the LM head -- untied from the embedding table, which stays
+    fp32) are ``dequantize(quantize(w))`` row by row: the model an int8
+    tenant of ``model`` computes (``llama_decode_programs(weights="int8")``),
+    for tests and users to compare against."""
+    import copy
+
+    import torch
+
+    m = copy.deepcopy(model)
+    with torch.no_grad():
+        head = m.lm_head.weight.detach().float().cpu().numpy()
+        if m.lm_head.weight.data_ptr() == m.model.embed_tokens.weight.data_ptr():   # tied: the head gets its own copy
+            m.config.tie_word_embeddings = False
+            m.lm_head.weight = torch.nn.Parameter(m.lm_head.weight.detach().clone())
+        for name, p in m.named_parameters():
+            if name == "lm_head.weight" or (name.endswith("_proj.weight") and name.split(".")[-2] in _Q8_LINEARS):
+                w = head if name == "lm_head.weight" else p.detach().float().cpu().numpy()
+                p.copy_(torch.from_numpy(dequantize_rows_q8(*quantize_rows_q8(w))).to(p.dtype))
+    return m
 
 
 def llama_tenant(dtype: str = "fp32", seed: int = 0, small: bool = True, seq: int = 512,
@@ -197,4 +261,5 @@ def llama_tenant(dtype: str = "fp32", seed: int = 0, small: bool = True, seq: in
     return llama_program(m, seq if small else 64, batch, dtype)
 
 
-__all__ = ["llama_config", "llama_model", "llama_program", "llama_decode_programs", "llama_tenant", "rope_tables"]
+__all__ = ["llama_config", "llama_model", "llama_program", "llama_decode_programs", "llama_tenant", "rope_tables",
+           "dequantized_llama"]

@@ -117,6 +117,12 @@ _SIGS = {
                  c_int, c_int, c_int, c_float, c_void_p],
     "nos_gemv_partials": [c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                           c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    # decode.hip: int8 weight-only linears (the GEMV of a decode step; the fp32 weight for more rows)
+    "nos_gemv_q8": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                    c_int, c_int, c_int, c_int, c_float, c_void_p],
+    "nos_gemv_q8_partials": [c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                             c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "nos_dequant_q8": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "nos_attn_h3g_workspace": [c_int, c_int, c_int, c_int, c_int, c_int],
     # LayerNorm hand-off (gemm_f32h.hip): producer row statistics, LN in the consumer's A load
     "nos_gemm_f32h3_stats": [c_void_p, c_int, c_ll, c_void_p, c_float, c_void_p, c_int, c_ll, c_void_p, c_void_p,

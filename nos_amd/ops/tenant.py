@@ -461,16 +461,23 @@ def _rows_h3(x3: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     return _split_rows_h3(x2 if x2.stride(-1) == 1 and x2.is_contiguous() else x2.contiguous(), ln=False)
 
 
-def mm(a: torch.Tensor, b: torch.Tensor, a_t: bool = False, b_t: bool = False) -> torch.Tensor:
+def mm(a: torch.Tensor, b: torch.Tensor, a_t: bool = False, b_t: bool = False, bias: torch.Tensor | None = None,
+       act: str | None = None, residual: torch.Tensor | None = None) -> torch.Tensor:
     """op(a) @ op(b) on the h3 batched GEMM, op(x) = x^T (last two dims) when
     the flag is set; batch dims equal, or one side 2-D.  A transposed A or a
     plain B operand is split by columns (``nos_split_cols_h3``), so no
     operand is ever copied into its transpose (training's dX = dY W and
-    dW = dY^T X, attention's P V and P^T dO)."""
+    dW = dY^T X, attention's P V and P^T dO).  An unbatched product takes the
+    GEMM's epilogue: ``bias`` [N], ``act`` (gelu / relu), then ``residual``
+    [M, N] (contiguous fp32)."""
     if not a.is_cuda:
         A = a.transpose(-1, -2) if a_t else a
         B = b.transpose(-1, -2) if b_t else b
-        return (A.float() @ B.float()).to(a.dtype)
+        y = A.float() @ B.float()
+        if bias is not None:
+            y = y + bias.float()
+        y = _act(y, act)
+        return (y if residual is None else y + residual.float()).to(a.dtype)
     dt = a.dtype
     M, K = (a.shape[-1], a.shape[-2]) if a_t else (a.shape[-2], a.shape[-1])
     N, Kb = (b.shape[-2], b.shape[-1]) if b_t else (b.shape[-1], b.shape[-2])
@@ -484,8 +491,12 @@ def mm(a: torch.Tensor, b: torch.Tensor, a_t: bool = False, b_t: bool = False) -
     bp, brinv = _rows_h3(b3) if b_t else _split_cols_h3(b3)      # W rows: op(b)'s N columns of K
     Kp = ap.shape[2]
     out = torch.empty((nb, M, N), dtype=torch.float32, device=a.device)
+    epi = _act_epi(act) | (EPI_BIAS if bias is not None else 0) | (EPI_RESID if residual is not None else 0)
+    if epi and (nb != 1 or (residual is not None and (residual.shape != (M, N) or not residual.is_contiguous()
+                                                        or residual.dtype != torch.float32))):
+        raise ValueError("mm: the epilogue takes an unbatched product and a contiguous fp32 [M, N] residual")
     _gemm_batched(ap, arinv, M * Kp if ba else 0, M if ba else 0, bp, brinv, N * Kp if bb else 0, N if bb else 0,
-                  out, M, N, Kp, nb, 0)
+                  out, M, N, Kp, nb, epi, bias=None if bias is None else bias.float().contiguous(), residual=residual)
     out = out.view(*bshape, M, N)
     return out if dt == torch.float32 else out.to(dt)
 
@@ -1037,13 +1048,160 @@ def gemv_partials(p: DecodePartials, w: torch.Tensor, bias: torch.Tensor | None 
     return y
 
 
+# ------------------------------------------------------------------ int8 weight-only linears
+def _q8_epi(bias, act, residual, glu) -> int:
+    epi = (EPI_BIAS if bias is not None else 0) | (EPI_RESID if residual is not None else 0) | (EPI_GLU if glu else 0)
+    return epi | {"gelu": EPI_GELU, "relu": EPI_RELU, "silu": EPI_SILU}.get(act or "", 0)
+
+
+def linear_q8_ref(x, wq, wscale, bias=None, act=None, residual=None, rms_eps: float = 0.0, gamma=None,
+                  glu: bool = False, dtype: torch.dtype = torch.float32):
+    """What an int8 weight-only linear means, in ``dtype`` arithmetic:
+    ``act(x' @ (wq.float() * wscale[:, None]).T + bias) + residual`` with
+    ``x' = rmsnorm(x) * gamma`` when ``rms_eps`` > 0, ``silu(gate) * up`` of
+    the two halves of the columns for ``glu``.  The dequantized weight is
+    formed in fp32 (one rounding, the storage format's definition) whatever
+    ``dtype`` the product runs in."""
+    wf = (wq.to(torch.float32) * wscale.to(torch.float32)[:, None]).to(dtype)
+    xf = x.to(dtype)
+    if rms_eps:
+        xf = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + rms_eps)
+        if gamma is not None:
+            xf = xf * gamma.to(dtype)
+    y = F.linear(xf, wf, None if bias is None else bias.to(dtype))
+    if glu:
+        h = y.shape[-1] // 2
+        y = F.silu(y[..., :h]) * y[..., h:]
+    y = F.silu(y) if act == "silu" else _act(y, act)
+    return y if residual is None else y + residual.to(dtype).reshape(y.shape)
+
+
+def gemv_q8_ok(x2: torch.Tensor, wq: torch.Tensor) -> bool:
+    """Whether the int8 GEMV takes this [M, K] fp32 x [N, K] int8 product."""
+    M, K = x2.shape
+    return (x2.is_cuda and 0 < M <= GEMV_MAX_ROWS and K % 16 == 0 and M * K * 4 <= 65536 and x2.stride(-1) == 1
+            and x2.stride(0) % 4 == 0 and x2.dtype == torch.float32 and x2.data_ptr() % 16 == 0
+            and wq.dtype == torch.int8 and wq.dim() == 2 and wq.shape[1] == K and wq.stride(-1) == 1
+            and wq.stride(0) % 16 == 0 and wq.data_ptr() % 16 == 0)
+
+
+def _q8_operands(wscale, gamma, bias, residual, M, N, K=None):
+    if (wscale.numel() != N or (bias is not None and bias.numel() != N) or (gamma is not None and gamma.numel() != K)
+            or (residual is not None and residual.numel() != M * N)):
+        raise ValueError(f"linear_q8: wscale / bias [{N}], gamma [{K}] and residual [{M}, {N}] required")
+    sc = wscale.float().contiguous()
+    g = None if gamma is None else gamma.float().contiguous()
+    b = None if bias is None else bias.float().contiguous()
+    r = None if residual is None else residual.reshape(M, N).float()
+    if r is not None and r.stride(-1) != 1:
+        r = r.contiguous()
+    return sc, g, b, r
+
+
+def gemv_q8(x2: torch.Tensor, wq: torch.Tensor, wscale: torch.Tensor, bias: torch.Tensor | None = None,
+            act: str | None = None, residual: torch.Tensor | None = None, rms_eps: float = 0.0,
+            gamma: torch.Tensor | None = None, glu: bool = False) -> torch.Tensor:
+    """y [M, N] = act(x' [M, K] (wq * wscale)^T + b) + R for M <= 8
+    (:func:`gemv_q8_ok`; :func:`linear_q8_ref` defines x' and ``glu``): the
+    weight-streaming kernel of an int8 tenant's decode step, one byte of HBM
+    per weight, fp32 FMAs on the int8 values and the row scale in the epilogue."""
+    M, K = x2.shape
+    N = wq.shape[0]
+    y = torch.empty((M, N // 2 if glu else N), dtype=torch.float32, device=x2.device)
+    if not gemv_q8_ok(x2, wq) or (glu and N % 2):
+        raise ValueError(f"gemv_q8: x {tuple(x2.shape)} {x2.dtype} and W {tuple(wq.shape)} {wq.dtype} are not a "
+                         f"product the int8 GEMV takes (gemv_q8_ok)")
+    sc, g, b, r = _q8_operands(wscale, gamma, bias, residual, M, N, K)
+    _lib.check(_lib.lib().nos_gemv_q8(x2.data_ptr(), x2.stride(0), wq.data_ptr(), wq.stride(0), sc.data_ptr(), _ptr(g),
+                                      _ptr(b), _ptr(r), r.stride(0) if r is not None else 0, y.data_ptr(), y.stride(0),
+                                      M, N, K, _q8_epi(b, act, r, glu), float(rms_eps), _stream()), "nos_gemv_q8")
+    return y
+
+
+def gemv_q8_partials(p: DecodePartials, wq: torch.Tensor, wscale: torch.Tensor, bias: torch.Tensor | None = None,
+                     act: str | None = None, residual: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`gemv_q8` whose x [B, H x D] is the decode attention's output,
+    combined from its split partials in the kernel's x staging (as
+    :func:`gemv_partials`): y [B, N] fp32."""
+    B, _, H, D = p.shape
+    K = H * D
+    N = wq.shape[0]
+    if (wq.dtype != torch.int8 or wq.shape[1] != K or wq.stride(-1) != 1 or wq.stride(0) % 16 or wq.data_ptr() % 16
+            or B > GEMV_MAX_ROWS):
+        raise ValueError(f"gemv_q8_partials: W {tuple(wq.shape)} {wq.dtype} for x [{B}, {K}]")
+    y = torch.empty((B, N), dtype=torch.float32, device=wq.device)
+    sc, _, b, r = _q8_operands(wscale, None, bias, residual, B, N)
+    _lib.check(_lib.lib().nos_gemv_q8_partials(p.ws.data_ptr(), p.ws.numel(), p.NS, p.G, p.G, p.Hkv, D, wq.data_ptr(),
+                                               wq.stride(0), sc.data_ptr(), _ptr(b), _ptr(r),
+                                               r.stride(0) if r is not None else 0, y.data_ptr(), y.stride(0), B, N, K,
+                                               _q8_epi(b, act, r, False), _stream()), "nos_gemv_q8_partials")
+    return y
+
+
+def dequant_q8(wq: torch.Tensor, wscale: torch.Tensor) -> torch.Tensor:
+    """``wq.float() * wscale[:, None]`` as a fresh fp32 [N, K] tensor, bit for bit."""
+    if not wq.is_cuda:
+        return wq.to(torch.float32) * wscale.to(torch.float32)[:, None]
+    N, K = wq.shape
+    if wq.dtype != torch.int8 or wq.stride(-1) != 1 or K % 4 or wq.stride(0) % 4 or wq.data_ptr() % 4:
+        raise ValueError(f"dequant_q8: an int8 [N, K] weight with K % 4 == 0 and 4-byte aligned rows, got "
+                         f"{tuple(wq.shape)} {wq.dtype}")
+    out = torch.empty((N, K), dtype=torch.float32, device=wq.device)
+    sc = wscale.float().contiguous()
+    _lib.check(_lib.lib().nos_dequant_q8(wq.data_ptr(), wq.stride(0), sc.data_ptr(), out.data_ptr(), K, N, K,
+                                         _stream()), "nos_dequant_q8")
+    return out
+
+
+def linear_q8(x: torch.Tensor, wq: torch.Tensor, wscale: torch.Tensor, bias: torch.Tensor | None = None,
+              act: str | None = None, residual: torch.Tensor | None = None, rms_eps: float = 0.0,
+              gamma: torch.Tensor | None = None, glu: bool = False) -> torch.Tensor:
+    """The int8 weight-only linear (:func:`linear_q8_ref`) of fp32 x [..., K]:
+    at most :data:`GEMV_MAX_ROWS` rows on :func:`gemv_q8`; more rows
+    dequantize the weight into a transient fp32 buffer (freed with the
+    call's other intermediates, never cached) for the run-time-split h3
+    product, after the ``rmsnorm`` kernel when there is a prologue.  CPU
+    tensors: the reference."""
+    if not x.is_cuda:
+        return linear_q8_ref(x, wq, wscale, bias, act, residual, rms_eps, gamma, glu)
+    if x.dtype != torch.float32:
+        raise ValueError(f"linear_q8 takes an fp32 x, got {x.dtype}")
+    K, N = x.shape[-1], wq.shape[0]
+    x2 = x.reshape(-1, K)
+    if x2.stride(-1) != 1 or x2.stride(0) % 4 or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.shape[0]
+    shape = (*x.shape[:-1], N // 2 if glu else N)
+    if M <= GEMV_MAX_ROWS and gemv_q8_ok(x2, wq):
+        return gemv_q8(x2, wq, wscale, bias, act, residual, rms_eps, gamma, glu).view(shape)
+    if rms_eps:
+        x2 = rmsnorm(x2, gamma if gamma is not None else torch.ones(K, dtype=torch.float32, device=x.device), rms_eps)
+    r = None if residual is None else residual.reshape(M, N).float().contiguous()
+    gemm_act = act if act in ("gelu", "relu") else None   # the GEMM's epilogue; silu: a pass of its own
+    y = mm(x2, dequant_q8(wq, wscale), b_t=True, bias=bias, act=gemm_act, residual=r if act == gemm_act else None)
+    if glu:
+        return _glu_halves(y).view(shape)
+    if act != gemm_act:
+        y = unary(y, act, torch.float32)
+        if r is not None:
+            y = y + r
+    return y.view(shape)
+
+
+def _glu_halves(y: torch.Tensor) -> torch.Tensor:
+    """silu(gate) * up of the two column halves of a merged [gate; up] product."""
+    h = y.shape[-1] // 2
+    return glu(y[..., :h], y[..., h:], "silu")
+
+
 def set_attention_h3g_kvsplit(n: int) -> None:
     """Key splits of :func:`sdpa` (0 = auto: fill the CU slots)."""
     _lib.check(_lib.lib().nos_attn_h3g_set_kvsplit(int(n)), "nos_attn_h3g_set_kvsplit")
 
 
 __all__ = ["glu", "kv_write", "rotary_at", "sdpa_cache", "pos_update", "argmax", "sample", "sample_row_ref",
-           "sampling_ctl", "philox4x32", "gemv", "gemv_ok", "gemv_partials",
+           "sampling_ctl", "philox4x32", "gemv", "gemv_ok", "gemv_partials", "gemv_q8", "gemv_q8_ok", "gemv_q8_partials",
+           "dequant_q8", "linear_q8", "linear_q8_ref",
            "DecodePartials", "conv2d", "matmul", "sdpa", "linear_rms", "embedding", "rmsnorm", "softmax", "rotary", "conv2d_ref",
            "sdpa_ref", "rope_ref", "rmsnorm_ref", "linear_rms_ref", "set_attention_h3g_kvsplit", "EPI_BIAS_ROW",
            "sdpa_lse", "sdpa_bwd", "sdpa_lse_ref", "sdpa_bwd_ref", "sdpa_bwd_workspace_bytes"]

@@ -20,6 +20,26 @@ def bf16_to_f32(bits: np.ndarray) -> np.ndarray:
     return (bits.astype(np.uint32) << 16).view(np.float32)
 
 
+def quantize_rows_q8(w: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """Symmetric int8 quantization of a weight [N, K], one scale per output row:
+    ``scale = max|row| / 127`` (1.0 for an all-zero row) and
+    ``q = clip(rint(row / scale), -127, 127)``.  Returns (q int8 [N, K], scale
+    fp32 [N]); :func:`dequantize_rows_q8` gives the weight the server computes with."""
+    a = np.ascontiguousarray(w, dtype=np.float32)
+    if a.ndim != 2:
+        raise ValueError(f"quantize_rows_q8 takes a [N, K] weight, got {a.shape}")
+    amax = np.abs(a).max(axis=1) if a.shape[1] else np.zeros(a.shape[0], np.float32)
+    scale = np.where(amax > 0, amax / np.float32(127), np.float32(1)).astype(np.float32)
+    q = np.clip(np.rint(a / scale[:, None]), -127, 127).astype(np.int8)
+    return q, scale
+
+
+def dequantize_rows_q8(q: np.ndarray, scale: np.ndarray) -> np.ndarray:
+    """``q.astype(fp32) * scale[:, None]`` in fp32 (one rounding per element): the
+    weight a ``linear_q8`` node means."""
+    return np.asarray(q).astype(np.float32) * np.asarray(scale, dtype=np.float32)[:, None]
+
+
 class Builder:
     """Assemble a wire program with numpy only (the pod side never imports
     torch).  ``param`` appends a weight to the payload; op methods append
@@ -47,6 +67,22 @@ class Builder:
         self.chunks.append(raw)
         self.offset += len(raw)
         return name
+
+    def param_q8(self, name: str, w_fp32: np.ndarray) -> tuple[str, str]:
+        """An fp32 weight [N, K] stored as int8 rows + fp32 row scales
+        (:func:`quantize_rows_q8`): the params ``name + ".q8"`` (i8) and
+        ``name + ".scale"`` a ``linear_q8`` node takes."""
+        q, scale = quantize_rows_q8(w_fp32)
+        raw = q.tobytes()
+        self.params.append({"name": name + ".q8", "shape": list(q.shape), "dtype": "i8", "offset": self.offset,
+                            "nbytes": len(raw)})
+        self.chunks.append(raw)
+        self.offset += len(raw)
+        pad = -self.offset % 4   # the fp32 params after it stay 4-byte aligned in the payload
+        if pad:
+            self.chunks.append(b"\0" * pad)
+            self.offset += pad
+        return name + ".q8", self.param(name + ".scale", scale)
 
     def state(self, name: str, shape, dtype: str = "fp32") -> str:
         """A state buffer (zero at registration, kept across requests)."""

@@ -93,6 +93,7 @@ class Lowered:
         # build's variants share it -- a compiled program keeping it would keep them alive
         self._derived = None
         self.stats["kernels"] = sum(1 for s in self.steps if s.kind in NATIVE_KINDS)
+        self.stats["q8_linears"] = sum(1 for s in self.steps if s.kind == "linear_q8")
 
     def _memo(self, tag: str, sources: list, extra, make):
         """``make()`` once per recipe: ``tag`` + the identities of the source
@@ -514,7 +515,7 @@ class Lowered:
         output dim ``d``, as (input index, input dim); None: not row-wise in d."""
         if p.kind in UNARY or p.kind == "cast":
             return [(0, d)]
-        if p.kind in ("linear", "layernorm", "rmsnorm"):
+        if p.kind in ("linear", "linear_q8", "layernorm", "rmsnorm"):
             return [(0, d)] if len(self._shape(p.inputs[0])) == r else None
         if p.kind in BINARY:
             plan = []
@@ -791,16 +792,25 @@ class Lowered:
     def _fold_rmsnorm(self, steps: list[_Step]) -> list[_Step]:
         """rmsnorm -> linear (its only consumer, constant weights) becomes one
         ``linear_rms``: gamma folded into the weight, the row statistics in
-        the h3 split pre-pass (ops.tenant.linear_rms)."""
+        the h3 split pre-pass (ops.tenant.linear_rms).  rmsnorm -> ``linear_q8``
+        keeps its int8 weight as it is (per-row scales leave no room for a
+        per-column gamma, and no fp32 copy is made): the step takes ``eps`` and
+        the gamma tensor as one more input, applied in the GEMV's x staging."""
         uses = self._consumers(steps, self.outputs)
         by_out = {s.output: s for s in steps}
-        drop, n = set(), 0
+        drop, n, nq = set(), 0, 0
         for s in steps:
-            if s.kind != "linear" or s.inputs[0] not in by_out:
+            if s.kind not in ("linear", "linear_q8") or s.inputs[0] not in by_out:
                 continue
             rn = by_out[s.inputs[0]]
             if rn.kind != "rmsnorm" or uses.get(rn.output) != 1 or not all(i in self.consts for i in
                                                                               s.inputs[1:] + rn.inputs[1:]):
+                continue
+            if s.kind == "linear_q8":
+                s.inputs = [rn.inputs[0]] + s.inputs[1:] + [rn.inputs[1]]
+                s.attrs = {**s.attrs, "eps": rn.attrs.get("eps", 1e-5), "gamma": True}
+                drop.add(rn.output)
+                nq += 1
                 continue
             w, g = self.consts[s.inputs[1]], self.consts[rn.inputs[1]]
             base = f"{s.output}::rms"
@@ -811,7 +821,7 @@ class Lowered:
             s.attrs = {"act": s.attrs.get("act"), "eps": rn.attrs.get("eps", 1e-5)}
             drop.add(rn.output)
             n += 1
-        self.stats["rmsnorm_folded"] = n
+        self.stats["rmsnorm_folded"], self.stats["q8_rms_prologue"] = n, nq
         return [s for s in steps if s.output not in drop]
 
     def _fuse_epilogues(self, steps: list[_Step]) -> list[_Step]:
@@ -824,7 +834,8 @@ class Lowered:
             orig = list(s.inputs)
             s.inputs = [rename.get(i, i) for i in s.inputs]
             src = by_out.get(s.inputs[0]) if s.inputs else None
-            if (s.kind in ("gelu", "relu") and src is not None and src.kind in ("linear", "linear_ln", "linear_rms")
+            if (s.kind in ("gelu", "relu") and src is not None
+                    and src.kind in ("linear", "linear_ln", "linear_rms", "linear_q8")
                     and uses.get(src.output) == 1 and not src.attrs.get("act") and "residual" not in src.attrs):
                 src.attrs["act"] = s.kind
                 rename[s.output] = src.output
@@ -844,7 +855,7 @@ class Lowered:
                 a, b = s.inputs
                 for prod, other in ((a, b), (b, a)):
                     p = by_out.get(prod)
-                    if (p is not None and p.kind in ("linear", "conv2d") and uses.get(prod) == 1
+                    if (p is not None and p.kind in ("linear", "conv2d", "linear_q8") and uses.get(prod) == 1
                             and "residual" not in p.attrs
                             and self._shape(prod) == self._shape(s.output) == self._shape(other)
                             and self._dtype(prod) == self._dtype(other) and other != prod):
@@ -955,16 +966,16 @@ class Lowered:
 
     def _fuse_gemv_glu(self, steps: list[_Step]) -> list[_Step]:
         """Decode rows (at most 8, known statically): ``glu(silu)`` of the two
-        column halves of a merged gate-up ``linear_rms`` becomes that GEMV's
-        epilogue (each wave computes a gate and its up column), one launch
-        instead of two."""
+        column halves of a merged gate-up ``linear_rms`` (or ``linear_q8``)
+        becomes that GEMV's epilogue (each wave computes gate columns and their
+        up columns), one launch instead of two."""
         from ...ops.tenant import GEMV_MAX_ROWS
 
         if not self.gpu:
             return steps
         uses = self._consumers(steps, self.outputs)
         by_out = {s.output: s for s in steps}
-        drop, n = set(), 0
+        drop, n, nq = set(), 0, 0
         for s in steps:
             if s.kind != "glu" or s.attrs.get("op") != "silu":
                 continue
@@ -973,8 +984,10 @@ class Lowered:
                 continue
             lin = by_out.get(a.inputs[0])
             shp = tuple(self._shape(lin.output)) if lin is not None else ()
-            if (lin is None or lin.kind != "linear_rms" or lin.attrs.get("act") or len(lin.inputs) > 2
-                    or uses.get(lin.output) != 2 or uses.get(a.output) != 1 or uses.get(b.output) != 1
+            q8 = lin is not None and lin.kind == "linear_q8"
+            plain = 3 + bool(lin.attrs.get("gamma")) if q8 else 2      # its inputs without a bias or a residual
+            if (lin is None or lin.kind not in ("linear_rms", "linear_q8") or lin.attrs.get("act")
+                    or len(lin.inputs) > plain or uses.get(lin.output) != 2 or uses.get(a.output) != 1 or uses.get(b.output) != 1
                     or math.prod(shp[:-1]) > GEMV_MAX_ROWS or shp[-1] % 2
                     or any(t.attrs.get("dim") not in (-1, len(shp) - 1) for t in (a, b))
                     or (a.attrs["start"], a.attrs["end"], b.attrs["start"], b.attrs["end"])
@@ -987,8 +1000,8 @@ class Lowered:
             for t in steps:
                 t.inputs = [rename.get(i, i) for i in t.inputs]
             self.outputs = [rename.get(o, o) for o in self.outputs]
-            n += 1
-        self.stats["gemv_glu_fused"] = n
+            n, nq = n + (not q8), nq + q8
+        self.stats["gemv_glu_fused"], self.stats["q8_glu_fused"] = n, nq
         return [s for s in steps if id(s) not in drop]
 
     def _merge_kv_writes(self, steps: list[_Step]) -> list[_Step]:
@@ -1086,7 +1099,7 @@ class Lowered:
         for t in steps:
             for i in t.inputs:
                 by_input.setdefault(i, []).append(t)
-        drop, n = set(), 0
+        drop, n, nq = set(), 0, 0
         for s in steps:
             if s.kind != "sdpa_cache" or s.attrs.get("sync") or uses.get(s.output) != 1:
                 continue
@@ -1100,15 +1113,16 @@ class Lowered:
             if rs[0] != shp[0] or math.prod(rs[1:]) != shp[2] * shp[3] or rs[-1] != shp[2] * shp[3]:
                 continue
             lin = by_input.get(r.output, [None])[0]
-            if (lin is None or lin.kind != "linear" or lin.inputs[0] != r.output or lin.attrs.get("out_into")
+            if (lin is None or lin.kind not in ("linear", "linear_q8") or lin.inputs[0] != r.output
+                    or lin.attrs.get("gamma") or lin.attrs.get("glu") or lin.attrs.get("out_into")
                     or lin.attrs.get("row_stats") or lin.attrs.get("planes_out") or lin.attrs.get("act") == "glu"):
                 continue
             s.attrs = {**s.attrs, "partials": True}
             lin.inputs = [s.output] + lin.inputs[1:]
             lin.attrs = {**lin.attrs, "x_partials": True}
             drop.add(id(r))
-            n += 1
-        self.stats["decode_combines_into_gemv"] = n
+            n, nq = n + (lin.kind == "linear"), nq + (lin.kind == "linear_q8")
+        self.stats["decode_combines_into_gemv"], self.stats["q8_combines_into_gemv"] = n, nq
         return [t for t in steps if id(t) not in drop]
 
     def _fuse_argmax_pos(self, steps: list[_Step]) -> list[_Step]:
@@ -1257,5 +1271,5 @@ class Lowered:
         if v is not None:
             return v.dtype
         t = str(self.consts[name].dtype)  # a constant: its wire name, as program values carry
-        return {"torch.float32": "fp32", "torch.bfloat16": "bf16", "torch.int32": "i32"}.get(t, t)
+        return {"torch.float32": "fp32", "torch.bfloat16": "bf16", "torch.int32": "i32", "torch.int8": "i8"}.get(t, t)
 

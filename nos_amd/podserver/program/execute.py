@@ -91,6 +91,16 @@ class CompiledProgram(Lowered):
             elif k == "linear_rms":
                 y = T.linear_rms(a[0], a[1], a[2] if len(a) > 2 else None, act=s.attrs.get("act"), eps=s.attrs["eps"],
                                  glu=bool(s.attrs.get("glu")))
+            elif k == "linear_q8":   # inputs: x, wq, wscale, [bias], [gamma], [residual]
+                res = a.pop() if s.attrs.get("residual") else None
+                g = a.pop() if s.attrs.get("gamma") else None
+                if s.attrs.get("x_partials"):   # x = the decode attention's split partials
+                    y = T.gemv_q8_partials(a[0], a[1], a[2], a[3] if len(a) > 3 else None, act=s.attrs.get("act"),
+                                           residual=res).reshape(self._shape(s.output))
+                else:
+                    y = T.linear_q8(a[0], a[1], a[2], a[3] if len(a) > 3 else None, act=s.attrs.get("act"),
+                                    residual=res, rms_eps=float(s.attrs.get("eps", 0.0)), gamma=g,
+                                    glu=bool(s.attrs.get("glu")))
             elif k == "matmul":
                 y = T.matmul(a[0], a[1])
             elif k == "softmax":

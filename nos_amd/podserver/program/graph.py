@@ -35,6 +35,15 @@ def _workspace(node: Node, ins: list[Value], out: Value, f32_math: str) -> int:
         p = out.numel // (n * oc)
         kp = -(-(cg * kh * kw) // 32) * 32
         return n * (c // cg) * p * (kp * 4 + 4) + ins[0].numel * 4 + out.numel * 4
+    if op == "linear_q8":
+        # decode rows run on the int8 GEMV; more dequantize the weight into a transient fp32
+        # buffer for the run-time-split h3 product (ops.tenant.linear_q8)
+        k = ins[0].shape[-1]
+        m, n = ins[0].numel // k, ins[1].shape[0]
+        if m <= 8:
+            return 0
+        kp = -(-k // 32) * 32
+        return n * k * 4 + (m + n) * kp * 12 + out.numel * 4
     if op == "matmul":
         k = ins[0].shape[-1]
         kp = -(-k // 32) * 32
@@ -168,7 +177,7 @@ class Program:
         buf = memoryview(self.payload)
         for name, v in self.params.items():
             off, nb = self.param_layout[name]
-            raw = np.frombuffer(buf[off:off + nb], dtype=np.float32 if v.dtype == "fp32" else np.int16)
+            raw = np.frombuffer(buf[off:off + nb], dtype={"fp32": np.float32, "i8": np.int8}.get(v.dtype, np.int16))
             t = torch.from_numpy(raw.copy()).view(v.shape)
             if v.dtype == "bf16":
                 t = t.view(torch.bfloat16)

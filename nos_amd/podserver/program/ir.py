@@ -6,7 +6,9 @@ import math
 from dataclasses import dataclass, field
 
 FORMAT = "nos-amd.program/v1"
-WIRE_DTYPES = {"fp32": 4, "bf16": 2, "i32": 4}   # i32: token ids (an input only; consumed by embedding)
+# i32: token ids (an input only; consumed by embedding); i8: quantized weights (a param only; linear_q8's input 1)
+WIRE_DTYPES = {"fp32": 4, "bf16": 2, "i32": 4, "i8": 1}
+PARAM_DTYPES = ("fp32", "bf16", "i8")
 FLOAT_DTYPES = ("fp32", "bf16")
 MAX_NODES = 8192
 MAX_PARAMS = 8192
@@ -110,7 +112,9 @@ OPS = ("linear", "layernorm", "attention", *BINARY, *UNARY, "cat", "slice", "res
        "cast", "interpolate",
        # general tenants: conv nets and decoder LLMs (nos_amd/ops/tenant.py)
        "conv2d", "batchnorm", "max_pool2d", "avg_pool2d", "mean", "sum", "matmul", "softmax", "embedding",
-       "rmsnorm", "rotary", "sdpa")
+       "rmsnorm", "rotary", "sdpa",
+       # int8 weight-only linear: act(x @ (wq.float() * wscale[:, None]).T + bias), fp32 math
+       "linear_q8")
 # stateful decoding (round 6): ops over state buffers that persist across a
 # tenant's requests (a K / V cache, a position counter).  STATE_WRITERS update
 # their first input IN PLACE and return its new version (the validator makes
@@ -120,15 +124,16 @@ STATE_WRITERS = ("kv_write", "pos_add", "pos_set")
 STATE_DTYPES = ("fp32", "bf16", "i32")
 MAX_STATE = 1024
 OPS = OPS + STATE_OPS
-NEVER_FOLD = ("attention", "sdpa", *STATE_OPS)
+# linear_q8: folding it would materialise the fp32 weight the format exists to avoid
+NEVER_FOLD = ("attention", "sdpa", "linear_q8", *STATE_OPS)
 # step kinds that run a gfx950 kernel of libnos_hip.so (CompiledProgram.stats["kernels"])
 NATIVE_KINDS = ("linear", "linear_ln", "linear_rms", "ln_qkv_attention", "attention", "layernorm", "conv2d", "matmul",
                 "softmax", "embedding", "rmsnorm", "rotary", "sdpa", "patches", "unary", "kv_write", "sdpa_cache",
-                "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu")
+                "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu", "linear_q8")
 GEMM_OPS = ("linear", "conv2d")
 
 
 def torch_dtype(dt: str):
     import torch
 
-    return {"fp32": torch.float32, "bf16": torch.bfloat16, "i32": torch.int32}[dt]
+    return {"fp32": torch.float32, "bf16": torch.bfloat16, "i32": torch.int32, "i8": torch.int8}[dt]

@@ -18,6 +18,10 @@ def _eager(op: str, args: list, attrs: dict, ref: bool = False):
         y = F.linear(args[0], args[1], args[2] if len(args) > 2 else None)
         act = attrs.get("act")
         return F.gelu(y) if act == "gelu" else (F.relu(y) if act == "relu" else y)
+    if op == "linear_q8":
+        from ...ops import tenant as T
+
+        return T.linear_q8(args[0], args[1], args[2], args[3] if len(args) > 3 else None, act=attrs.get("act"))
     if op == "layernorm":
         x = args[0]
         return F.layer_norm(x, (x.shape[-1],), args[1], args[2], attrs.get("eps", 1e-5))

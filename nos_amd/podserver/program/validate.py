@@ -7,7 +7,7 @@ import math
 
 from .graph import Program
 from .ir import (FLOAT_DTYPES, FORMAT, MAX_NUMEL, MAX_PARAMS, MAX_NODES, MAX_RANK, MAX_STATE, MAX_VARIANTS, OPS,
-                 STATE_DTYPES, STATE_WRITERS, ACTS, BINARY,
+                 PARAM_DTYPES, STATE_DTYPES, STATE_WRITERS, ACTS, BINARY,
                  INTERP_MODES, UNARY, WIRE_DTYPES, Node, ProgramError, Value, _broadcast, _eps, _int, _name,
                  _pair, _req, _shape)
 
@@ -43,6 +43,27 @@ def _infer(node: Node, ins: list[Value], gpu: bool) -> tuple[tuple[int, ...], st
             k_mult = 64 if dt == "bf16" else 32
             _req(x.shape[-1] % k_mult == 0, f"{what}: the {dt} GEMM kernels need K % {k_mult} == 0, K = {x.shape[-1]}")
         return x.shape[:-1] + (w.shape[0],), dt
+    if op == "linear_q8":
+        # weight-only int8: wq [N, K] i8 with one fp32 scale per output row; fp32 x, bias and result
+        only("act")
+        arity(3, 4)
+        x, w, sc = ins[0], ins[1], ins[2]
+        _req(w.dtype == "i8" and w.kind == "param" and len(w.shape) == 2,
+             f"{what}: the weight must be an i8 [N, K] param, got {w.kind} {w.dtype} {list(w.shape)}")
+        _req(x.dtype == "fp32", f"{what}: x must be fp32 (int8 weights are an fp32 tenant's storage format; "
+             f"a bf16 x is not taken), got {x.dtype}")
+        _req(len(x.shape) >= 1 and x.shape[-1] == w.shape[1],
+             f"{what}: x [..., K] and weight [N, K] required, got {x.shape} and {w.shape}")
+        _req(sc.dtype == "fp32" and sc.shape == (w.shape[0],),
+             f"{what}: wscale must be fp32 [{w.shape[0]}], got {sc.dtype} {list(sc.shape)}")
+        if len(ins) == 4:
+            _req(ins[3].dtype == "fp32" and ins[3].shape == (w.shape[0],),
+                 f"{what}: bias must be fp32 [{w.shape[0]}], got {ins[3].dtype} {list(ins[3].shape)}")
+        _req(a.get("act") in ACTS, f"{what}: act must be one of {ACTS}")
+        if gpu:
+            _req(x.shape[-1] % 32 == 0, f"{what}: the int8 GEMV and its h3 fallback need K % 32 == 0, "
+                 f"K = {x.shape[-1]}")
+        return x.shape[:-1] + (w.shape[0],), "fp32"
     if op == "layernorm":
         only("eps")
         arity(3, 3)
@@ -383,7 +404,7 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     for d in ins:
         _req(isinstance(d, dict), "inputs must be objects")
         dt = d.get("dtype", "fp32")
-        _req(dt in WIRE_DTYPES, f"input dtype must be one of {sorted(WIRE_DTYPES)}")
+        _req(dt in WIRE_DTYPES and dt != "i8", f"input dtype must be one of {sorted(set(WIRE_DTYPES) - {'i8'})}")
         v = Value(_name(d.get("name"), "input name"), _shape(d.get("shape"), "input shape"), dt, "input")
         define(v)
         inputs.append(v)
@@ -395,7 +416,7 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     for d in ps:
         _req(isinstance(d, dict), "params must be objects")
         dt = d.get("dtype", "fp32")
-        _req(dt in FLOAT_DTYPES, f"param dtype must be one of {FLOAT_DTYPES}")
+        _req(dt in PARAM_DTYPES, f"param dtype must be one of {PARAM_DTYPES}")
         v = Value(_name(d.get("name"), "param name"), _shape(d.get("shape"), "param shape"), dt, "param")
         off, nb = _int(d.get("offset"), "param offset", 0), _int(d.get("nbytes"), "param nbytes", 0)
         _req(nb == v.nbytes, f"param {v.name!r}: nbytes {nb} != {v.nbytes} for {v.shape} {dt}")
@@ -440,6 +461,9 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
         attrs = d.get("attrs") or {}
         _req(isinstance(attrs, dict), "attrs must be an object")
         n = Node(op, list(refs), _name(d.get("output"), "node output"), dict(attrs))
+        for k, r in enumerate(refs):   # an i8 value is a quantized weight: only linear_q8 reads it, as its weight
+            _req(values[r].dtype != "i8" or (op == "linear_q8" and k == 1),
+                 f"node {n.output!r} ({op}): input {r!r} is an i8 param; only linear_q8 takes one, as its weight")
         shape, dt = _infer(n, [values[r] for r in refs], gpu)
         _req(math.prod(shape) <= MAX_NUMEL, f"node {n.output!r}: output too large")
         if op in STATE_WRITERS:
@@ -459,6 +483,7 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     _req(isinstance(outs, list) and outs and all(isinstance(o, str) and o in values for o in outs),
          "outputs must name defined values")
     _req(not any(o in root_of for o in outs), "a state (or a version of one) cannot be an output: it is mutable")
+    _req(not any(values[o].dtype == "i8" for o in outs), "an i8 param cannot be an output")
     return Program(name, inputs, params, layout, nodes, list(outs), values, payload, state=state,
                    state_root={k: v for k, v in root_of.items() if k != v}, sampling_state=sampling)
 
