@@ -249,6 +249,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
       x0 = y0;
       x1 = y1;
     }
+    if (CBF) {  // a bf16 cache holds the row rounded: the step attends what every later read of the cache sees
+      x0 = nos::bf16_to_f32(nos::f32_to_bf16(x0));
+      x1 = nos::bf16_to_f32(nos::f32_to_bf16(x1));
+    }
   };
   // the split's K and V rows are loaded into registers first, every load of both in flight
   // at once; the fresh-row stores, the q staging and the scores overlap their latency (a
@@ -284,7 +288,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
     }
   }
   // the fresh rows this split attends come from the registers' source, not the cache
-  // (its stores above may still be in flight): staged over the cache's rows
+  // (its stores above may still be in flight): staged over the cache's rows, at the cache's
+  // precision (fresh_row)
   auto overlay = [&](bool isk) {
     if (!fresh) return;
     __syncthreads();
