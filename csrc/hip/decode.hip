@@ -19,6 +19,9 @@
 //    query head of the group (grouped-query) served from one read of the
 //    split's keys and values, staged through LDS with 16-byte loads;
 //    nos_attn_decode_combine merges the splits (log-sum-exp);
+//  * nos_kv_write_q8 / nos_attn_decode_q8 -- the two over int8 caches (D int8 values
+//    and one fp32 scale per row): the write quantizes the rows, the attention
+//    dequantizes them as it stages a split and is the fp32 cache's code after that;
 //  * nos_pos_update -- pos += n / pos = n;
 //  * nos_argmax -- greedy next tokens, one wave per row;
 //  * nos_sample -- sampled next tokens (temperature, top-k, top-p, seed read
@@ -76,6 +79,42 @@ __device__ __forceinline__ float4 cvt4(uint4 r, int bf) {
   return float4{__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w)};
 }
 
+// ------------------------------------------------------------------ int8 K / V cache rows
+// A cache row (one (sequence, position, K/V head) vector of D values) of an int8 cache is D int8
+// values and one fp32 scale, the int8 weights' rule on the row in fp32: scale = max|row| / 127 (1 for
+// an all-zero row), q = clip(rint(row / scale), -127, 127); the value the cache holds is (float)q x
+// scale, one rounding.  A wave quantizes a row: lane d < D / 2 holds the rotate_half pair (d, d + D/2).
+__device__ __forceinline__ float4 q8_cvt4(unsigned v) {
+  return float4{(float)(int)(signed char)(v & 255u), (float)(int)(signed char)((v >> 8) & 255u),
+                (float)(int)(signed char)((v >> 16) & 255u), (float)(int)(signed char)(v >> 24)};
+}
+
+// the wave's row (x0, x1 per lane; 0 in the lanes past D / 2) -> its scale and this lane's two values
+__device__ __forceinline__ float q8_row(float x0, float x1, int& q0, int& q1) {
+  const float amax = nos::wave_max(fmaxf(fabsf(x0), fabsf(x1)));
+  const float s = amax > 0.f ? amax / 127.f : 1.f;
+  q0 = (int)fminf(fmaxf(rintf(x0 / s), -127.f), 127.f);
+  q1 = (int)fminf(fmaxf(rintf(x1 / s), -127.f), 127.f);
+  return s;
+}
+
+// the row's D bytes leave the wave as D / 4 dword stores: lane l < D / 4 gathers elements 4 l .. 4 l + 3
+// (element e sits in lane e % (D / 2), half e / (D / 2)) from the lanes' packed pairs; lane 0 the scale
+template <int D>
+__device__ __forceinline__ void q8_row_store(signed char* __restrict__ row, float* __restrict__ scale, float s, int q0,
+                                             int q1, int lane) {
+  const int pk = (q0 & 255) | ((q1 & 255) << 8);
+  unsigned w = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int e = (4 * lane + i) % D;
+    const int t = __shfl(pk, e % (D / 2), 64);
+    w |= (unsigned)((e >= D / 2 ? t >> 8 : t) & 255) << (8 * i);
+  }
+  if (lane < D / 4) reinterpret_cast<unsigned*>(row)[lane] = w;
+  if (lane == 0) *scale = s;
+}
+
 // ------------------------------------------------------------------ kv_write / rotary at device positions
 // one thread per (b, s, h, d < D/2) pair (d, d + D/2): the rotate_half pair
 // a fused rotary needs; without tables it just copies both elements
@@ -121,6 +160,66 @@ __global__ __launch_bounds__(256) void kv_write_kernel(const void* __restrict__ 
   const long long co = (((long long)b * L + p) * H + h) * D;
   stf(cache, co + d, x0, cbf);
   stf(cache, co + d + hd, x1, cbf);
+}
+
+// kv_write into an int8 cache: one wave per (b, s, h) row -- rotate (K), the row's scale across the
+// lanes, quantize, D / 4 dword stores and the scale (q8_row_store); deq (optional, [B, S, H, D] fp32):
+// the row as the cache now holds it, for a prefill that attends these rows with the flash kernel
+struct KvPairQ8 {
+  const float* x2;
+  int ldx2;
+  long long bsx2;
+  signed char* cache2;
+  float* scales2;
+  float* deq2;
+};
+
+template <int D>
+__global__ __launch_bounds__(256) void kv_write_q8_kernel(const float* __restrict__ x, int ldx, long long bsx,
+                                                          signed char* __restrict__ cache, float* __restrict__ scales,
+                                                          float* __restrict__ deq, const int* __restrict__ pos,
+                                                          const float* __restrict__ cs, const float* __restrict__ sn,
+                                                          int R, int B, int S, int H, int L, KvPairQ8 v2) {
+  if (blockIdx.y == 1) {  // the V half: its own rows, no rotation
+    x = v2.x2;
+    ldx = v2.ldx2;
+    bsx = v2.bsx2;
+    cache = v2.cache2;
+    scales = v2.scales2;
+    deq = v2.deq2;
+    cs = sn = nullptr;
+  }
+  constexpr int hd = D / 2;
+  const int lane = threadIdx.x & 63;
+  long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);  // the wave's row
+  if (r >= (long long)B * S * H) return;
+  const int h = (int)(r % H);
+  r /= H;
+  const int s = (int)(r % S), b = (int)(r / S);
+  const int p = pos[b] + s;
+  if (p < 0 || p >= L) return;  // past the cache: dropped (the whole wave)
+  float x0 = 0.f, x1 = 0.f;
+  if (lane < hd) {
+    const long long xo = b * bsx + (long long)s * ldx + (long long)h * D;
+    x0 = x[xo + lane];
+    x1 = x[xo + lane + hd];
+    if (cs != nullptr) {
+      const long long t = (long long)min(p, R - 1) * D;
+      const float y0 = fmaf(x0, cs[t + lane], -x1 * sn[t + lane]);
+      const float y1 = fmaf(x1, cs[t + lane + hd], x0 * sn[t + lane + hd]);
+      x0 = y0;
+      x1 = y1;
+    }
+  }
+  int q0, q1;
+  const float sc = q8_row(x0, x1, q0, q1);
+  const long long row = ((long long)b * L + p) * H + h;
+  q8_row_store<D>(cache + row * D, scales + row, sc, q0, q1, lane);
+  if (deq != nullptr && lane < hd) {
+    const long long yo = (((long long)b * S + s) * H + h) * D;
+    deq[yo + lane] = (float)q0 * sc;
+    deq[yo + lane + hd] = (float)q1 * sc;
+  }
 }
 
 __global__ __launch_bounds__(256) void rotary_pos_kernel(const void* __restrict__ x, int ldx, long long bsx,
@@ -211,18 +310,35 @@ __device__ __forceinline__ void decode_combine_last(const float* __restrict__ ws
   if (tid == 0) atomicExch(&sync[bk], 0);
 }
 
+// the row scales [B, L, Hkv] of int8 caches (CBF == 2): a kernel argument only of that instantiation
+template <int CBF>
+struct CacheScales {};
+template <>
+struct CacheScales<2> {
+  float* k;
+  float* v;
+};
+
+// CBF: the cache kind -- 0 fp32, 1 bf16, 2 int8 rows with a scale each (dequantized as they are staged
+// into the fp32 LDS tile: a quarter of the fp32 cache's bytes from HBM, the same arithmetic after it)
 template <int D, int CBF>
 __global__ __launch_bounds__(256) void attn_decode_kernel(
     const void* __restrict__ q, int qbf, int ldq, long long bsq, const void* __restrict__ kc,
     const void* __restrict__ vc, int /*cbf = CBF*/, const int* __restrict__ pos, const float* __restrict__ cs,
     const float* __restrict__ sn, int Rtab, float* __restrict__ ws, int B, int H, int Hkv, int Sq, int q0, int L,
-    int NS, float scale, Fresh fr, int* __restrict__ sync, void* __restrict__ o, int obf, int Sq_total) {
+    int NS, float scale, Fresh fr, int* __restrict__ sync, void* __restrict__ o, int obf, int Sq_total,
+    CacheScales<CBF> csc) {
   constexpr int cbf = CBF;   // the cache dtype fixed at compile time: no per-load dtype branch
   constexpr int DP = D + 4;  // padded LDS row (16-byte reads of consecutive rows hit distinct banks)
   __shared__ __attribute__((aligned(16))) float qs[MAXR * D];
   __shared__ __attribute__((aligned(16))) float kv[KC * DP];
   __shared__ float sc[MAXR * KC];
   __shared__ float mrow[MAXR], lrow[MAXR];
+  float* rsc = nullptr;  // int8 caches: the split's K row scales, then its V row scales
+  if constexpr (CBF == 2) {
+    __shared__ float rsc_[2 * KC];
+    rsc = rsc_;
+  }
   const int G = H / Hkv, R = G * Sq;
   const int split = blockIdx.x % NS, bk = blockIdx.x / NS;
   const int kvh = bk % Hkv, b = bk / Hkv;
@@ -249,32 +365,66 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
       x0 = y0;
       x1 = y1;
     }
-    if (CBF) {  // a bf16 cache holds the row rounded: the step attends what every later read of the cache sees
+    if (CBF == 1) {  // a bf16 cache holds the row rounded: the step attends what every later read of the cache sees
       x0 = nos::bf16_to_f32(nos::f32_to_bf16(x0));
       x1 = nos::bf16_to_f32(nos::f32_to_bf16(x1));
     }
+  };
+  // an int8 cache holds the row quantized, which takes the row's maximum: one wave per fresh row,
+  // lane d < D / 2 its pair; every lane gets the scale
+  auto fresh_row_q8 = [&](int t, bool isk, int& q0_, int& q1_) {
+    float x0 = 0.f, x1 = 0.f;
+    if (lane < D / 2) fresh_row(t, lane, isk, x0, x1);
+    return q8_row(x0, x1, q0_, q1_);
   };
   // the split's K and V rows are loaded into registers first, every load of both in flight
   // at once; the fresh-row stores, the q staging and the scores overlap their latency (a
   // fresh row's stale cache value is replaced by the overlay below)
   const long long cbase = ((long long)b * L + k0) * cstride + (long long)kvh * D;
-  constexpr int PER = KC * (D / 4) / 256;
-  static_assert(PER * 256 == KC * (D / 4), "whole float4 pieces per thread");
+  // a thread's piece: 4 elements (16 bytes of fp32, 8 of bf16), or 16 bytes = 16 values of an int8 row
+  constexpr int EPP = CBF == 2 ? 16 : 4;
+  constexpr int PER = KC * (D / EPP) / 256;
+  static_assert(PER * 256 == KC * (D / EPP), "whole pieces per thread");
   uint4 kr[PER], vr[PER];
+  float rs = 0.f;  // int8: thread j < KC the scale of K row j, thread KC + j of V row j
   const bool live = nk > 0 && p0 >= 0;
   if (live) {
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      const int e = tid + 256 * u, j = e / (D / 4), d4 = (e % (D / 4)) * 4;
-      kr[u] = j < nk ? ld4raw(kc, cbase + j * cstride + d4, cbf) : uint4{0u, 0u, 0u, 0u};
+    if constexpr (CBF == 2) {
+      const int j = tid & (KC - 1);
+      if (j < nk) rs = (tid < KC ? csc.k : csc.v)[((long long)b * L + k0 + j) * Hkv + kvh];
     }
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
-      const int e = tid + 256 * u, j = e / (D / 4), d4 = (e % (D / 4)) * 4;
-      vr[u] = j < nk ? ld4raw(vc, cbase + j * cstride + d4, cbf) : uint4{0u, 0u, 0u, 0u};
+      const int e = tid + 256 * u, j = e / (D / EPP), d4 = (e % (D / EPP)) * EPP;
+      if constexpr (CBF == 2)
+        kr[u] = j < nk ? *reinterpret_cast<const uint4*>(static_cast<const signed char*>(kc) + cbase + j * cstride + d4)
+                       : uint4{0u, 0u, 0u, 0u};
+      else
+        kr[u] = j < nk ? ld4raw(kc, cbase + j * cstride + d4, cbf) : uint4{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int e = tid + 256 * u, j = e / (D / EPP), d4 = (e % (D / EPP)) * EPP;
+      if constexpr (CBF == 2)
+        vr[u] = j < nk ? *reinterpret_cast<const uint4*>(static_cast<const signed char*>(vc) + cbase + j * cstride + d4)
+                       : uint4{0u, 0u, 0u, 0u};
+      else
+        vr[u] = j < nk ? ld4raw(vc, cbase + j * cstride + d4, cbf) : uint4{0u, 0u, 0u, 0u};
     }
   }
-  if (fresh) {
+  if constexpr (CBF == 2) {
+    if (fresh) {
+      for (int r = wid; r < 2 * fr.n; r += 4) {  // wave-uniform: the whole wave takes or skips a row
+        const int isv = r >= fr.n, t = isv ? r - fr.n : r, jabs = pos[b] + t;
+        if (jabs < k0 || jabs >= k0 + KC || jabs >= L) continue;
+        int q0_, q1_;
+        const float s = fresh_row_q8(t, !isv, q0_, q1_);
+        const long long row = ((long long)b * L + jabs) * Hkv + kvh;
+        q8_row_store<D>(static_cast<signed char*>(isv ? fr.vc : fr.kc) + row * D, (isv ? csc.v : csc.k) + row, s, q0_,
+                        q1_, lane);
+      }
+    }
+  } else if (fresh) {
     for (int e = tid; e < 2 * fr.n * (D / 2); e += 256) {
       const int isv = e >= fr.n * (D / 2), ee = isv ? e - fr.n * (D / 2) : e;
       const int t = ee / (D / 2), d = ee % (D / 2), jabs = pos[b] + t;
@@ -293,6 +443,19 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   auto overlay = [&](bool isk) {
     if (!fresh) return;
     __syncthreads();
+    if constexpr (CBF == 2) {  // what the stores above put into the cache, dequantized
+      for (int t = wid; t < fr.n; t += 4) {
+        const int j = pos[b] + t - k0;
+        if (j < 0 || j >= nk) continue;
+        int q0_, q1_;
+        const float s = fresh_row_q8(t, isk, q0_, q1_);
+        if (lane < D / 2) {
+          kv[j * (D + 4) + lane] = (float)q0_ * s;
+          kv[j * (D + 4) + lane + D / 2] = (float)q1_ * s;
+        }
+      }
+      return;
+    }
     for (int e = tid; e < fr.n * (D / 2); e += 256) {
       const int t = e / (D / 2), d = e % (D / 2), j = pos[b] + t - k0;
       if (j < 0 || j >= nk) continue;
@@ -327,14 +490,29 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
     qs[r * D + d + D / 2] = x1 * scale;
   }
   // the split's rows -> LDS from the registers loaded at the start (rows past nk zero)
-  auto stage = [&](const uint4 (&v)[PER]) {
+  // (int8: each value times its row's scale, rsc + sbase; rows past nk have zero bytes and a zero scale)
+  auto stage = [&](const uint4 (&v)[PER], int sbase) {
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
-      const int e = tid + 256 * u, j = e / (D / 4), d4 = (e % (D / 4)) * 4;
-      *reinterpret_cast<float4*>(&kv[j * DP + d4]) = cvt4(v[u], cbf);
+      const int e = tid + 256 * u, j = e / (D / EPP), d4 = (e % (D / EPP)) * EPP;
+      if constexpr (CBF == 2) {
+        const float s = rsc[sbase + j];
+        const unsigned wd[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float4 f = q8_cvt4(wd[i]);
+          *reinterpret_cast<float4*>(&kv[j * DP + d4 + 4 * i]) = float4{f.x * s, f.y * s, f.z * s, f.w * s};
+        }
+      } else {
+        *reinterpret_cast<float4*>(&kv[j * DP + d4]) = cvt4(v[u], cbf);
+      }
     }
   };
-  stage(kr);
+  if constexpr (CBF == 2) {
+    rsc[tid] = rs;
+    __syncthreads();
+  }
+  stage(kr, 0);
   overlay(true);
   __syncthreads();
   // scores: thread -> key j, rows of one parity
@@ -386,7 +564,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
     }
   }
   __syncthreads();  // every wave is done with the keys
-  stage(vr);
+  stage(vr, KC);
   overlay(false);
   __syncthreads();
   // P V: thread -> column d, rows of one residue
@@ -970,11 +1148,6 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ x, i
 // leave no room to fold it into W) multiplies x on its way into LDS.
 constexpr int Q8_R = 4;   // weight rows per wave: 16 per workgroup pass (GLU: 8 gate + 8 up)
 
-__device__ __forceinline__ float4 q8_cvt4(unsigned v) {
-  return float4{(float)(int)(signed char)(v & 255u), (float)(int)(signed char)((v >> 8) & 255u),
-                (float)(int)(signed char)((v >> 16) & 255u), (float)(int)(signed char)(v >> 24)};
-}
-
 template <int M, int KU>
 __global__ __launch_bounds__(256) void gemv_q8_kernel(const float* __restrict__ x, int ldx,
                                                       const signed char* __restrict__ w, int ldw,
@@ -1176,6 +1349,33 @@ NOS_API int nos_kv_write(const void* x, int xbf, int ldx, long long bsx, void* c
   return (int)hipGetLastError();
 }
 
+// nos_kv_write into int8 caches: x fp32, cache [B, L, H, D] int8 (16-byte aligned) with its row scales
+// [B, L, H] fp32, D = 64 / 128; deq (or null): [B, S, H, D] fp32 contiguous, the rows as the cache holds
+// them.  x2 / cache2 / scales2 / deq2: the unrotated second write of the launch (V).
+NOS_API int nos_kv_write_q8(const float* x, int ldx, long long bsx, void* cache, float* scales, float* deq,
+                            const int* pos, const float* cos_t, const float* sin_t, int R, int B, int S, int H, int D,
+                            int L, const float* x2, int ldx2, long long bsx2, void* cache2, float* scales2,
+                            float* deq2, hipStream_t stream) {
+  if (B <= 0 || S <= 0 || H <= 0 || (D != 64 && D != 128) || L <= 0 || S > L || ldx < H * D || !x || !cache ||
+      !scales || !pos || (B > 1 && bsx < (long long)(S - 1) * ldx + H * D) || ((uintptr_t)cache & 15) ||
+      ((uintptr_t)scales & 3) || ((uintptr_t)x & 3) || ((uintptr_t)deq & 3) ||
+      ((cos_t == nullptr) != (sin_t == nullptr)) || (cos_t && R <= 0) || ((x2 == nullptr) != (cache2 == nullptr)) ||
+      ((x2 == nullptr) != (scales2 == nullptr)) || (!x2 && deq2) ||
+      (x2 && (ldx2 < H * D || (B > 1 && bsx2 < (long long)(S - 1) * ldx2 + H * D) || ((uintptr_t)cache2 & 15) ||
+              ((uintptr_t)scales2 & 3) || ((uintptr_t)x2 & 3) || ((uintptr_t)deq2 & 3))))
+    return (int)hipErrorInvalidValue;
+  const long long rows = (long long)B * S * H;
+  const dim3 grid((unsigned)((rows + 3) / 4), x2 ? 2u : 1u);
+  const KvPairQ8 v2{x2, ldx2, bsx2, static_cast<signed char*>(cache2), scales2, deq2};
+  if (D == 64)
+    hipLaunchKernelGGL(kv_write_q8_kernel<64>, grid, dim3(256), 0, stream, x, ldx, bsx, static_cast<signed char*>(cache),
+                       scales, deq, pos, cos_t, sin_t, R, B, S, H, L, v2);
+  else
+    hipLaunchKernelGGL(kv_write_q8_kernel<128>, grid, dim3(256), 0, stream, x, ldx, bsx,
+                       static_cast<signed char*>(cache), scales, deq, pos, cos_t, sin_t, R, B, S, H, L, v2);
+  return (int)hipGetLastError();
+}
+
 NOS_API int nos_rotary_pos(const void* x, int ldx, long long bsx, void* y, const int* pos, const float* cos_t,
                            const float* sin_t, int R, int B, int S, int H, int D, int bf16, hipStream_t stream) {
   if (B <= 0 || S <= 0 || H <= 0 || D <= 0 || (D % 2) || R <= 0 || ldx < H * D || !cos_t || !sin_t || !pos ||
@@ -1207,15 +1407,21 @@ NOS_API long long nos_attn_decode_workspace(int B, int H, int Hkv, int Sq, int L
 // from there: the kv_write launch of the step folded in (nfresh == Sq).  sync
 // (sync_n >= B x Hkv i32, zero before the first call, left zero by each): the
 // combine folded into the decode launch (its last workgroup per (b, kv head)).
-NOS_API int nos_attn_decode(const void* q, int qbf, int ldq, long long bsq, const void* kc, const void* vc, int cbf,
-                            const int* pos, const float* cos_t, const float* sin_t, int R, void* out, int obf, int B,
-                            int H, int Hkv, int Sq, int L, int D, float scale, void* ws, long long ws_bytes,
-                            const void* kn, const void* vn, int nbf, int ldk, long long bsk, int ldv, long long bsv,
-                            int nfresh, int* sync, long long sync_n, int partials_only, hipStream_t stream) {
+// cbf 2: int8 caches with their row scales ks / vs (nos_attn_decode_q8)
+static int attn_decode_launch(const void* q, int qbf, int ldq, long long bsq, const void* kc, const void* vc, int cbf,
+                              float* ks, float* vs, const int* pos, const float* cos_t, const float* sin_t, int R,
+                              void* out, int obf, int B, int H, int Hkv, int Sq, int L, int D, float scale, void* ws,
+                              long long ws_bytes, const void* kn, const void* vn, int nbf, int ldk, long long bsk,
+                              int ldv, long long bsv, int nfresh, int* sync, long long sync_n, int partials_only,
+                              hipStream_t stream) {
   if (B <= 0 || H <= 0 || Hkv <= 0 || H % Hkv || H / Hkv > MAXR || Sq <= 0 || L <= 0 || (D != 64 && D != 128) ||
       ldq < H * D || (B > 1 && bsq < (long long)(Sq - 1) * ldq + H * D) || !q || !kc || !vc || !pos || !out ||
       !ws || ((cos_t == nullptr) != (sin_t == nullptr)) || (cos_t && R <= 0) || (qbf != 0 && qbf != 1) ||
-      (cbf != 0 && cbf != 1) || (obf != 0 && obf != 1) || !(scale > 0.f))
+      (cbf != 0 && cbf != 1 && cbf != 2) || (obf != 0 && obf != 1) || !(scale > 0.f))
+    return (int)hipErrorInvalidValue;
+  // int8 rows load as 16-byte pieces; fp32 q, rows and output only (an fp32 tenant's storage format)
+  if (cbf == 2 && (!ks || !vs || ((uintptr_t)kc & 15) || ((uintptr_t)vc & 15) || ((uintptr_t)ks & 3) ||
+                   ((uintptr_t)vs & 3) || qbf || obf || (nfresh != 0 && nbf)))
     return (int)hipErrorInvalidValue;
   if (ws_bytes < nos_attn_decode_workspace(B, H, Hkv, Sq, L, D)) return (int)hipErrorInvalidValue;
   if (sync != nullptr && sync_n < (long long)B * Hkv) return (int)hipErrorInvalidValue;
@@ -1243,11 +1449,14 @@ NOS_API int nos_attn_decode(const void* q, int qbf, int ldq, long long bsq, cons
     const int sq = Sq - q0 < chunk ? Sq - q0 : chunk;
     const unsigned grid = (unsigned)(B * Hkv * NS);
     const unsigned rows = (unsigned)(B * Hkv * G * sq);
-#define NOS_ATTN_DECODE(d, c)                                                                                   \
+#define NOS_ATTN_DECODE(d, c, ...)                                                                              \
   hipLaunchKernelGGL((attn_decode_kernel<d, c>), dim3(grid), dim3(256), 0, stream, q, qbf, ldq, bsq, kc, vc, cbf, pos, \
-                     cos_t, sin_t, R, static_cast<float*>(ws), B, H, Hkv, sq, q0, L, NS, scale, fr, sync, out, obf, Sq)
+                     cos_t, sin_t, R, static_cast<float*>(ws), B, H, Hkv, sq, q0, L, NS, scale, fr, sync, out, obf, Sq, \
+                     CacheScales<c>{__VA_ARGS__})
     if (D == 64) {
-      if (cbf)
+      if (cbf == 2)
+        NOS_ATTN_DECODE(64, 2, ks, vs);
+      else if (cbf)
         NOS_ATTN_DECODE(64, 1);
       else
         NOS_ATTN_DECODE(64, 0);
@@ -1255,7 +1464,9 @@ NOS_API int nos_attn_decode(const void* q, int qbf, int ldq, long long bsq, cons
         hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3(rows), dim3(64), 0, stream,
                            static_cast<const float*>(ws), out, obf, B, H, Hkv, sq, q0, Sq, NS);
     } else {
-      if (cbf)
+      if (cbf == 2)
+        NOS_ATTN_DECODE(128, 2, ks, vs);
+      else if (cbf)
         NOS_ATTN_DECODE(128, 1);
       else
         NOS_ATTN_DECODE(128, 0);
@@ -1266,6 +1477,32 @@ NOS_API int nos_attn_decode(const void* q, int qbf, int ldq, long long bsq, cons
   }
   #undef NOS_ATTN_DECODE
   return (int)hipGetLastError();
+}
+
+NOS_API int nos_attn_decode(const void* q, int qbf, int ldq, long long bsq, const void* kc, const void* vc, int cbf,
+                            const int* pos, const float* cos_t, const float* sin_t, int R, void* out, int obf, int B,
+                            int H, int Hkv, int Sq, int L, int D, float scale, void* ws, long long ws_bytes,
+                            const void* kn, const void* vn, int nbf, int ldk, long long bsk, int ldv, long long bsv,
+                            int nfresh, int* sync, long long sync_n, int partials_only, hipStream_t stream) {
+  if (cbf != 0 && cbf != 1) return (int)hipErrorInvalidValue;
+  return attn_decode_launch(q, qbf, ldq, bsq, kc, vc, cbf, nullptr, nullptr, pos, cos_t, sin_t, R, out, obf, B, H, Hkv,
+                            Sq, L, D, scale, ws, ws_bytes, kn, vn, nbf, ldk, bsk, ldv, bsv, nfresh, sync, sync_n,
+                            partials_only, stream);
+}
+
+// nos_attn_decode over int8 caches [B, L, Hkv, D] (16-byte aligned) with one fp32 scale per row in
+// kscales / vscales [B, L, Hkv]: the attention, in fp32, of the values (float)q x scale the caches hold.
+// q, out and the fresh rows kn / vn are fp32; fresh rows are quantized into the caches and the scales
+// by the launch (which is why those are not const) and attended as stored.
+NOS_API int nos_attn_decode_q8(const float* q, int ldq, long long bsq, void* kc, void* vc, float* kscales,
+                               float* vscales, const int* pos, const float* cos_t, const float* sin_t, int R,
+                               float* out, int B, int H, int Hkv, int Sq, int L, int D, float scale, void* ws,
+                               long long ws_bytes, const float* kn, const float* vn, int ldk, long long bsk, int ldv,
+                               long long bsv, int nfresh, int* sync, long long sync_n, int partials_only,
+                               hipStream_t stream) {
+  return attn_decode_launch(q, 0, ldq, bsq, kc, vc, 2, kscales, vscales, pos, cos_t, sin_t, R, out, 0, B, H, Hkv, Sq, L,
+                            D, scale, ws, ws_bytes, kn, vn, 0, ldk, bsk, ldv, bsv, nfresh, sync, sync_n,
+                            partials_only, stream);
 }
 
 NOS_API int nos_pos_update(int* pos, int B, int add, int n, hipStream_t stream) {

@@ -112,7 +112,7 @@ def llama_program(model, seq: int, batch: int = 1, dtype: str = "fp32",
 
 def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, dtype: str = "fp32",
                           extend: tuple[int, ...] = (), sampling: bool = False,
-                          weights: str = "fp32") -> tuple[list[dict], bytes]:
+                          weights: str = "fp32", kv: str | None = None) -> tuple[list[dict], bytes]:
     """A STATEFUL generation tenant: ``[prefill, decode, *extends]`` programs
     over one weight payload and one state -- per layer a K and a V cache
     ``[batch, max_len, kv_heads, head_dim]`` plus the position counter
@@ -148,14 +148,27 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     merged, down and the LM head (its own quantized copy when the head is
     tied; the embedding table stays fp32).  Quantization is a storage format:
     the server computes, in fp32, exactly the model
-    :func:`dequantized_llama` returns."""
+    :func:`dequantized_llama` returns.
+
+    ``kv="int8"`` (fp32 tenants; default: the tenant's dtype): the caches are
+    i8 states ``kc{i}`` / ``vc{i}`` with one fp32 scale per (sequence,
+    position, KV head) row in ``ks{i}`` / ``vs{i}`` ``[batch, max_len,
+    kv_heads]`` -- a quarter of the fp32 caches' bytes plus the scales.  Here
+    the server does quantize: every K (after its rotation) and V row as it is
+    written, by ``quantize_rows_q8``'s rule, and every program attends the
+    rows as the cache holds them -- an HF model run with
+    :func:`kv_q8_roundtrip_cache` is the model such a tenant computes."""
     if not 0 < prompt_len <= max_len:
         raise ValueError(f"prompt_len must be in [1, {max_len}]")
     if weights not in ("fp32", "int8"):
         raise ValueError(f"weights must be 'fp32' or 'int8', got {weights!r}")
     if weights == "int8" and dtype != "fp32":
         raise ValueError("int8 weights are an fp32 tenant's storage format: dtype must be 'fp32'")
-    q8 = weights == "int8"
+    if kv not in (None, "fp32", "int8") or (kv == "fp32" and dtype != "fp32"):
+        raise ValueError(f"kv must be None (the tenant's dtype), 'fp32' (fp32 tenants) or 'int8', got {kv!r}")
+    if kv == "int8" and dtype != "fp32":
+        raise ValueError("int8 K / V caches are an fp32 tenant's storage format: dtype must be 'fp32'")
+    q8, kvq8 = weights == "int8", kv == "int8"
     cfg = model.config
     sd = {k: v.detach().float().cpu().numpy() for k, v in model.state_dict().items()}
     d, nh = cfg.hidden_size, cfg.num_attention_heads
@@ -169,7 +182,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     chunks = [(prompt_len, True), (1, False)] + [(n, False) for n in extend]
     payload = b""
     for seq, reset in chunks:
-        b = Builder(f"llama-h{d}-l{cfg.num_hidden_layers}-{dtype}{'-q8' if q8 else ''}-"
+        b = Builder(f"llama-h{d}-l{cfg.num_hidden_layers}-{dtype}{'-q8' if q8 else ''}{'-kvq8' if kvq8 else ''}-"
                     f"{'prefill' if reset else 'step'}{seq}")
         ids = b.input("input_ids", [batch, seq], "i32")
         P = lambda k: b.param(k, sd[k], dtype)  # noqa: E731
@@ -186,8 +199,13 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
         rc, rs = b.param("rope.cos", cos, "fp32"), b.param("rope.sin", sin, "fp32")
         b.state("pos", [batch], "i32")
         ctl = b.state("sampling", [4], "i32") if sampling else None
-        caches = [(b.state(f"kc{i}", [batch, max_len, nkv, hd], cache_dt),
-                   b.state(f"vc{i}", [batch, max_len, nkv, hd], cache_dt)) for i in range(cfg.num_hidden_layers)]
+        cshape = [batch, max_len, nkv, hd]
+        if kvq8:   # ((K cache, its scales), (V cache, its scales)) per layer
+            caches = [(b.cache_q8(f"kc{i}", f"ks{i}", cshape), b.cache_q8(f"vc{i}", f"vs{i}", cshape))
+                      for i in range(cfg.num_hidden_layers)]
+        else:
+            caches = [((b.state(f"kc{i}", cshape, cache_dt),), (b.state(f"vc{i}", cshape, cache_dt),))
+                      for i in range(cfg.num_hidden_layers)]
         p = b.op("pos_set", "pos", value=0) if reset else "pos"
         h = b.op("embedding", ids, P("model.embed_tokens.weight"))
         for i in range(cfg.num_hidden_layers):
@@ -203,9 +221,10 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
             k = b.op("reshape", proj(1), shape=[batch, seq, nkv, hd])
             v = b.op("reshape", proj(2), shape=[batch, seq, nkv, hd])
             q, k = b.op("rotary_at", q, rc, rs, p), b.op("rotary_at", k, rc, rs, p)
-            kc = b.op("kv_write", caches[i][0], k, p)
-            vc = b.op("kv_write", caches[i][1], v, p)
-            o = b.op("reshape", b.op("sdpa_cache", q, kc, vc, p), shape=[batch, seq, nh * hd])
+            (kc0, *ks), (vc0, *vs) = caches[i]   # ks / vs: the scales states of i8 caches, else empty
+            kc = b.op("kv_write", kc0, k, p, *ks)
+            vc = b.op("kv_write", vc0, v, p, *vs)
+            o = b.op("reshape", b.op("sdpa_cache", q, kc, vc, p, *ks, *vs), shape=[batch, seq, nh * hd])
             h = b.op("add", lin(o, pf + "self_attn.o_proj.weight"), h)
             y = b.op("rmsnorm", h, P(pf + "post_attention_layernorm.weight"), eps=eps)
             if q8:
@@ -253,6 +272,28 @@ def dequantized_llama(model):
     return m
 
 
+def kv_q8_roundtrip_cache():
+    """A ``transformers`` cache for ``model(..., past_key_values=...)`` whose
+    ``update()`` replaces the incoming K (already rotated) and V by
+    ``dequantize(quantize(.))`` -- per token and KV head, in fp32, by
+    ``quantize_rows_q8``'s rule -- and stores and returns those: an HF model
+    run with it is the model an int8-KV tenant computes
+    (``llama_decode_programs(kv="int8")``), for tests and users to compare against."""
+    import torch
+    from transformers import DynamicCache
+
+    def roundtrip(x):   # [B, Hkv, S, D]
+        rows = x.detach().to(torch.float32).cpu().reshape(-1, x.shape[-1]).numpy()
+        deq = torch.from_numpy(dequantize_rows_q8(*quantize_rows_q8(rows)))
+        return deq.reshape(x.shape).to(device=x.device, dtype=x.dtype)
+
+    class KvQ8RoundtripCache(DynamicCache):
+        def update(self, key_states, value_states, layer_idx, cache_kwargs=None):
+            return super().update(roundtrip(key_states), roundtrip(value_states), layer_idx, cache_kwargs)
+
+    return KvQ8RoundtripCache()
+
+
 def llama_tenant(dtype: str = "fp32", seed: int = 0, small: bool = True, seq: int = 512,
                  batch: int = 1) -> tuple[dict, bytes]:
     """(program, weights) of the decoder-LLM tenant (``small=False``: the
@@ -262,4 +303,4 @@ def llama_tenant(dtype: str = "fp32", seed: int = 0, small: bool = True, seq: in
 
 
 __all__ = ["llama_config", "llama_model", "llama_program", "llama_decode_programs", "llama_tenant", "rope_tables",
-           "dequantized_llama"]
+           "dequantized_llama", "kv_q8_roundtrip_cache"]

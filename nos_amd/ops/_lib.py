@@ -109,6 +109,13 @@ _SIGS = {
     "nos_attn_decode": [c_void_p, c_int, c_int, c_ll, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                         c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_ll,
                         c_void_p, c_void_p, c_int, c_int, c_ll, c_int, c_ll, c_int, c_void_p, c_ll, c_int, c_void_p],
+    # int8 K / V caches with a scale per row (decode.hip)
+    "nos_kv_write_q8": [c_void_p, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                        c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_ll, c_void_p, c_void_p, c_void_p,
+                        c_void_p],
+    "nos_attn_decode_q8": [c_void_p, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_ll,
+                           c_void_p, c_void_p, c_int, c_ll, c_int, c_ll, c_int, c_void_p, c_ll, c_int, c_void_p],
     "nos_pos_update": [c_void_p, c_int, c_int, c_int, c_void_p],
     "nos_argmax": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     "nos_sample_row_in_lds": [c_int],

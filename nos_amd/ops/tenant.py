@@ -704,13 +704,24 @@ def _i32_pos(pos: torch.Tensor, B: int) -> torch.Tensor:
 
 
 def kv_write(cache: torch.Tensor, x: torch.Tensor, pos: torch.Tensor, rope: tuple | None = None,
-             second: tuple | None = None) -> torch.Tensor:
+             second: tuple | None = None, scales: torch.Tensor | None = None, deq: bool = False):
     """cache[b, pos[b] + s] = x[b, s] in place (rows past the cache dropped);
     ``rope`` = (cos, sin) fp32 tables: x rotated at those positions first.
     ``second`` = (cache2, x2): a second, unrotated write of the same shape in
-    the same launch (a layer's V beside its K).  Returns ``cache``."""
+    the same launch (a layer's V beside its K).  Returns ``cache``.
+
+    An int8 ``cache`` with its ``scales`` [B, L, H] (fp32; ``second`` then
+    (cache2, x2, scales2)): the fp32 rows are quantized as they are written
+    (after the rotation; ``quantize_rows_q8``'s rule per row).  ``deq``:
+    also return the written rows as the cache now holds them, fp32
+    [B, S, H, D] -- ``(cache, deq)``, with ``second`` ``(cache, deq, deq2)``."""
     from ..podserver.program.reference import kv_write_ref, rotary_at_ref
 
+    q8 = cache.dtype == torch.int8
+    if q8 != (scales is not None) or (deq and not q8):
+        raise ValueError("kv_write: an int8 cache, and only an int8 cache, takes scales (and gives deq)")
+    if q8:
+        return _kv_write_q8(cache, x, pos, rope, second, scales, deq)
     if not cache.is_cuda:
         if second is not None:
             kv_write_ref(second[0], second[1], pos)
@@ -737,6 +748,57 @@ def kv_write(cache: torch.Tensor, x: torch.Tensor, pos: torch.Tensor, rope: tupl
                                        _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R, B, S, H, D, L, x2p, ld2, bs2,
                                        c2p, _stream()), "nos_kv_write")
     return cache
+
+
+def _q8_cache_ok(what: str, cache: torch.Tensor, scales: torch.Tensor) -> None:
+    if (cache.dtype != torch.int8 or scales.dtype != torch.float32 or tuple(scales.shape) != tuple(cache.shape[:3])
+            or not cache.is_contiguous() or not scales.is_contiguous() or scales.device != cache.device):
+        raise ValueError(f"{what}: an int8 cache [B, L, H, D] with fp32 scales [B, L, H] (both contiguous) required, "
+                         f"got {cache.dtype} {tuple(cache.shape)} and {scales.dtype} {tuple(scales.shape)}")
+
+
+def _kv_write_q8(cache, x, pos, rope, second, scales, deq):
+    """:func:`kv_write` into int8 caches (decode.hip ``nos_kv_write_q8``; the eager reference on the CPU)."""
+    from ..podserver.program.reference import dequantize_kv_rows, kv_write_ref, quantize_kv_rows, rotary_at_ref
+
+    _q8_cache_ok("kv_write", cache, scales)
+    if second is not None:
+        if len(second) != 3:
+            raise ValueError("kv_write: the second write into an int8 cache is (cache2, x2, scales2)")
+        _q8_cache_ok("kv_write", second[0], second[2])
+    if x.dtype != torch.float32 or (second is not None and second[1].dtype != torch.float32):
+        raise ValueError("kv_write: int8 caches take fp32 rows")
+    if not cache.is_cuda:
+        xs = [rotary_at_ref(x, rope[0], rope[1], pos) if rope else x] + ([second[1]] if second is not None else [])
+        kv_write_ref(cache, xs[0], pos, scales)
+        if second is not None:
+            kv_write_ref(second[0], xs[1], pos, second[2])
+        return (cache, *(dequantize_kv_rows(*quantize_kv_rows(t)) for t in xs)) if deq else cache
+    B, L, H, D = cache.shape
+    S = x.shape[1]
+    if x.shape[0] != B or x.shape[2:] != cache.shape[2:]:
+        raise ValueError(f"kv_write: x {tuple(x.shape)} does not fit the cache {tuple(cache.shape)}")
+    x, ldx, bsx = _rows(x)
+    c = s_ = None
+    R = 0
+    if rope is not None:
+        c, s_ = rope[0].float().contiguous(), rope[1].float().contiguous()
+        R = c.shape[0]
+    dq = torch.empty((B, S, H, D), dtype=torch.float32, device=x.device) if deq else None
+    x2p, ld2, bs2, c2p, s2p, dq2 = None, 0, 0, None, None, None
+    if second is not None:
+        c2, x2, s2 = second
+        if c2.shape != cache.shape or x2.shape != x.shape:
+            raise ValueError("kv_write: the second write must match the first's shapes and dtypes")
+        x2, ld2, bs2 = _rows(x2)
+        x2p, c2p, s2p = x2.data_ptr(), c2.data_ptr(), s2.data_ptr()
+        dq2 = torch.empty_like(dq) if deq else None
+    _lib.check(_lib.lib().nos_kv_write_q8(x.data_ptr(), ldx, bsx, cache.data_ptr(), scales.data_ptr(), _ptr(dq),
+                                          _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R, B, S, H, D, L, x2p, ld2,
+                                          bs2, c2p, s2p, _ptr(dq2), _stream()), "nos_kv_write_q8")
+    if not deq:
+        return cache
+    return (cache, dq) if second is None else (cache, dq, dq2)
 
 
 def rotary_at(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
@@ -769,7 +831,7 @@ class DecodePartials:
 
 def sdpa_cache(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: torch.Tensor, scale: float | None = None,
                rope: tuple | None = None, fresh: tuple | None = None, sync: torch.Tensor | None = None,
-               partials: bool = False):
+               partials: bool = False, scales: tuple | None = None):
     """Query i of sequence b, at position pos[b] + i, attends the cached keys
     0 .. pos[b] + i: q [B, Sq, H, D], caches [B, L, Hkv, D] (fp32 / bf16).
     ``rope`` = (cos, sin): q rotated at its positions inside the kernel.
@@ -781,14 +843,28 @@ def sdpa_cache(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: torch.T
     workgroup per K / V head instead of a launch of its own.  ``partials``
     (CUDA, fp32 q, one query token): no combine -- returns the splits'
     :class:`DecodePartials` for :func:`gemv_partials`.  The
-    flash-decoding kernel (decode.hip) for CUDA tensors, fp32 math."""
+    flash-decoding kernel (decode.hip) for CUDA tensors, fp32 math.
+
+    int8 caches with ``scales`` = (kscales, vscales) [B, L, Hkv] fp32 (q and
+    ``fresh`` fp32): the attention of the values ``float(q) * scale`` the
+    caches hold; fresh rows are quantized into the caches and the scales (as
+    :func:`kv_write` does) and attended as stored."""
     from ..podserver.program.reference import kv_write_ref, rotary_at_ref, sdpa_cache_ref
 
+    q8 = kc.dtype == torch.int8
+    if q8 != (scales is not None):
+        raise ValueError("sdpa_cache: int8 caches, and only int8 caches, take scales")
+    if q8:
+        _q8_cache_ok("sdpa_cache", kc, scales[0])
+        _q8_cache_ok("sdpa_cache", vc, scales[1])
+        if q.dtype != torch.float32 or (fresh is not None and fresh[0].dtype != torch.float32):
+            raise ValueError("sdpa_cache: int8 caches take an fp32 q and fp32 fresh rows")
+    ks, vs = scales if q8 else (None, None)
     if not q.is_cuda:
         if fresh is not None:
-            kv_write_ref(kc, rotary_at_ref(fresh[0], rope[0], rope[1], pos) if rope else fresh[0], pos)
-            kv_write_ref(vc, fresh[1], pos)
-        return sdpa_cache_ref(rotary_at_ref(q, rope[0], rope[1], pos) if rope else q, kc, vc, pos, scale)
+            kv_write_ref(kc, rotary_at_ref(fresh[0], rope[0], rope[1], pos) if rope else fresh[0], pos, ks)
+            kv_write_ref(vc, fresh[1], pos, vs)
+        return sdpa_cache_ref(rotary_at_ref(q, rope[0], rope[1], pos) if rope else q, kc, vc, pos, scale, ks, vs)
     B, Sq, H, D = q.shape
     L, Hkv = kc.shape[1], kc.shape[2]
     if (kc.shape != vc.shape or kc.dtype != vc.dtype or kc.shape[0] != B or kc.shape[3] != D or H % Hkv
@@ -818,12 +894,20 @@ def sdpa_cache(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: torch.T
         raise ValueError(f"sdpa_cache: sync needs >= {B * Hkv} contiguous int32 device counters")
     if partials and (Sq != 1 or sync is not None or q.dtype != torch.float32):
         raise ValueError("sdpa_cache: partials need one fp32 query token and no sync")
-    _lib.check(L_.nos_attn_decode(q.data_ptr(), _bf(q), ldq, bsq, kc.data_ptr(), vc.data_ptr(), _bf(kc),
-                                  _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R, out.data_ptr(), _bf(out), B, H,
-                                  Hkv, Sq, L, D, float(sc), ws.data_ptr(), ws.numel() * 4, _ptr(kn), _ptr(vn), nbf,
-                                  ldk, bsk, ldv, bsv, Sq if fresh is not None else 0, _ptr(sync),
-                                  sync.numel() if sync is not None else 0, int(bool(partials)), _stream()),
-               "nos_attn_decode")
+    if q8:
+        _lib.check(L_.nos_attn_decode_q8(q.data_ptr(), ldq, bsq, kc.data_ptr(), vc.data_ptr(), ks.data_ptr(),
+                                         vs.data_ptr(), _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R,
+                                         out.data_ptr(), B, H, Hkv, Sq, L, D, float(sc), ws.data_ptr(), ws.numel() * 4,
+                                         _ptr(kn), _ptr(vn), ldk, bsk, ldv, bsv, Sq if fresh is not None else 0,
+                                         _ptr(sync), sync.numel() if sync is not None else 0, int(bool(partials)),
+                                         _stream()), "nos_attn_decode_q8")
+    else:
+        _lib.check(L_.nos_attn_decode(q.data_ptr(), _bf(q), ldq, bsq, kc.data_ptr(), vc.data_ptr(), _bf(kc),
+                                      _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R, out.data_ptr(), _bf(out), B, H,
+                                      Hkv, Sq, L, D, float(sc), ws.data_ptr(), ws.numel() * 4, _ptr(kn), _ptr(vn), nbf,
+                                      ldk, bsk, ldv, bsv, Sq if fresh is not None else 0, _ptr(sync),
+                                      sync.numel() if sync is not None else 0, int(bool(partials)), _stream()),
+                   "nos_attn_decode")
     if partials:
         return DecodePartials(ws, (L + 127) // 128, H // Hkv, Hkv, D, (B, Sq, H, D), q.dtype)
     return out

@@ -89,6 +89,13 @@ class Builder:
         self.states.append({"name": name, "shape": list(shape), "dtype": dtype})
         return name
 
+    def cache_q8(self, name: str, scales: str, shape) -> tuple[str, str]:
+        """A K / V cache [B, L, Hkv, D] kept as int8 rows with one fp32 scale per row: the i8
+        state ``name`` and its fp32 [B, L, Hkv] state ``scales`` (``kv_write`` takes the scales as
+        input 3, ``sdpa_cache`` K's and V's as inputs 4 and 5; the server quantizes the rows as it
+        writes them, by :func:`quantize_rows_q8`'s rule)."""
+        return self.state(name, shape, "i8"), self.state(scales, list(shape)[:3], "fp32")
+
     def op(self, op: str, *inputs: str, out: str | None = None, **attrs) -> str:
         self._n += 1
         out = out or f"%{self._n}"

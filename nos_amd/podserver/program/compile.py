@@ -50,6 +50,7 @@ class Lowered:
             # NOS_AMD_SKIP_PASSES=name,...: leave launch-trimming passes out (A/B runs)
             skip = self._skip = set(os.environ.get("NOS_AMD_SKIP_PASSES", "").split(","))
             steps = self._fold_constants(prog)
+            steps = self._lift_cache_scales(steps)
             steps = self._lower_static_positions(steps)
             if "add_over_cat" not in skip:
                 steps = self._distribute_add_over_cat(steps)
@@ -140,6 +141,23 @@ class Lowered:
         self.stats["constant_folded"] = folded
         return steps
 
+    def _lift_cache_scales(self, steps: list[_Step]) -> list[_Step]:
+        """The scales states of i8 caches (``kv_write``'s input 3, ``sdpa_cache``'s
+        inputs 4 and 5) move from the steps' inputs into ``attrs["scales"]``: they
+        are fixed companions of their caches (the validator pairs them for the
+        program), never versioned or released, so every pass below sees the
+        3- / 4-input forms of float caches and fuses them alike; the executor
+        looks the tensors up in the state."""
+        roots = set()
+        for s in steps:
+            n = {"kv_write": 3, "sdpa_cache": 4}.get(s.kind)
+            if n is not None and len(s.inputs) > n:
+                s.attrs = {**s.attrs, "scales": list(s.inputs[n:])}
+                s.inputs = s.inputs[:n]
+                roots.update(s.attrs["scales"])
+        self.stats["kv_q8_caches"] = len(roots)
+        return steps
+
     def _lower_static_positions(self, steps: list[_Step]) -> list[_Step]:
         """Positions the program fixes itself (``pos_set`` and then ``pos_add``
         by constants) are known at build: a prefill program that starts a
@@ -148,7 +166,10 @@ class Lowered:
         ``sdpa_cache`` whose caches were just written from the same keys /
         values at position 0 (Sq = their S) is causal ``sdpa`` on those keys
         and values (the flash kernel; the writes stay, for the decode steps
-        after it).  Dynamic positions keep the cache kernels."""
+        after it).  Over i8 caches the attention must see the rows as the cache
+        holds them: the writes also give their rows dequantized (``deq_out``, a
+        transient the estimate charges) and the ``sdpa`` reads those.  Dynamic
+        positions keep the cache kernels."""
         by_out = {s.output: s for s in steps}
         known: dict[str, int] = {}
         n = 0
@@ -177,7 +198,14 @@ class Lowered:
                         or wk.inputs[2] != s.inputs[3] or wv.inputs[2] != s.inputs[3]
                         or self._shape(wk.inputs[1])[1] != sq or self._shape(wv.inputs[1])[1] != sq):
                     continue
-                s.kind, s.inputs = "sdpa", [s.inputs[0], wk.inputs[1], wv.inputs[1]]
+                kv = [wk.inputs[1], wv.inputs[1]]
+                if s.attrs.get("scales"):
+                    for w in (wk, wv):
+                        w.attrs = {**w.attrs, "deq_out": w.output + "::deq"}
+                        self._new_shapes[w.attrs["deq_out"]] = tuple(self._shape(w.inputs[1]))
+                        self._new_dtypes[w.attrs["deq_out"]] = "fp32"
+                    kv = [wk.attrs["deq_out"], wv.attrs["deq_out"]]
+                s.kind, s.inputs = "sdpa", [s.inputs[0], *kv]
                 s.attrs = {"causal": True, **({"scale": s.attrs["scale"]} if "scale" in s.attrs else {})}
                 n += 1
         self.stats["static_positions"] = n
@@ -889,6 +917,7 @@ class Lowered:
                 if all(x in defined for x in s.inputs) and readers_before.get(id(s), set()) <= placed:
                     out.append(s)
                     defined.add(s.output)
+                    defined.add(s.attrs.get("deq_out"))   # an i8 kv_write's second value (or None)
                     placed.add(id(s))
                     pending.pop(i)
                     break
@@ -1017,13 +1046,15 @@ class Lowered:
             wk, wv = by_out.get(s.inputs[1]), by_out.get(s.inputs[2])
             if (wk is None or wv is None or wk.kind != "kv_write" or wv.kind != "kv_write" or id(wk) in drop
                     or wv.attrs.get("rope") or wv.attrs.get("pair") or wk.inputs[2] != wv.inputs[2]
+                    or wk.attrs.get("deq_out") or wv.attrs.get("deq_out")
                     or tuple(self._shape(wk.inputs[1])) != tuple(self._shape(wv.inputs[1]))
                     or tuple(self._shape(wk.inputs[0])) != tuple(self._shape(wv.inputs[0]))
                     or self._dtype(wk.inputs[0]) != self._dtype(wv.inputs[0])
                     or steps.index(wk) > steps.index(wv)):
                 continue
             wv.inputs = wk.inputs + [wv.inputs[0], wv.inputs[1]]   # K cache, K x, pos, [cos, sin], V cache, V x
-            wv.attrs = {"pair": True, "rope": bool(wk.attrs.get("rope")), "k_out": wk.output}
+            wv.attrs = {"pair": True, "rope": bool(wk.attrs.get("rope")), "k_out": wk.output,
+                        **({"scales": wk.attrs["scales"] + wv.attrs["scales"]} if wk.attrs.get("scales") else {})}
             drop.add(id(wk))
             n += 1
         self.stats["kv_writes_paired"] = n
@@ -1034,7 +1065,9 @@ class Lowered:
         its ``sdpa_cache`` reads, at the same positions and (K and q) with the
         same rotary tables, folds into that attention launch: the decode kernel
         writes the step's rows into the caches itself and attends them from
-        registers (decode.hip ``Fresh``) -- one launch per layer fewer."""
+        registers (decode.hip ``Fresh``) -- one launch per layer fewer.  i8
+        caches alike: the kernel quantizes the rows it writes (the attention
+        step already names the pair's scales)."""
         if not self.gpu:
             return steps
         uses = self._consumers(steps, self.outputs)

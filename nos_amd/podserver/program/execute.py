@@ -134,16 +134,23 @@ class CompiledProgram(Lowered):
                 y = T.glu(a[0], a[1], s.attrs["op"])
             elif k == "kv_write" and s.attrs.get("pair"):   # K (maybe rotated) and V of one layer, one launch
                 r = 5 if s.attrs.get("rope") else 3
+                sc = [self.state[n] for n in s.attrs.get("scales", ())]   # i8 caches: K's and V's row scales
                 env[s.attrs["k_out"]] = T.kv_write(a[0], a[1], a[2], rope=(a[3], a[4]) if s.attrs.get("rope") else None,
-                                                   second=(a[r], a[r + 1]))
+                                                   second=(a[r], a[r + 1], *sc[1:]), scales=sc[0] if sc else None)
                 y = a[r]
             elif k == "kv_write":
-                y = T.kv_write(a[0], a[1], a[2], rope=(a[3], a[4]) if s.attrs.get("rope") else None)
+                sc = [self.state[n] for n in s.attrs.get("scales", ())]
+                y = T.kv_write(a[0], a[1], a[2], rope=(a[3], a[4]) if s.attrs.get("rope") else None,
+                               scales=sc[0] if sc else None, deq=bool(s.attrs.get("deq_out")))
+                if s.attrs.get("deq_out"):   # the rows as the i8 cache holds them, for the prefill's flash attention
+                    y, env[s.attrs["deq_out"]] = y
             elif k == "sdpa_cache":
+                sc = tuple(self.state[n] for n in s.attrs.get("scales", ()))
                 y = T.sdpa_cache(a[0], a[1], a[2], a[3], scale=s.attrs.get("scale"),
                                  rope=(a[4], a[5]) if s.attrs.get("rope") else None,
                                  fresh=(a[-2], a[-1]) if s.attrs.get("fresh") else None,
-                                 sync=self.aux.get(s.attrs.get("sync")), partials=bool(s.attrs.get("partials")))
+                                 sync=self.aux.get(s.attrs.get("sync")), partials=bool(s.attrs.get("partials")),
+                                 scales=sc or None)
             elif k == "rotary_at":
                 y = T.rotary_at(a[0], a[1], a[2], a[3])
             elif k in ("pos_add", "pos_set"):

@@ -130,10 +130,18 @@ class Program:
                 last[i] = k
         keep = set(self.outputs)
         live = peak = 0
+        start = {n.output for n in self.nodes if n.op == "pos_set" and n.attrs.get("value") == 0}
         for k, n in enumerate(self.nodes):
             if n.output in folded:
                 continue
             ws = _workspace(n, [self.values[i] for i in n.inputs], self.values[n.output], f32_math)
+            # a prefill at position 0 into i8 caches attends the rows the writes hand over dequantized
+            # (fp32 copies of K and V, alive from their writes to the attention): charged at all three
+            if n.op in ("kv_write", "sdpa_cache"):
+                cache, x, p = (1, 0, 3) if n.op == "sdpa_cache" else (0, 1, 2)
+                if self.values[n.inputs[cache]].dtype == "i8" and n.inputs[p] in start:
+                    b, _, hkv, d = self.values[n.inputs[cache]].shape
+                    ws += 2 * b * self.values[n.inputs[x]].shape[1] * hkv * d * 4
             if not self.is_state(n.output):   # an in-place state update allocates nothing
                 live += self.values[n.output].nbytes
             peak = max(peak, live + ws)
@@ -232,7 +240,8 @@ class Program:
         ps = params if params is not None else self.tensors("cpu")
         env = {k: t.float().cpu() for k, t in ps.items()}
         if state is None:
-            state = {k: (t if t.dtype == torch.int32 else t.float()) for k, t in self.state_tensors("cpu").items()}
+            state = {k: (t if t.dtype in (torch.int32, torch.int8) else t.float())
+                     for k, t in self.state_tensors("cpu").items()}
         env.update(state)
         env[self.inputs[0].name] = x.cpu() if self.inputs[0].dtype == "i32" else x.float().cpu()
         with torch.no_grad():

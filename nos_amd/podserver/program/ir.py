@@ -6,7 +6,8 @@ import math
 from dataclasses import dataclass, field
 
 FORMAT = "nos-amd.program/v1"
-# i32: token ids (an input only; consumed by embedding); i8: quantized weights (a param only; linear_q8's input 1)
+# i32: token ids (an input only; consumed by embedding); i8: quantized weights (a param; linear_q8's input 1)
+# or a quantized K / V cache (a state; the cache operand of kv_write / sdpa_cache, with an fp32 scales state)
 WIRE_DTYPES = {"fp32": 4, "bf16": 2, "i32": 4, "i8": 1}
 PARAM_DTYPES = ("fp32", "bf16", "i8")
 FLOAT_DTYPES = ("fp32", "bf16")
@@ -121,7 +122,7 @@ OPS = ("linear", "layernorm", "attention", *BINARY, *UNARY, "cat", "slice", "res
 # the old version dead from then on, so in-place equals SSA semantics)
 STATE_OPS = ("kv_write", "sdpa_cache", "rotary_at", "pos_add", "pos_set", "argmax", "sample")
 STATE_WRITERS = ("kv_write", "pos_add", "pos_set")
-STATE_DTYPES = ("fp32", "bf16", "i32")
+STATE_DTYPES = ("fp32", "bf16", "i32", "i8")
 MAX_STATE = 1024
 OPS = OPS + STATE_OPS
 # linear_q8: folding it would materialise the fp32 weight the format exists to avoid

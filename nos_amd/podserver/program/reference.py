@@ -114,9 +114,9 @@ def _eager(op: str, args: list, attrs: dict, ref: bool = False):
     if op == "sdpa":
         return T.sdpa_ref(args[0], args[1], args[2], attrs.get("causal", False), attrs.get("scale"))
     if op == "kv_write":
-        return kv_write_ref(args[0], args[1], args[2])
+        return kv_write_ref(args[0], args[1], args[2], args[3] if len(args) > 3 else None)
     if op == "sdpa_cache":
-        return sdpa_cache_ref(args[0], args[1], args[2], args[3], attrs.get("scale"))
+        return sdpa_cache_ref(args[0], args[1], args[2], args[3], attrs.get("scale"), *args[4:6])
     if op == "rotary_at":
         return rotary_at_ref(args[0], args[1], args[2], args[3])
     if op == "pos_add":
@@ -130,23 +130,57 @@ def _eager(op: str, args: list, attrs: dict, ref: bool = False):
     raise ProgramError(f"op {op!r}")
 
 
-def kv_write_ref(cache, x, pos):
-    """cache[b, pos[b] + i] = x[b, i] for the rows that fit (in place)."""
+def quantize_kv_rows(x):
+    """The rows x [..., D] as an i8 cache stores them: ``builder.quantize_rows_q8``'s rule on each
+    row, in fp32 whatever x's dtype -- (q int8 [..., D], scale fp32 [...])."""
+    import torch
+
+    xf = x.to(torch.float32)
+    amax = xf.abs().amax(dim=-1)
+    scale = torch.where(amax > 0, amax / 127, torch.ones_like(amax))
+    q = torch.clamp(torch.round(xf / scale[..., None]), -127, 127).to(torch.int8)
+    return q, scale
+
+
+def dequantize_kv_rows(q, scale):
+    """What an i8 cache holds: ``float(q) * scale`` in fp32, one rounding."""
+    import torch
+
+    return q.to(torch.float32) * scale.to(torch.float32)[..., None]
+
+
+def kv_write_ref(cache, x, pos, scales=None):
+    """cache[b, pos[b] + i] = x[b, i] for the rows that fit (in place).  An int8 cache with its
+    ``scales`` [B, L, Hkv] (fp32): the rows quantized (:func:`quantize_kv_rows`) into both."""
+    import torch
+
+    q8 = cache.dtype == torch.int8
+    if q8 != (scales is not None):
+        raise ValueError("kv_write: an int8 cache, and only an int8 cache, takes scales")
     L, S = cache.shape[1], x.shape[1]
     for b in range(cache.shape[0]):
         p0 = int(pos[b])
         n = max(0, min(S, L - p0))
         if p0 >= 0 and n:
-            cache[b, p0:p0 + n] = x[b, :n].to(cache.dtype)
+            if q8:
+                cache[b, p0:p0 + n], scales[b, p0:p0 + n] = quantize_kv_rows(x[b, :n])
+            else:
+                cache[b, p0:p0 + n] = x[b, :n].to(cache.dtype)
     return cache
 
 
-def sdpa_cache_ref(q, kc, vc, pos, scale=None):
+def sdpa_cache_ref(q, kc, vc, pos, scale=None, kscales=None, vscales=None):
     """Query i of sequence b at position pos[b] + i attends the cached keys
-    0 .. min(pos[b] + i, L - 1) (fp32 math, fp64 for an fp64 q; grouped-query K / V heads)."""
+    0 .. min(pos[b] + i, L - 1) (fp32 math, fp64 for an fp64 q; grouped-query K / V heads).
+    int8 caches with their scales: the attention of the values they hold (:func:`dequantize_kv_rows`)."""
     import math
 
     import torch
+
+    if (kc.dtype == torch.int8) != (kscales is not None) or (vc.dtype == torch.int8) != (vscales is not None):
+        raise ValueError("sdpa_cache: int8 caches, and only int8 caches, take scales")
+    if kscales is not None:
+        kc, vc = dequantize_kv_rows(kc, kscales), dequantize_kv_rows(vc, vscales)
 
     B, Sq, H, D = q.shape
     L, Hkv = kc.shape[1], kc.shape[2]

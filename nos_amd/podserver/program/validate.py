@@ -287,25 +287,42 @@ def _infer(node: Node, ins: list[Value], gpu: bool) -> tuple[tuple[int, ...], st
         return q.shape, dt
     if op == "kv_write":
         # cache [B, L, Hkv, D] <- x [B, S, Hkv, D] at rows pos[b] .. pos[b] + S - 1 (rows past L are dropped)
+        # an i8 cache (rows quantized as they are written) takes its fp32 scales state [B, L, Hkv] as input 3
         only()
-        arity(3, 3)
-        c, x, p = ins
-        _req(len(c.shape) == 4 and c.dtype in FLOAT_DTYPES, f"{what}: the cache must be a float [B, L, Hkv, D] state")
-        _req(len(x.shape) == 4 and x.shape[0] == c.shape[0] and x.shape[2:] == c.shape[2:] and x.dtype == c.dtype
+        arity(3, 4)
+        c, x, p = ins[:3]
+        _req(len(c.shape) == 4 and c.dtype in FLOAT_DTYPES + ("i8",),
+             f"{what}: the cache must be a float or i8 [B, L, Hkv, D] state")
+        q8 = c.dtype == "i8"
+        _req(q8 or len(ins) == 3, f"{what}: a {c.dtype} cache takes no scales (input 3 belongs to an i8 cache)")
+        _req(not q8 or len(ins) == 4, f"{what}: an i8 cache needs its scales state as input 3")
+        xdt = "fp32" if q8 else c.dtype
+        _req(len(x.shape) == 4 and x.shape[0] == c.shape[0] and x.shape[2:] == c.shape[2:] and x.dtype == xdt
              and x.shape[1] <= c.shape[1], f"{what}: x must be [{c.shape[0]}, S <= {c.shape[1]}, {c.shape[2]}, "
-             f"{c.shape[3]}] {c.dtype}, got {x.shape} {x.dtype}")
+             f"{c.shape[3]}] {xdt}, got {x.shape} {x.dtype}")
         _pos_vector(p, c.shape[0], what)
+        if q8:
+            _scales_state(ins[3], c, what)
         return c.shape, c.dtype
     if op == "sdpa_cache":
         # q [B, Sq, H, D] at positions pos[b] + i over the cached keys 0 .. pos[b] + i (causal)
+        # i8 caches take their fp32 scales states [B, L, Hkv] as inputs 4 (K) and 5 (V)
         only("scale")
-        arity(4, 4)
-        q, kc, vc, p = ins
+        _req(len(ins) in (4, 6), f"{what}: takes 4 inputs (6 with the scales of i8 caches), got {len(ins)}")
+        q, kc, vc, p = ins[:4]
         _req(len(q.shape) == 4 and len(kc.shape) == 4 and kc.shape == vc.shape and kc.dtype == vc.dtype
              and q.shape[0] == kc.shape[0] and q.shape[3] == kc.shape[3] and q.shape[2] % kc.shape[2] == 0
-             and q.shape[1] <= kc.shape[1] and q.dtype in FLOAT_DTYPES and kc.dtype in FLOAT_DTYPES,
+             and q.shape[1] <= kc.shape[1] and q.dtype in FLOAT_DTYPES and kc.dtype in FLOAT_DTYPES + ("i8",),
              f"{what}: q [B, Sq, H, D], caches [B, L >= Sq, Hkv, D] with H % Hkv == 0 required, got {q.shape}, "
              f"{kc.shape}")
+        q8 = kc.dtype == "i8"
+        _req(q8 or len(ins) == 4, f"{what}: {kc.dtype} caches take no scales (inputs 4 and 5 belong to i8 caches)")
+        _req(not q8 or len(ins) == 6, f"{what}: i8 caches need their scales states as inputs 4 and 5")
+        if q8:
+            _req(q.dtype == "fp32", f"{what}: q must be fp32 over i8 caches (they are an fp32 tenant's storage "
+                 f"format), got {q.dtype}")
+            _scales_state(ins[4], kc, what)
+            _scales_state(ins[5], vc, what)
         _pos_vector(p, q.shape[0], what)
         if "scale" in a:
             _req(isinstance(a["scale"], (int, float)) and not isinstance(a["scale"], bool) and a["scale"] > 0,
@@ -357,6 +374,16 @@ def _infer(node: Node, ins: list[Value], gpu: bool) -> tuple[tuple[int, ...], st
 def _pos_vector(p: Value, b: int, what: str) -> None:
     _req(p.dtype == "i32" and p.shape == (b,), f"{what}: pos must be an i32 [{b}] (a position state), got {p.shape}")
 
+
+def _scales_state(s: Value, cache: Value, what: str) -> None:
+    """The row scales of an i8 cache [B, L, Hkv, D]: an fp32 [B, L, Hkv] state."""
+    _req(s.kind == "state" and s.dtype == "fp32" and s.shape == cache.shape[:3],
+         f"{what}: the scales of an i8 cache must be an fp32 {list(cache.shape[:3])} state, got {s.kind} "
+         f"{s.name!r} {s.dtype} {list(s.shape)}")
+
+
+# the slots an i8 state (a quantized cache) and its scales state may fill
+_Q8_CACHE_SLOTS = {"kv_write": {0: 3}, "sdpa_cache": {1: 4, 2: 5}}   # op -> {cache slot: its scales' slot}
 
 
 def parse_variants(objs: list, payload: bytes | memoryview = b"", gpu: bool = False) -> list[Program]:
@@ -445,6 +472,9 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     root_of = {k: k for k in state}
     dead: set[str] = set()
     sampling = None   # the control state of the program's sample nodes
+    scales_of: dict[str, str] = {}      # a scales state -> the i8 cache (root) whose row scales it holds
+    cache_scales: dict[str, str] = {}   # and back
+    other_use: dict[str, str] = {}      # a state -> the first node naming it as anything but a cache's scales
     ns = obj.get("nodes")
     _req(isinstance(ns, list) and 0 < len(ns) <= MAX_NODES, f"nodes must be a list of 1..{MAX_NODES}")
     nodes = []
@@ -461,11 +491,37 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
         attrs = d.get("attrs") or {}
         _req(isinstance(attrs, dict), "attrs must be an object")
         n = Node(op, list(refs), _name(d.get("output"), "node output"), dict(attrs))
-        for k, r in enumerate(refs):   # an i8 value is a quantized weight: only linear_q8 reads it, as its weight
-            _req(values[r].dtype != "i8" or (op == "linear_q8" and k == 1),
-                 f"node {n.output!r} ({op}): input {r!r} is an i8 param; only linear_q8 takes one, as its weight")
+        # an i8 value is a quantized weight (only linear_q8 reads it, as its weight) or a quantized
+        # cache state (only kv_write / sdpa_cache take it, as their cache)
+        slots = _Q8_CACHE_SLOTS.get(op, {})
+        for k, r in enumerate(refs):
+            if values[r].dtype != "i8":
+                continue
+            if r in root_of:
+                _req(k in slots, f"node {n.output!r} ({op}): input {r!r} is an i8 state; only kv_write and "
+                     f"sdpa_cache take one, as their cache")
+            else:
+                _req(op == "linear_q8" and k == 1, f"node {n.output!r} ({op}): input {r!r} is an i8 param; only "
+                     f"linear_q8 takes one, as its weight")
         shape, dt = _infer(n, [values[r] for r in refs], gpu)
         _req(math.prod(shape) <= MAX_NUMEL, f"node {n.output!r}: output too large")
+        # a scales state is not versioned: it is named only beside versions of its ONE cache, so the
+        # cache's version chain orders its reads and writes too
+        as_scales = set()
+        for ck, sk in slots.items():
+            if values[refs[ck]].dtype != "i8":
+                continue
+            root, sname = root_of[refs[ck]], refs[sk]
+            _req(scales_of.setdefault(sname, root) == root,
+                 f"node {n.output!r} ({op}): scales state {sname!r} belongs to the cache {scales_of[sname]!r}; "
+                 f"it cannot also hold the scales of {root!r}")
+            _req(cache_scales.setdefault(root, sname) == sname,
+                 f"node {n.output!r} ({op}): the cache {root!r} keeps its scales in {cache_scales[root]!r}, "
+                 f"not in {sname!r}")
+            as_scales.add(sk)
+        for k, r in enumerate(refs):
+            if r in state and k not in as_scales:
+                other_use.setdefault(r, f"node {n.output!r} ({op})")
         if op in STATE_WRITERS:
             tgt = refs[0]
             _req(tgt in root_of, f"node {n.output!r} ({op}): updates a state in place; {tgt!r} is not one")
@@ -482,6 +538,13 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     outs = obj.get("outputs")
     _req(isinstance(outs, list) and outs and all(isinstance(o, str) and o in values for o in outs),
          "outputs must name defined values")
+    for k, v in state.items():
+        _req(v.dtype != "i8" or k in cache_scales, f"state {k!r}: state dtype i8 is a quantized K / V cache's; "
+             f"no kv_write / sdpa_cache node names it as its cache")
+    for s_ in scales_of:
+        _req(s_ not in other_use, f"{other_use.get(s_)}: {s_!r} holds the scales of the i8 cache {scales_of[s_]!r}; "
+             f"a scales state is named only beside that cache in kv_write / sdpa_cache")
+        _req(s_ not in outs, f"the scales state {s_!r} of the i8 cache {scales_of[s_]!r} cannot be an output")
     _req(not any(o in root_of for o in outs), "a state (or a version of one) cannot be an output: it is mutable")
     _req(not any(values[o].dtype == "i8" for o in outs), "an i8 param cannot be an output")
     return Program(name, inputs, params, layout, nodes, list(outs), values, payload, state=state,
