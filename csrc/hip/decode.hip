@@ -26,6 +26,9 @@
 //  * nos_argmax -- greedy next tokens, one wave per row;
 //  * nos_sample -- sampled next tokens (temperature, top-k, top-p, seed read
 //    from device memory; Gumbel-max over Philox keyed on the position);
+//  * nos_seen_mark / nos_penalize / nos_stop_step -- stop ids and the repetition penalty of a
+//    stopping tenant: the bitmap of a row's tokens, the penalised logits, and the closing step
+//    (pad finished rows, hold their counters, mark rows that drew a stop id);
 //  * nos_gemv -- y = act(r x W^T + b) + R for M <= 8 rows (a decode step's
 //    every GEMM): weight-streaming, each wave two output columns, lanes over
 //    K with 16-byte weight loads, x rows in LDS (optionally RMS-normalised in
@@ -667,6 +670,94 @@ __global__ __launch_bounds__(NT) void argmax_kernel(const void* __restrict__ x, 
       }
     out[row] = bi >= L ? 0 : bi;  // an all -inf row: index 0
     if (pos != nullptr) pos[row] += pos_n;  // the step's position advance folded in (row = sequence)
+  }
+}
+
+// ------------------------------------------------------------------ stop ids and repetition penalty
+// The stopping tenant's control words, read from device memory when a kernel runs (one captured
+// graph serves every request): ctl = [penalty fp32 bits, pad_id, n_stop (0..4), stop0 .. stop3, 0].
+// All zero: no stop ids, penalty 1.
+
+// seen [B, W] (i32 bitmaps, bit id & 31 of word id >> 5) |= the ids [B, S] of each row; reset: every
+// row cleared first.  One workgroup per row, so clear-then-mark is one launch with no ordering
+// between workgroups; ids outside [0, vocab) (vocab <= 32 W) are dropped.
+__global__ __launch_bounds__(256) void seen_mark_kernel(int* __restrict__ seen, int W, const int* __restrict__ ids,
+                                                        int S, long long ld_ids, int vocab, int reset) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  int* words = seen + (long long)row * W;
+  if (reset) {
+    for (int w = tid; w < W; w += 256) words[w] = 0;
+    __threadfence();   // the clears reach L2, where the atomics below run, before any of them
+    __syncthreads();
+  }
+  for (int s = tid; s < S; s += 256) {
+    const int id = ids[(long long)row * ld_ids + s];
+    if (id >= 0 && id < vocab) atomicOr(&words[id >> 5], (int)(1u << (id & 31)));
+  }
+}
+
+__device__ __forceinline__ float penalized(float x, float p, bool seen) {
+  return seen ? (x < 0.f ? x * p : x / p) : x;   // a true division (correctly rounded), as the reference's
+}
+
+// out[row, v] = x[row, v] where bit v of the row's bitmap is clear, else x < 0 ? x p : x / p (fp32
+// math; bf16 logits rounded once).  x is only read and out is another buffer, so a token seen twice
+// is penalised once.  Each thread 4 consecutive logits; a wave covers 256 of them = 8 bitmap words,
+// loaded by its lanes 0 .. 7 and handed to the others by a shuffle: one load per 32 logits.
+// vec: 16-byte (bf16: 8-byte) loads and stores (the host checked the strides and alignments).
+__global__ __launch_bounds__(256) void penalize_kernel(const void* __restrict__ x, int bf, int L, long long ldx,
+                                                       void* __restrict__ out, long long ldo,
+                                                       const int* __restrict__ seen, int W,
+                                                       const int* __restrict__ ctl, int vec) {
+  const int row = blockIdx.y, lane = threadIdx.x & 63;
+  const long long j = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;   // this thread's first logit
+  const long long wbase = (j - 4 * lane) >> 5;                            // the wave's first bitmap word
+  unsigned word = 0;
+  if (lane < 8 && wbase + lane < W) word = (unsigned)seen[(long long)row * W + wbase + lane];
+  word = (unsigned)__shfl((int)word, lane >> 3, 64);
+  if (j >= L) return;
+  const int cp = ctl[0];
+  const float p = cp == 0 ? 1.f : __int_as_float(cp);
+  const unsigned bits = p == 1.f ? 0u : (word >> ((lane & 7) * 4)) & 15u;   // penalty 1: an exact copy
+  const long long xi = (long long)row * ldx + j, oi = (long long)row * ldo + j;
+  if (vec && j + 3 < L) {
+    const float4 v = ld4(x, xi, bf);
+    const float r0 = penalized(v.x, p, bits & 1u), r1 = penalized(v.y, p, bits & 2u);
+    const float r2 = penalized(v.z, p, bits & 4u), r3 = penalized(v.w, p, bits & 8u);
+    if (bf) {
+      const unsigned lo = (unsigned)nos::f32_to_bf16(r0) | ((unsigned)nos::f32_to_bf16(r1) << 16);
+      const unsigned hi = (unsigned)nos::f32_to_bf16(r2) | ((unsigned)nos::f32_to_bf16(r3) << 16);
+      *reinterpret_cast<uint2*>(static_cast<unsigned short*>(out) + oi) = uint2{lo, hi};
+    } else {
+      *reinterpret_cast<float4*>(static_cast<float*>(out) + oi) = float4{r0, r1, r2, r3};
+    }
+    return;
+  }
+  for (int u = 0; u < 4 && j + u < L; ++u)
+    stf(out, oi + u, penalized(ldf(x, xi + u, bf), p, (bits >> u) & 1u), bf);
+}
+
+// A stopping program's closing trio in one launch, one thread per row (mode: which of the three
+// run; all = 7).  The row's done flag is read first, then
+//  1: ids_out[b] = done ? pad_id : next[b]                      (stop_ids)
+//  2: pos[b] += n unless done                                   (pos_add(pos, done))
+//  4: done[b] |= id in {stop0 .. stop(n_stop - 1)}              (done_mark; id: what 1 wrote, or next[b])
+__global__ void stop_step_kernel(const int* __restrict__ next, int* __restrict__ ids_out, int* __restrict__ pos,
+                                 int* __restrict__ done, const int* __restrict__ ctl, int B, int n, int mode) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int d = done[b];
+  int id = (mode & 5) ? next[b] : 0;
+  if (mode & 1) {
+    if (d) id = ctl[1];
+    ids_out[b] = id;
+  }
+  if ((mode & 2) && !d) pos[b] += n;
+  if (mode & 4) {
+    const int ns = min(max(ctl[2], 0), 4);
+    int hit = 0;
+    for (int k = 0; k < ns; ++k) hit |= id == ctl[3 + k];
+    if (hit) done[b] = d | 1;
   }
 }
 
@@ -1559,6 +1650,43 @@ NOS_API int nos_sample(const void* x, int bf16, int rows, int L, int ldx, int* o
   else
     hipLaunchKernelGGL(sample_kernel<256>, dim3((unsigned)rows), dim3(256), lds, stream, x, bf16, rows, L, ldx, out,
                        pos, pos_n, ctl, lds_row);
+  return (int)hipGetLastError();
+}
+
+// seen [B, W] i32 bitmaps |= ids [B, S] (row stride ld_ids); reset: the rows cleared first
+NOS_API int nos_seen_mark(int* seen, int B, int W, const int* ids, int S, long long ld_ids, int vocab, int reset,
+                          hipStream_t stream) {
+  if (!seen || !ids || B <= 0 || W <= 0 || S <= 0 || ld_ids < S || vocab <= 0 || (long long)vocab > 32ll * W)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(seen_mark_kernel, dim3((unsigned)B), dim3(256), 0, stream, seen, W, ids, S, ld_ids, vocab, reset);
+  return (int)hipGetLastError();
+}
+
+// out [rows, L] (row stride ldo) = the logits x [rows, L] (row stride ldx) under the repetition
+// penalty ctl[0] (fp32 bits; 0 or 1.0: a copy) on the tokens of seen [rows, W], 32 W >= L
+NOS_API int nos_penalize(const void* x, int bf16, int rows, int L, long long ldx, void* out, long long ldo,
+                         const int* seen, int W, const int* ctl, hipStream_t stream) {
+  if (!x || !out || !seen || !ctl || x == out || rows <= 0 || rows > 65535 || L <= 0 || ldx < L || ldo < L ||
+      (bf16 != 0 && bf16 != 1) || 32ll * W < L)
+    return (int)hipErrorInvalidValue;
+  const size_t al = bf16 ? 8 : 16;
+  const int vec = ldx % 4 == 0 && ldo % 4 == 0 && reinterpret_cast<size_t>(x) % al == 0 &&
+                  reinterpret_cast<size_t>(out) % al == 0;
+  hipLaunchKernelGGL(penalize_kernel, dim3((unsigned)((L + 1023) / 1024), (unsigned)rows), dim3(256), 0, stream, x,
+                     bf16, L, ldx, out, ldo, seen, W, ctl, vec);
+  return (int)hipGetLastError();
+}
+
+// the closing steps of a stopping program over B rows (stop_step_kernel); mode: 1 ids_out =
+// done ? pad : next, 2 pos += n unless done, 4 done |= id is a stop id -- the pointers a mode
+// needs must be there
+NOS_API int nos_stop_step(const int* next, int* ids_out, int* pos, int* done, const int* ctl, int B, int n, int mode,
+                          hipStream_t stream) {
+  if (!done || B <= 0 || n < 0 || mode <= 0 || mode > 7 || ((mode & 5) && (!next || !ctl)) || ((mode & 1) && !ids_out) ||
+      ((mode & 2) && !pos))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(stop_step_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, next, ids_out, pos,
+                     done, ctl, B, n, mode);
   return (int)hipGetLastError();
 }
 

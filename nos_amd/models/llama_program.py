@@ -112,7 +112,8 @@ def llama_program(model, seq: int, batch: int = 1, dtype: str = "fp32",
 
 def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, dtype: str = "fp32",
                           extend: tuple[int, ...] = (), sampling: bool = False,
-                          weights: str = "fp32", kv: str | None = None) -> tuple[list[dict], bytes]:
+                          weights: str = "fp32", kv: str | None = None,
+                          stopping: bool = False) -> tuple[list[dict], bytes]:
     """A STATEFUL generation tenant: ``[prefill, decode, *extends]`` programs
     over one weight payload and one state -- per layer a K and a V cache
     ``[batch, max_len, kv_heads, head_dim]`` plus the position counter
@@ -157,7 +158,25 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     the server does quantize: every K (after its rotation) and V row as it is
     written, by ``quantize_rows_q8``'s rule, and every program attends the
     rows as the cache holds them -- an HF model run with
-    :func:`kv_q8_roundtrip_cache` is the model such a tenant computes."""
+    :func:`kv_q8_roundtrip_cache` is the model such a tenant computes.
+
+    ``stopping`` (any dtype, with or without the options above): generation
+    that ends, with transformers' ``generate(eos_token_id=[...],
+    pad_token_id=..., repetition_penalty=...)`` semantics, all on the device.
+    The programs also declare ``done`` (i32 [batch]: the row has emitted a stop
+    id), ``seen`` (i32 [batch, ceil(vocab / 32)]: the bitmap of the ids the
+    row's sequence holds, prompt and fed-back ids) and the control state
+    ``stopping`` (i32 [8], filled by the server from each request's
+    ``"stopping"`` field: up to four stop ids, a pad id, a repetition
+    penalty).  Every program marks its input ids (the prefill clears the
+    bitmaps and ``done`` first), draws from the penalised logits (the
+    ``logits`` output stays raw) and closes with ``pos_add(pos, done)`` ->
+    ``stop_ids`` -> ``done_mark``: a row's counter advances in every step it
+    entered unfinished (the one that emits its stop id included), the stop id
+    itself is emitted and every later id of the row is the pad id, and a
+    finished row's counter -- so its cache rows below it -- never changes
+    again.  All-zero control words (a request without the field): exactly the
+    plain tenant's tokens."""
     if not 0 < prompt_len <= max_len:
         raise ValueError(f"prompt_len must be in [1, {max_len}]")
     if weights not in ("fp32", "int8"):
@@ -183,7 +202,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     payload = b""
     for seq, reset in chunks:
         b = Builder(f"llama-h{d}-l{cfg.num_hidden_layers}-{dtype}{'-q8' if q8 else ''}{'-kvq8' if kvq8 else ''}-"
-                    f"{'prefill' if reset else 'step'}{seq}")
+                    f"{'stop-' if stopping else ''}{'prefill' if reset else 'step'}{seq}")
         ids = b.input("input_ids", [batch, seq], "i32")
         P = lambda k: b.param(k, sd[k], dtype)  # noqa: E731
 
@@ -199,6 +218,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
         rc, rs = b.param("rope.cos", cos, "fp32"), b.param("rope.sin", sin, "fp32")
         b.state("pos", [batch], "i32")
         ctl = b.state("sampling", [4], "i32") if sampling else None
+        done, seen, sctl = b.stopping_states(batch, cfg.vocab_size) if stopping else (None, None, None)
         cshape = [batch, max_len, nkv, hd]
         if kvq8:   # ((K cache, its scales), (V cache, its scales)) per layer
             caches = [(b.cache_q8(f"kc{i}", f"ks{i}", cshape), b.cache_q8(f"vc{i}", f"vs{i}", cshape))
@@ -241,8 +261,19 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
         h = b.op("rmsnorm", h, P("model.norm.weight"), eps=eps)
         # a tied head reads the embedding table: quantized, it is a copy of its own (the table stays fp32)
         logits = lin(h, "lm_head.weight", head, out="logits") if q8 else lin(h, head, out="logits")
-        nxt = b.op("sample", logits, ctl, p, out="next_ids") if sampling else b.op("argmax", logits, out="next_ids")
-        b.op("pos_add", p, n=seq)
+        if stopping:
+            # the input ids join the row's bitmap, the seen tokens' logits are penalised (the ``logits``
+            # output stays raw), then the draw; a finished row emits the pad id and keeps its counter,
+            # and a row that emits a stop id is finished from the next step on
+            dn = b.op("pos_set", done, value=0) if reset else done
+            pen = b.op("penalize", logits, b.op("seen_mark", seen, ids, reset=reset), sctl)
+            raw = b.op("sample", pen, ctl, p) if sampling else b.op("argmax", pen)
+            b.op("pos_add", p, dn, n=seq)
+            nxt = b.op("stop_ids", raw, dn, sctl, out="next_ids")
+            b.op("done_mark", dn, nxt, sctl)
+        else:
+            nxt = b.op("sample", logits, ctl, p, out="next_ids") if sampling else b.op("argmax", logits, out="next_ids")
+            b.op("pos_add", p, n=seq)
         prog, w = b.build([logits, nxt])
         progs.append(prog)
         payload = w

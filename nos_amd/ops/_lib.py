@@ -120,6 +120,10 @@ _SIGS = {
     "nos_argmax": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     "nos_sample_row_in_lds": [c_int],
     "nos_sample": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    # stop ids and repetition penalty (decode.hip)
+    "nos_seen_mark": [c_void_p, c_int, c_int, c_void_p, c_int, c_ll, c_int, c_int, c_void_p],
+    "nos_penalize": [c_void_p, c_int, c_int, c_int, c_ll, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p],
+    "nos_stop_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "nos_gemv": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                  c_int, c_int, c_int, c_float, c_void_p],
     "nos_gemv_partials": [c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,

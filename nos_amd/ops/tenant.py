@@ -1071,6 +1071,175 @@ def sample(x: torch.Tensor, ctl: torch.Tensor, pos: torch.Tensor | None = None, 
     return out
 
 
+# ------------------------------------------------------------------ stop ids and repetition penalty
+STOP_CTL_WORDS, MAX_STOP_IDS = 8, 4
+
+
+def stopping_ctl(stop_ids=(), pad_id: int | None = None, repetition_penalty: float = 1.0,
+                 id_bound: int | None = None) -> np.ndarray:
+    """The eight i32 control words the stopping ops read from device memory:
+    ``[penalty as fp32 bits, pad_id, n_stop, stop0, stop1, stop2, stop3, 0]``
+    (unused stop slots 0).  ``stop_ids``: at most four token ids that end a
+    row; ``pad_id``: what a finished row emits from then on (default: the
+    first stop id, 0 without one); ``repetition_penalty``: finite and > 0,
+    1 = off.  ``id_bound``: stop and pad ids must lie in [0, id_bound).  The
+    defaults pack to all zeros but for the penalty's 1.0, which the kernels
+    treat as zero bits: no stop ids, no penalty."""
+    if isinstance(stop_ids, int) and not isinstance(stop_ids, bool):
+        stop_ids = [stop_ids]
+    if not isinstance(stop_ids, (list, tuple)) or len(stop_ids) > MAX_STOP_IDS:
+        raise ValueError(f"stopping: stop_ids must be a list of at most {MAX_STOP_IDS} token ids, got {stop_ids!r}")
+
+    def token(v, what):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            raise ValueError(f"stopping: {what} must be an int token id, got {v!r}")
+        hi = (1 << 31) if id_bound is None else int(id_bound)
+        if not 0 <= v < hi:
+            raise ValueError(f"stopping: {what} must lie in [0, {hi}), got {v!r}")
+        return int(v)
+
+    stops = [token(v, "stop_ids") for v in stop_ids]
+    pad = token(pad_id, "pad_id") if pad_id is not None else (stops[0] if stops else 0)
+    p = repetition_penalty
+    if not isinstance(p, (int, float)) or isinstance(p, bool) or not math.isfinite(p) or not p > 0:
+        raise ValueError(f"stopping: repetition_penalty must be finite and > 0, got {p!r}")
+    if not math.isfinite(float(np.float32(p))) or not float(np.float32(p)) > 0:
+        raise ValueError(f"stopping: repetition_penalty must be a positive finite fp32, got {p!r}")
+    bits = int(np.array([p], dtype=np.float32).view(np.int32)[0])
+    return np.array([bits, pad, len(stops), *stops, *([0] * (MAX_STOP_IDS - len(stops))), 0], dtype=np.int32)
+
+
+def _stop_ctl(ctl: torch.Tensor, like: torch.Tensor, what: str) -> torch.Tensor:
+    if ctl.dtype != torch.int32 or ctl.numel() != STOP_CTL_WORDS or not ctl.is_contiguous() or ctl.device != like.device:
+        raise ValueError(f"{what}: ctl must be {STOP_CTL_WORDS} contiguous i32 control words on the operands' device")
+    return ctl
+
+
+def _i32_rows(t: torch.Tensor, n: int, what: str) -> torch.Tensor:
+    if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous i32 tensor of {n} elements, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def seen_mark(seen: torch.Tensor, ids: torch.Tensor, reset: bool = False, vocab: int | None = None) -> torch.Tensor:
+    """seen [B, W] (i32 bitmaps: bit ``id & 31`` of word ``id >> 5`` stands for
+    token ``id``; token 31 is word 0's sign bit) |= the ids [B, S] (i32) of
+    each row, in place; ``reset``: every row cleared first.  Ids outside
+    [0, vocab) (default and at most 32 W) are ignored.  Returns ``seen``."""
+    if seen.dtype != torch.int32 or seen.dim() != 2 or not seen.is_contiguous():
+        raise ValueError(f"seen_mark: seen must be a contiguous i32 [B, W] bitmap, got {seen.dtype} {tuple(seen.shape)}")
+    B, W = seen.shape
+    if ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[0] != B or ids.device != seen.device:
+        raise ValueError(f"seen_mark: ids must be i32 [{B}, S] on seen's device, got {ids.dtype} {tuple(ids.shape)}")
+    vocab = 32 * W if vocab is None else int(vocab)
+    if not 0 < vocab <= 32 * W:
+        raise ValueError(f"seen_mark: vocab must lie in [1, {32 * W}], got {vocab}")
+    if not seen.is_cuda:
+        if reset:
+            seen.zero_()
+        idl = ids.to(torch.int64)
+        bits = torch.zeros((B, 32 * W), dtype=torch.bool)
+        ok = (idl >= 0) & (idl < vocab)
+        rows = torch.arange(B).view(B, 1).expand_as(idl)
+        bits[rows[ok], idl[ok]] = True
+        words = (bits.view(B, W, 32).to(torch.int64) << torch.arange(32)).sum(-1)       # 0 .. 2^32 - 1
+        seen |= torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32)
+        return seen
+    if ids.stride(1) != 1:
+        ids = ids.contiguous()
+    _lib.check(_lib.lib().nos_seen_mark(seen.data_ptr(), B, W, ids.data_ptr(), ids.shape[1], ids.stride(0), vocab,
+                                        int(bool(reset)), _stream()), "nos_seen_mark")
+    return seen
+
+
+def seen_bits(seen: torch.Tensor, vocab: int) -> torch.Tensor:
+    """The bitmaps [B, W] as a bool mask [B, vocab]."""
+    w = seen.to(torch.int64).cpu()
+    return ((w[:, :, None] >> torch.arange(32)) & 1).bool().view(seen.shape[0], -1)[:, :vocab]
+
+
+def penalize(x: torch.Tensor, seen: torch.Tensor, ctl: torch.Tensor) -> torch.Tensor:
+    """The logits x [..., V] under the repetition penalty p of the control
+    words ``ctl`` (:func:`stopping_ctl`; read on the device), a new tensor of
+    x's shape and dtype: ``x`` where the row's bit in ``seen`` [rows, ceil(V /
+    32)] is clear, else ``x * p`` for ``x < 0`` and ``x / p`` otherwise -- fp32
+    math with a true division, bf16 logits rounded once; penalty bits 0 or
+    p = 1: an exact copy.  x is only read, so a token seen twice is penalised
+    once (transformers' gather / scatter)."""
+    L = x.shape[-1]
+    x2 = x.reshape(-1, L)
+    rows, W = x2.shape[0], -(-L // 32)
+    if seen.dtype != torch.int32 or tuple(seen.shape) != (rows, W) or not seen.is_contiguous() or seen.device != x.device:
+        raise ValueError(f"penalize: seen must be a contiguous i32 [{rows}, {W}] bitmap on x's device, got "
+                         f"{seen.dtype} {tuple(seen.shape)}")
+    _stop_ctl(ctl, x, "penalize")
+    if not x.is_cuda:
+        _bf(x)
+        p = ctl[:1].view(torch.float32) if int(ctl[0]) else torch.ones(1)
+        xf = x2.float()
+        hit = seen_bits(seen, L) & bool(p.item() != 1.0)
+        return torch.where(hit, torch.where(xf < 0, xf * p, xf / p), xf).to(x.dtype).reshape(x.shape)
+    if x2.stride(-1) != 1:
+        x2 = x2.contiguous()
+    out = torch.empty((rows, L), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.lib().nos_penalize(x2.data_ptr(), _bf(x2), rows, L, x2.stride(0), out.data_ptr(), L,
+                                       seen.data_ptr(), W, ctl.data_ptr(), _stream()), "nos_penalize")
+    return out.reshape(x.shape)
+
+
+def stop_step(next_ids: torch.Tensor | None, pos: torch.Tensor | None, done: torch.Tensor,
+              ctl: torch.Tensor | None, n: int = 1, mode: int = 7) -> torch.Tensor | None:
+    """The closing steps of a stopping program over B rows in one launch;
+    each row's ``done`` flag is read first, then (``mode`` bits):
+
+    * 1 -- ``stop_ids``: the returned ids (next_ids' shape) are ``pad_id``
+      for a finished row, else ``next_ids``;
+    * 2 -- ``pos_add(pos, done)``: ``pos += n`` for unfinished rows, in place;
+    * 4 -- ``done_mark``: ``done |= id in the stop ids`` in place (id: what 1
+      returned, or ``next_ids`` itself without 1).
+
+    ``ctl``: :func:`stopping_ctl`'s words on the device.  Returns the ids
+    (mode 1) or None."""
+    B = done.numel()
+    _i32_rows(done, B, "stop_step: done")
+    if mode & 5:
+        _i32_rows(next_ids, B, "stop_step: next ids")
+        _stop_ctl(ctl, done, "stop_step")
+    if mode & 2:
+        _i32_rows(pos, B, "stop_step: pos")
+    if not 0 < mode <= 7 or n < 0:
+        raise ValueError(f"stop_step: mode {mode}, n {n}")
+    if not done.is_cuda:
+        d = done.reshape(-1) != 0
+        ids = next_ids.reshape(-1).clone() if mode & 5 else None
+        c = ctl.tolist() if mode & 5 else None
+        if mode & 1:
+            ids[d] = c[1]
+        if mode & 2:
+            pos += (~d).to(torch.int32).view(pos.shape) * int(n)
+        if mode & 4:
+            stops = torch.tensor(c[3:3 + min(max(c[2], 0), MAX_STOP_IDS)], dtype=torch.int32)
+            done |= torch.isin(ids, stops).to(torch.int32).view(done.shape)
+        return ids.view(next_ids.shape) if mode & 1 else None
+    out = torch.empty_like(next_ids) if mode & 1 else None
+    _lib.check(_lib.lib().nos_stop_step(_ptr(next_ids) if mode & 5 else None, _ptr(out),
+                                        _ptr(pos) if mode & 2 else None, done.data_ptr(),
+                                        _ptr(ctl) if mode & 5 else None, B, int(n), int(mode), _stream()),
+               "nos_stop_step")
+    return out
+
+
+def stop_ids(next_ids: torch.Tensor, done: torch.Tensor, ctl: torch.Tensor) -> torch.Tensor:
+    """``done[b] ? pad_id : next_ids[b]`` (:func:`stop_step`, mode 1)."""
+    return stop_step(next_ids, None, done, ctl, mode=1)
+
+
+def done_mark(done: torch.Tensor, ids: torch.Tensor, ctl: torch.Tensor) -> torch.Tensor:
+    """``done[b] |= ids[b] is a stop id`` in place (:func:`stop_step`, mode 4); returns ``done``."""
+    stop_step(ids, None, done, ctl, mode=4)
+    return done
+
+
 GEMV_MAX_ROWS = 8
 EPI_SILU = 64 # csrc/hip/epilogue.h; decode.hip's GEMV: SiLU epilogue
 EPI_GLU = 256  # decode.hip's GEMV: W = [gate; up], y = silu(gate) * up

@@ -153,7 +153,7 @@ class PodClient:
         raise PodServerGone(f"pod server did not come back within {self.reconnect_s} s: {last}")
 
     def infer(self, x: np.ndarray | None = None, outputs: bool | list = False,
-              sampling: dict | None = None) -> tuple[list[np.ndarray], dict]:
+              sampling: dict | None = None, stopping: dict | None = None) -> tuple[list[np.ndarray], dict]:
         """One inference on the pod's model; ``x`` replaces the resident input
         (one of the registered input shapes; without ``x`` the primary
         shape's resident input runs).  ``outputs``: return every output
@@ -161,10 +161,15 @@ class PodClient:
         reply carries its counters (``rep["state"]``, e.g. the position).
         ``sampling``: ``{"temperature", "top_k", "top_p", "seed"}`` (any
         subset) for a tenant whose programs end in ``sample``; without it the
-        request is greedy."""
+        request is greedy.  ``stopping``: ``{"stop_ids", "pad_id",
+        "repetition_penalty"}`` (any subset) for a tenant registered with
+        stopping programs; the reply's ``state`` then carries the rows'
+        ``done`` flags beside ``pos``."""
         req = {"op": "infer", "outputs": outputs}
         if sampling:
             req["sampling"] = dict(sampling)
+        if stopping:
+            req["stopping"] = dict(stopping)
         if x is None:
             payload = b""
         else:
@@ -188,7 +193,8 @@ class PodClient:
 
     def generate(self, prompt: np.ndarray, max_new_tokens: int, next_output: int = -1,
                  server_loop: bool = True, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
-                 seed: int = 0) -> tuple[np.ndarray, dict]:
+                 seed: int = 0, eos_token_id: int | list | None = None, pad_token_id: int | None = None,
+                 repetition_penalty: float = 1.0) -> tuple[np.ndarray, dict]:
         """Generation on a stateful decoder tenant
         (models/llama_program.llama_decode_programs): the prompt ids [B, P]
         go to the prefill variant, then the decode variant runs once per new
@@ -202,40 +208,72 @@ class PodClient:
         defaults, for a tenant registered with sampling programs
         (``llama_decode_programs(..., sampling=True)``): the ids are then
         drawn on the device, the same ones on either path and on every
-        repeat of the sequence with the same seed.  Returns (ids [B,
-        max_new_tokens], timings: the prefill's round trip, every decode
-        step's (server loop: the loop's time / steps), the server's final
-        counters)."""
+        repeat of the sequence with the same seed.
+
+        ``eos_token_id`` (an int or a list of at most four), ``pad_token_id``
+        (default: the first stop id) and ``repetition_penalty``, for a tenant
+        registered with stopping programs (``llama_decode_programs(...,
+        stopping=True)``), are transformers' ``generate`` arguments of those
+        names: a row ends with its first stop id and emits the pad id from
+        then on, and the generation ends once every row has -- the server
+        loop leaves its loop then, the per-request path stops sending.
+
+        Returns (ids [B, n], timings): n = ``max_new_tokens``, or fewer with
+        stop ids (what ``generate(...)[:, P:]`` of transformers returns; 1
+        when the prefill draws every row's stop id); the prefill's round
+        trip, every decode step's (server loop: the loop's time / steps),
+        ``steps_run`` (the decode steps the server ran: with stop ids up to
+        two check windows more than n - 1) and the server's final counters."""
         prompt = np.asarray(prompt)
         B = prompt.shape[0]
         given = {"temperature": temperature, "top_k": top_k, "top_p": top_p, "seed": seed}
         sampling = {k: v for k, v in given.items() if v != _GREEDY[k]}   # older servers keep serving greedy clients
+        stops = [] if eos_token_id is None else ([eos_token_id] if isinstance(eos_token_id, (int, np.integer))
+                                                 else list(eos_token_id))
+        stopping = {}
+        if stops:
+            stopping["stop_ids"] = [int(v) if isinstance(v, np.integer) else v for v in stops]
+        if pad_token_id is not None:
+            stopping["pad_id"] = int(pad_token_id) if isinstance(pad_token_id, np.integer) else pad_token_id
+        if repetition_penalty != 1.0:
+            stopping["repetition_penalty"] = repetition_penalty
+        extra = {**({"sampling": sampling} if sampling else {}), **({"stopping": stopping} if stopping else {})}
+
+        def ended(rep) -> bool:
+            done = (rep.get("state") or {}).get("done")
+            return bool(stops) and done is not None and all(done)
+
         t0 = time.monotonic()
-        outs, rep = self.infer(prompt, outputs=[next_output], sampling=sampling)
+        outs, rep = self.infer(prompt, outputs=[next_output], **extra)
         t1 = time.monotonic()
         tok = outs[0].reshape(B, -1)[:, -1].astype(np.int32)
         toks, steps = [tok], []
-        n = max_new_tokens - 1
+        n = 0 if ended(rep) else max_new_tokens - 1
+        run = 0
         if server_loop and n > 0:
             wire = _wire(tok.reshape(B, 1), self.input_dtype, "input")
             req = {"op": "generate", "steps": n, "output": next_output, "shape": [B, 1],
-                   "dtype": "i32" if wire.dtype == np.int32 else "f32"}
-            if sampling:
-                req["sampling"] = sampling
+                   "dtype": "i32" if wire.dtype == np.int32 else "f32", **extra}
             s0 = time.monotonic()
             rep, data = self._call(req, wire.tobytes())
             dt = time.monotonic() - s0
-            ids = P.unpack_arrays(rep["outputs"], data)[0].reshape(n, B, -1)[:, :, -1].astype(np.int32)
+            out = P.unpack_arrays(rep["outputs"], data)[0]
+            ids = out.reshape(out.shape[0], B, -1)[:, :, -1].astype(np.int32)
             toks += list(ids)
-            steps = [dt / n] * n
+            run = int(rep.get("steps_run", n))
+            steps = [dt / run] * len(ids)
         else:
             for _ in range(n):
                 s0 = time.monotonic()
-                outs, rep = self.infer(tok.reshape(B, 1), outputs=[next_output], sampling=sampling)
+                outs, rep = self.infer(tok.reshape(B, 1), outputs=[next_output], **extra)
                 steps.append(time.monotonic() - s0)
                 tok = outs[0].reshape(B, -1)[:, -1].astype(np.int32)
                 toks.append(tok)
-        return np.stack(toks, axis=1), {"prefill_s": t1 - t0, "step_s": steps, "state": rep.get("state")}
+                run += 1
+                if ended(rep):
+                    break
+        return np.stack(toks, axis=1), {"prefill_s": t1 - t0, "step_s": steps, "state": rep.get("state"),
+                                        "steps_run": run}
 
     def train_step(self, x: np.ndarray, target: np.ndarray) -> dict:
         """One optimisation step of a training tenant on (x, target): the

@@ -96,6 +96,15 @@ class Builder:
         writes them, by :func:`quantize_rows_q8`'s rule)."""
         return self.state(name, shape, "i8"), self.state(scales, list(shape)[:3], "fp32")
 
+    def stopping_states(self, batch: int, vocab: int, done: str = "done", seen: str = "seen",
+                        ctl: str = "stopping") -> tuple[str, str, str]:
+        """The three states of a stopping program (stop ids, repetition penalty): the rows' ``done``
+        flags i32 [batch], the ``seen`` bitmaps i32 [batch, ceil(vocab / 32)] (bit ``id & 31`` of word
+        ``id >> 5``: token ``id`` is in the row's sequence) and the control words ``ctl`` i32 [8] the
+        server fills from each request's ``"stopping"`` field (``ops.tenant.stopping_ctl``)."""
+        return (self.state(done, [batch], "i32"), self.state(seen, [batch, -(-vocab // 32)], "i32"),
+                self.state(ctl, [8], "i32"))
+
     def op(self, op: str, *inputs: str, out: str | None = None, **attrs) -> str:
         self._n += 1
         out = out or f"%{self._n}"

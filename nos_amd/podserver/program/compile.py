@@ -9,7 +9,7 @@ import os
 from dataclasses import dataclass, field
 
 from .graph import Program
-from .ir import BINARY, NATIVE_KINDS, NEVER_FOLD, STATE_WRITERS, UNARY, ProgramError, torch_dtype
+from .ir import BINARY, NATIVE_KINDS, NEVER_FOLD, STATE_WRITERS, STOP_KINDS, UNARY, ProgramError, torch_dtype
 from .reference import _eager
 
 
@@ -78,6 +78,8 @@ class Lowered:
                 self._fold_decode_combines(steps)
             if "argmax_pos" not in skip:
                 steps = self._fuse_argmax_pos(steps)
+            if "stop_step" not in skip:
+                steps = self._fuse_stop_step(steps)
             steps = self._fuse_gemv_glu(steps)
             if "combine_gemv" not in skip:
                 steps = self._fold_combine_into_gemv(steps)
@@ -95,6 +97,9 @@ class Lowered:
         self._derived = None
         self.stats["kernels"] = sum(1 for s in self.steps if s.kind in NATIVE_KINDS)
         self.stats["q8_linears"] = sum(1 for s in self.steps if s.kind == "linear_q8")
+        if "stop_steps_fused" in self.stats:   # a stopping program: the launches its stopping ops cost
+            self.stats["stop_launches"] = sum(1 for s in self.steps if s.kind in STOP_KINDS
+                                              or (s.kind == "pos_add" and len(s.inputs) == 2))
 
     def _memo(self, tag: str, sources: list, extra, make):
         """``make()`` once per recipe: ``tag`` + the identities of the source
@@ -176,7 +181,7 @@ class Lowered:
         for s in steps:
             if s.kind == "pos_set":
                 known[s.output] = int(s.attrs["value"])
-            elif s.kind == "pos_add" and s.inputs[0] in known:
+            elif s.kind == "pos_add" and s.inputs[0] in known and len(s.inputs) == 1:
                 known[s.output] = known[s.inputs[0]] + int(s.attrs["n"])
             elif s.kind == "rotary_at" and s.inputs[3] in known and all(i in self.consts for i in s.inputs[1:3]):
                 p0, S = known[s.inputs[3]], self._shape(s.inputs[0])[1]
@@ -1171,7 +1176,7 @@ class Lowered:
             self.stats["pos_add_into_sample"] = 0
         uses = self._consumers(steps, self.outputs)
         for k, p in enumerate(steps):
-            if p.kind != "pos_add" or k == 0:
+            if p.kind != "pos_add" or k == 0 or len(p.inputs) != 1:   # pos_add(pos, done): _fuse_stop_step's
                 continue
             a = steps[k - 1]
             shp = tuple(self._shape(a.inputs[0])) if a.kind in ("argmax", "sample") else ()
@@ -1185,6 +1190,29 @@ class Lowered:
             a.attrs = {**a.attrs, "pos_out": p.output, "pos_n": int(p.attrs["n"])}
             self.stats["pos_add_into_" + a.kind] = 1
             return steps[:k] + steps[k + 1:]
+        return steps
+
+    def _fuse_stop_step(self, steps: list[_Step]) -> list[_Step]:
+        """A stopping program's closing trio -- ``pos_add(pos, done)``, ``stop_ids(next, done, ctl)``,
+        ``done_mark(done, ids, ctl)`` on that ``stop_ids``' output, adjacent, over the same ``done``
+        version and control words -- becomes ONE ``stop_step``: a thread per row reads the flag,
+        then writes the id, the counter and the flag (``ops.tenant.stop_step``)."""
+        n = 0
+        for k in range(len(steps) - 2):
+            p, i, d = steps[k:k + 3]
+            if (p.kind != "pos_add" or len(p.inputs) != 2 or i.kind != "stop_ids" or d.kind != "done_mark"
+                    or not p.inputs[1] == i.inputs[1] == d.inputs[0] or i.inputs[2] != d.inputs[2]
+                    or d.inputs[1] != i.output or i.inputs[0] in (p.inputs[0], p.inputs[1])
+                    or tuple(self._shape(p.inputs[0])) != tuple(self._shape(p.inputs[1]))
+                    or math.prod(self._shape(i.inputs[0])) != self._shape(p.inputs[0])[0]):
+                continue
+            fused = _Step("stop_step", [i.inputs[0], p.inputs[0], p.inputs[1], i.inputs[2]], i.output,
+                          {"n": int(p.attrs["n"]), "pos_out": p.output, "done_out": d.output})
+            steps = steps[:k] + [fused] + steps[k + 3:]
+            n = 1
+            break
+        if any(s.kind in STOP_KINDS for s in steps):
+            self.stats["stop_steps_fused"] = n
         return steps
 
     def _prep_conv_weights(self, steps: list[_Step]) -> None:

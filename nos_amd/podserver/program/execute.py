@@ -153,6 +153,20 @@ class CompiledProgram(Lowered):
                                  scales=sc or None)
             elif k == "rotary_at":
                 y = T.rotary_at(a[0], a[1], a[2], a[3])
+            elif k == "stop_step":   # pos_add(pos, done) / stop_ids / done_mark: next ids, pos, done, ctl
+                y = T.stop_step(a[0], a[1], a[2], a[3], n=int(s.attrs["n"]), mode=7)
+                env[s.attrs["pos_out"]], env[s.attrs["done_out"]] = a[1], a[2]
+            elif k == "pos_add" and len(a) == 2:   # finished rows (done) keep their counter
+                T.stop_step(None, a[0], a[1], None, n=int(s.attrs["n"]), mode=2)
+                y = a[0]
+            elif k == "seen_mark":
+                y = T.seen_mark(a[0], a[1], reset=bool(s.attrs.get("reset", False)))
+            elif k == "penalize":
+                y = T.penalize(a[0], a[1], a[2])
+            elif k == "stop_ids":
+                y = T.stop_ids(a[0], a[1], a[2])
+            elif k == "done_mark":
+                y = T.done_mark(a[0], a[1], a[2])
             elif k in ("pos_add", "pos_set"):
                 y = T.pos_update(a[0], add=k == "pos_add", n=int(s.attrs["n" if k == "pos_add" else "value"]))
             elif k == "argmax" and s.attrs.get("pos_out"):   # the step's pos_add folded in

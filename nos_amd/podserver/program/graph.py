@@ -73,6 +73,9 @@ class Program:
     state: dict[str, Value] = field(default_factory=dict)        # persistent buffers (K / V caches, positions)
     state_root: dict[str, str] = field(default_factory=dict)     # a state's in-place versions -> the state
     sampling_state: str | None = None    # the i32 [4] state its ``sample`` nodes read (the server fills it per request)
+    stopping_state: str | None = None    # the i32 [8] state its stopping ops read (stop ids, pad id, penalty; per request)
+    done_state: str | None = None        # the i32 [B] flags ``done_mark`` sets (a row that drew a stop id)
+    seen_state: str | None = None        # the i32 [B, ceil(vocab / 32)] bitmap ``seen_mark`` fills
 
     # ------------------------------------------------------------ accounting
     @property

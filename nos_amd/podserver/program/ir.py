@@ -122,6 +122,15 @@ OPS = ("linear", "layernorm", "attention", *BINARY, *UNARY, "cat", "slice", "res
 # the old version dead from then on, so in-place equals SSA semantics)
 STATE_OPS = ("kv_write", "sdpa_cache", "rotary_at", "pos_add", "pos_set", "argmax", "sample")
 STATE_WRITERS = ("kv_write", "pos_add", "pos_set")
+# stop ids and repetition penalty (a stopping tenant): seen_mark(seen, ids) sets the ids' bits in
+# the rows' bitmaps, penalize(logits, seen, ctl) penalises the seen tokens' logits,
+# stop_ids(next, done, ctl) pads finished rows, done_mark(done, ids, ctl) finishes rows that
+# drew a stop id; pos_add takes ``done`` as a second input (finished rows keep their counter)
+STOP_CTL_WORDS = 8           # [penalty fp32 bits, pad_id, n_stop, stop0 .. stop3, 0] (ops.tenant.stopping_ctl)
+MAX_STOP_IDS = 4
+STOP_OPS = ("seen_mark", "penalize", "stop_ids", "done_mark")
+STATE_OPS = STATE_OPS + STOP_OPS
+STATE_WRITERS = STATE_WRITERS + ("seen_mark", "done_mark")
 STATE_DTYPES = ("fp32", "bf16", "i32", "i8")
 MAX_STATE = 1024
 OPS = OPS + STATE_OPS
@@ -130,7 +139,10 @@ NEVER_FOLD = ("attention", "sdpa", "linear_q8", *STATE_OPS)
 # step kinds that run a gfx950 kernel of libnos_hip.so (CompiledProgram.stats["kernels"])
 NATIVE_KINDS = ("linear", "linear_ln", "linear_rms", "ln_qkv_attention", "attention", "layernorm", "conv2d", "matmul",
                 "softmax", "embedding", "rmsnorm", "rotary", "sdpa", "patches", "unary", "kv_write", "sdpa_cache",
-                "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu", "linear_q8")
+                "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu", "linear_q8", *STOP_OPS, "stop_step")
+# the steps a stopping program adds to a plain one (CompiledProgram.stats["stop_launches"]); stop_step:
+# the pos_add(pos, done) / stop_ids / done_mark trio fused into one launch
+STOP_KINDS = (*STOP_OPS, "stop_step")
 GEMM_OPS = ("linear", "conv2d")
 
 

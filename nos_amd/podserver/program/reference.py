@@ -119,8 +119,19 @@ def _eager(op: str, args: list, attrs: dict, ref: bool = False):
         return sdpa_cache_ref(args[0], args[1], args[2], args[3], attrs.get("scale"), *args[4:6])
     if op == "rotary_at":
         return rotary_at_ref(args[0], args[1], args[2], args[3])
+    if op == "pos_add" and len(args) == 2:   # a stopping tenant's: finished rows keep their counter
+        T.stop_step(None, args[0], args[1], None, n=int(attrs["n"]), mode=2)
+        return args[0]
     if op == "pos_add":
         return args[0].add_(int(attrs["n"]))
+    if op == "seen_mark":
+        return T.seen_mark(args[0], args[1], reset=bool(attrs.get("reset", False)))
+    if op == "penalize":
+        return T.penalize(args[0], args[1], args[2])
+    if op == "stop_ids":
+        return T.stop_ids(args[0], args[1], args[2])
+    if op == "done_mark":
+        return T.done_mark(args[0], args[1], args[2])
     if op == "pos_set":
         return args[0].fill_(int(attrs["value"]))
     if op == "argmax":

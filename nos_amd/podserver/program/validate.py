@@ -7,7 +7,7 @@ import math
 
 from .graph import Program
 from .ir import (FLOAT_DTYPES, FORMAT, MAX_NUMEL, MAX_PARAMS, MAX_NODES, MAX_RANK, MAX_STATE, MAX_VARIANTS, OPS,
-                 PARAM_DTYPES, STATE_DTYPES, STATE_WRITERS, ACTS, BINARY,
+                 PARAM_DTYPES, STATE_DTYPES, STATE_WRITERS, STOP_CTL_WORDS, ACTS, BINARY,
                  INTERP_MODES, UNARY, WIRE_DTYPES, Node, ProgramError, Value, _broadcast, _eps, _int, _name,
                  _pair, _req, _shape)
 
@@ -343,8 +343,10 @@ def _infer(node: Node, ins: list[Value], gpu: bool) -> tuple[tuple[int, ...], st
         return x.shape, x.dtype
     if op in ("pos_add", "pos_set"):
         only("n" if op == "pos_add" else "value")
-        arity(1, 1)
+        arity(1, 2 if op == "pos_add" else 1)
         _req(ins[0].dtype == "i32" and len(ins[0].shape) == 1, f"{what}: takes an i32 [B] position state")
+        if len(ins) == 2:   # a stopping tenant's: rows whose done flag is set keep their counter
+            _done_vector(ins[1], ins[0].shape[0], what)
         v = a.get("n" if op == "pos_add" else "value")
         _req(isinstance(v, int) and not isinstance(v, bool) and 0 <= v <= 1 << 24,
              f"{what}: {'n' if op == 'pos_add' else 'value'} must be an int in [0, 2^24]")
@@ -368,11 +370,66 @@ def _infer(node: Node, ins: list[Value], gpu: bool) -> tuple[tuple[int, ...], st
              f"{list(ctl.shape)}")
         _pos_vector(p, math.prod(x.shape[:-1]), what)
         return x.shape[:-1], "i32"
+    if op == "seen_mark":
+        # seen [B, W] (i32 bitmaps: bit id & 31 of word id >> 5) |= the ids [B, S]; reset: cleared first
+        only("reset")
+        arity(2, 2)
+        seen, ids = ins
+        _req(seen.dtype == "i32" and len(seen.shape) == 2, f"{what}: seen must be an i32 [B, words] bitmap state, "
+             f"got {seen.dtype} {list(seen.shape)}")
+        _req(ids.dtype == "i32" and len(ids.shape) == 2 and ids.shape[0] == seen.shape[0],
+             f"{what}: ids must be i32 [{seen.shape[0]}, S], got {ids.dtype} {list(ids.shape)}")
+        _req(isinstance(a.get("reset", False), bool), f"{what}: reset must be a bool")
+        return seen.shape, "i32"
+    if op == "penalize":
+        # the logits of the tokens in seen under the control words' repetition penalty (ops.tenant.penalize)
+        only()
+        arity(3, 3)
+        x, seen, ctl = ins
+        _req(len(x.shape) >= 1 and x.dtype in FLOAT_DTYPES, f"{what}: takes a float tensor (last dim: the logits)")
+        rows, words = math.prod(x.shape[:-1]), -(-x.shape[-1] // 32)
+        _req(seen.dtype == "i32" and seen.shape == (rows, words),
+             f"{what}: seen must be an i32 [{rows}, {words}] bitmap (one bit per logit, 32 a word), got "
+             f"{seen.dtype} {list(seen.shape)}")
+        _stop_ctl(ctl, what)
+        if gpu:
+            _req(rows <= 65535, f"{what}: at most 65535 rows of logits")
+        return x.shape, x.dtype
+    if op == "stop_ids":
+        # done[b] ? pad_id : next_ids[b]
+        only()
+        arity(3, 3)
+        nxt, done, ctl = ins
+        _req(nxt.dtype == "i32", f"{what}: next ids must be i32, got {nxt.dtype}")
+        _done_vector(done, nxt.numel, what)
+        _stop_ctl(ctl, what)
+        return nxt.shape, "i32"
+    if op == "done_mark":
+        # done[b] |= ids[b] is one of the control words' stop ids
+        only()
+        arity(3, 3)
+        done, ids, ctl = ins
+        _req(ids.dtype == "i32", f"{what}: ids must be i32, got {ids.dtype}")
+        _done_vector(done, ids.numel, what)
+        _stop_ctl(ctl, what)
+        return done.shape, "i32"
     raise ProgramError(f"{what}: op {op!r} is not one the pod server runs (whitelist: {' '.join(OPS)})")
 
 
 def _pos_vector(p: Value, b: int, what: str) -> None:
     _req(p.dtype == "i32" and p.shape == (b,), f"{what}: pos must be an i32 [{b}] (a position state), got {p.shape}")
+
+
+def _done_vector(d: Value, b: int, what: str) -> None:
+    _req(d.dtype == "i32" and d.shape == (b,), f"{what}: done must be an i32 [{b}] (a flag per row), got "
+         f"{d.dtype} {list(d.shape)}")
+
+
+def _stop_ctl(ctl: Value, what: str) -> None:
+    """The stopping control words: an i32 [8] STATE (the server fills it per request)."""
+    _req(ctl.kind == "state" and ctl.dtype == "i32" and ctl.shape == (STOP_CTL_WORDS,),
+         f"{what}: the stopping control words must be an i32 [{STOP_CTL_WORDS}] state, got {ctl.kind} {ctl.name!r} "
+         f"{ctl.dtype} {list(ctl.shape)}")
 
 
 def _scales_state(s: Value, cache: Value, what: str) -> None:
@@ -384,6 +441,12 @@ def _scales_state(s: Value, cache: Value, what: str) -> None:
 
 # the slots an i8 state (a quantized cache) and its scales state may fill
 _Q8_CACHE_SLOTS = {"kv_write": {0: 3}, "sdpa_cache": {1: 4, 2: 5}}   # op -> {cache slot: its scales' slot}
+
+
+# the states a stopping program's ops name: op -> ((role, input slot), ...); a program has one of each
+_STOP_ROLES = {"seen_mark": (("seen", 0),), "penalize": (("seen", 1), ("stopping", 2)),
+               "stop_ids": (("done", 1), ("stopping", 2)), "done_mark": (("done", 0), ("stopping", 2)),
+               "pos_add": (("done", 1),)}   # the mask of pos_add(pos, done): the flags stop_ids / done_mark name
 
 
 def parse_variants(objs: list, payload: bytes | memoryview = b"", gpu: bool = False) -> list[Program]:
@@ -408,6 +471,9 @@ def parse_variants(objs: list, payload: bytes | memoryview = b"", gpu: bool = Fa
         _req(p.inputs[0].shape not in seen, f"two variants take the input shape {list(p.inputs[0].shape)}")
         seen.add(p.inputs[0].shape)
     _req(len({p.sampling_state for p in progs} - {None}) <= 1, "variants must share one sampling control state")
+    for what in ("stopping_state", "done_state", "seen_state"):
+        _req(len({getattr(p, what) for p in progs} - {None}) <= 1,
+             f"variants must share one {what.replace('_', ' ')} (the stopping control words, the done flags, the bitmap)")
     return progs
 
 
@@ -472,6 +538,7 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     root_of = {k: k for k in state}
     dead: set[str] = set()
     sampling = None   # the control state of the program's sample nodes
+    stop = {"stopping": None, "done": None, "seen": None}   # a stopping program's control words, flags and bitmap
     scales_of: dict[str, str] = {}      # a scales state -> the i8 cache (root) whose row scales it holds
     cache_scales: dict[str, str] = {}   # and back
     other_use: dict[str, str] = {}      # a state -> the first node naming it as anything but a cache's scales
@@ -533,6 +600,15 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
             _req(sampling in (None, refs[1]), f"node {n.output!r} (sample): a program has one control state; "
                  f"{sampling!r} and {refs[1]!r} are two")
             sampling = refs[1]
+        for role, k in _STOP_ROLES.get(op, ()):
+            if k >= len(refs):   # pos_add's optional mask
+                continue
+            r = refs[k]
+            root = root_of.get(r, r)
+            _req(root in state, f"node {n.output!r} ({op}): {role} must be a state (or a version of one); {r!r} is not")
+            _req(stop[role] in (None, root), f"node {n.output!r} ({op}): a program has one {role} state; "
+                 f"{stop[role]!r} and {root!r} are two")
+            stop[role] = root
         define(Value(n.output, shape, dt, "node"))
         nodes.append(n)
     outs = obj.get("outputs")
@@ -548,5 +624,6 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     _req(not any(o in root_of for o in outs), "a state (or a version of one) cannot be an output: it is mutable")
     _req(not any(values[o].dtype == "i8" for o in outs), "an i8 param cannot be an output")
     return Program(name, inputs, params, layout, nodes, list(outs), values, payload, state=state,
-                   state_root={k: v for k, v in root_of.items() if k != v}, sampling_state=sampling)
+                   state_root={k: v for k, v in root_of.items() if k != v}, sampling_state=sampling,
+                   stopping_state=stop["stopping"], done_state=stop["done"], seen_state=stop["seen"])
 

@@ -116,6 +116,9 @@ class Tenant:
     pos_limits: dict = field(default_factory=dict)  # position state -> rows of the caches written at it
     host: dict = field(default_factory=dict)        # pinned staging buffers (input, outputs, counters)
     sampling_state: str | None = None               # the control state of its programs' ``sample`` nodes
+    stopping_state: str | None = None               # the control state of its programs' stopping ops (stop ids, penalty)
+    done_state: str | None = None                   # ... the rows' done flags (replied; the server loop's early exit)
+    seen_state: str | None = None                   # ... the rows' token bitmaps (never replied)
 
 
 @dataclass
@@ -150,6 +153,8 @@ class _Job:
     error: str | None = None
     state: dict | None = None      # the tenant's counters after the run (stateful tenants)
     ctl: np.ndarray | None = None  # the sampling control words written before the run (sampling tenants)
+    stop: np.ndarray | None = None  # the stopping control words written before the run (stopping tenants)
+    steps_run: int = 0             # "generate": the runs made (fewer than ``steps`` once every row was done)
 
 
 class AdmissionError(RuntimeError):
@@ -179,6 +184,46 @@ def _sampling_words(req: dict, tenant: Tenant) -> np.ndarray | None:
     return sampling_ctl(**s)
 
 
+def _stopping_words(req: dict, tenant: Tenant) -> np.ndarray | None:
+    """The control words a request's optional ``"stopping"`` object asks for:
+    ``{"stop_ids": [...], "pad_id": int, "repetition_penalty": float}``, any
+    subset (``ops.tenant.stopping_ctl`` checks the values; ids must lie in
+    the tenant's id range).  A stopping tenant's request without one gets
+    zeros: no stop ids, no penalty, whatever the request before it set.  None
+    for a tenant whose programs have no stopping ops."""
+    s = req.get("stopping")
+    if s is None:
+        return np.zeros(8, dtype=np.int32) if tenant.stopping_state else None
+    if not tenant.stopping_state:
+        raise ValueError("stopping: the tenant's programs have no stopping state (they run every step)")
+    keys = ("stop_ids", "pad_id", "repetition_penalty")
+    if not isinstance(s, dict) or set(s) - set(keys):
+        raise ValueError(f"stopping must be an object with keys among {list(keys)}")
+    from ..ops.tenant import stopping_ctl
+
+    return stopping_ctl(**s, id_bound=tenant.id_bound)
+
+
+def _stop_ids_of(words: np.ndarray | None) -> list[int]:
+    """The stop ids the control words arm ([] without any)."""
+    return [] if words is None else [int(v) for v in words[3:3 + int(words[2])]]
+
+
+def _steps_until_done(toks: np.ndarray, stops: list[int], done_before=None) -> int:
+    """toks [steps, B, ...] (one id per row and step): the steps up to and
+    including the first one after which every row was done -- it has emitted
+    a stop id, or its flag in ``done_before`` ([B], the ``done`` state before
+    the first step) was set already: such a row (one the prefill finished)
+    emits only pad ids here, which need be no stop ids.  All the steps when
+    some row is never done; at least one step."""
+    hit = np.isin(toks.reshape(toks.shape[0], toks.shape[1], -1)[:, :, -1].astype(np.int64), stops)
+    if done_before is not None and hit.size:
+        hit[0] |= np.asarray(done_before).reshape(-1) != 0
+    if not hit.size or not hit.any(axis=0).all():
+        return toks.shape[0]
+    return int(hit.argmax(axis=0).max()) + 1
+
+
 def _pos_limits(progs) -> dict:
     """Position state -> the fewest cache rows any ``kv_write`` at it writes
     (past that the writes are dropped: the server reports the overflow)."""
@@ -195,6 +240,12 @@ def _pos_limits(progs) -> dict:
 def _sampling_state(progs) -> str | None:
     """The control state the programs' ``sample`` nodes read (variants share one)."""
     return next((p.sampling_state for p in progs if p.sampling_state), None)
+
+
+def _stop_states(progs) -> dict:
+    """The states of the programs' stopping ops (variants share them), as Tenant fields."""
+    return {k: next((getattr(p, k) for p in progs if getattr(p, k)), None)
+            for k in ("stopping_state", "done_state", "seen_state")}
 
 
 def _target_wire(trainer) -> str:
@@ -328,7 +379,7 @@ class PodServer:
                  allocations_dir: str | os.PathLike | None = None, pod_resources=None,
                  reap_interval_s: float = 1.0, max_inflight_register_gb: float = 16.0,
                  register_timeout_s: float = 30.0, register_min_mb_s: float = 50.0, priority_lanes: int = 0,
-                 latency_cus: int = 0, masked_queues: int = 8):
+                 latency_cus: int = 0, masked_queues: int = 8, stop_check_every: int = 4):
         """``allocations_dir``: this GPU's allocation records (tokens
         required; allocations.py).  Without it admission is open: the client
         declares its slice, which must be > 0 when the server accounts
@@ -347,9 +398,20 @@ class PodServer:
         lanes' to the rest, so a decode step's chain of small kernels never
         waits for CUs held by a throughput tenant's long workgroups.
         ``masked_queues``: with ``latency_cus``, the number of CU-masked
-        streams (each a hardware queue) the throughput lanes share."""
+        streams (each a hardware queue) the throughput lanes share.
+        ``stop_check_every``: a ``generate`` request with stop ids on the GPU
+        looks at the rows' ``done`` flags after every that many steps (a
+        queued copy and an event, waited for one window later, so the GPU
+        never idles) and leaves the loop once every row is done; requests
+        without stop ids run their loop without any of it.  The default, 4, is
+        the smallest of 4 / 8 / 16 / 32 whose armed loop ran within the
+        unarmed stopping tenant's run-to-run spread
+        (``tools/stop_decode_loop.py``, ``profiles/stop_decode_loop.json``)."""
         if lanes < 1:
             raise ValueError("lanes must be >= 1")
+        self.stop_check_every = int(stop_check_every)
+        if self.stop_check_every < 1:
+            raise ValueError("stop_check_every must be >= 1")
         self.path = Path(socket_path)
         self.device = device
         self.gpu = device == "cuda"
@@ -607,7 +669,8 @@ class PodServer:
                                 raise ValueError("outputs must be true / false or a list of output indices")
                         else:
                             want = bool(want)
-                        job = _Job(tenant, payload, want, shp, ctl=_sampling_words(req, tenant))
+                        job = _Job(tenant, payload, want, shp, ctl=_sampling_words(req, tenant),
+                                   stop=_stopping_words(req, tenant))
                         self._jobs.put(job, hi=tenant.latency)
                         job.done.wait()
                         if job.error:
@@ -631,7 +694,7 @@ class PodServer:
                         shp = tuple(int(d) for d in shp) if isinstance(shp, list) and len(shp) <= 8 else None
                         _check_wire_dtype(req.get("dtype"), _wire_dtype(tenant.x), "input")
                         job = _Job(tenant, payload, [feed], shp, kind="generate", steps=n, feed=feed,
-                                   ctl=_sampling_words(req, tenant))
+                                   ctl=_sampling_words(req, tenant), stop=_stopping_words(req, tenant))
                         self._jobs.put(job, hi=tenant.latency)
                         job.done.wait()
                         if job.error:
@@ -639,7 +702,7 @@ class PodServer:
                         descs, out = P.pack_arrays(job.outputs)
                         P.send_msg(conn, {"ok": True, "queue_us": round(1e6 * (job.t_start - job.t_enq), 1),
                                           "gpu_us": round(1e6 * (job.t_end - job.t_start), 1), "outputs": descs,
-                                          "state": job.state}, out)
+                                          "state": job.state, "steps_run": job.steps_run}, out)
                     elif op == "reset":
                         if tenant is None:
                             raise AdmissionError("register first")
@@ -855,7 +918,8 @@ class PodServer:
             m, x = built[0]
             return Tenant(tid, pod, limit, dtype, m, x, program=prog.name, compile_stats=dict(m.stats), cu_mask=mask,
                           id_bound=prog.id_bound(), alts={tuple(xv.shape): _Variant(mv, xv) for mv, xv in built[1:]},
-                          state=state, pos_limits=_pos_limits(progs), sampling_state=_sampling_state(progs))
+                          state=state, pos_limits=_pos_limits(progs), sampling_state=_sampling_state(progs),
+                          **_stop_states(progs))
         base = torch.cuda.memory_allocated()
         torch.cuda.reset_peak_memory_stats()
         stream = None
@@ -902,7 +966,7 @@ class PodServer:
                    solo_graph=v0.solo_graph, solo_outputs=v0.solo_outputs,
                    program=prog.name, compile_stats={**v0.model.stats, **times}, id_bound=prog.id_bound(),
                    alts={tuple(v.x.shape): v for v in variants[1:]}, state=state, pos_limits=_pos_limits(progs),
-                   sampling_state=_sampling_state(progs))
+                   sampling_state=_sampling_state(progs), **_stop_states(progs))
         if limit and peak > limit:
             self._free(t)
             raise AdmissionError(f"tenant needs {peak:.2f} GB, its slice has {limit} GB")
@@ -1147,19 +1211,32 @@ class PodServer:
                                  f"{tuple(v.x.shape)} {v.x.dtype}")
             return o
 
+        # generate with stop ids: the loop ends once every row's done flag is set (the steps past
+        # that point would only emit pad ids; a finished row's counter and cache rows never change)
+        stops = _stop_ids_of(job.stop) if gen else []
+        done = t.state.get(t.done_state) if stops else None
+        done0 = None   # the flags before the loop's first step: a row the prefill finished emits only pad ids in it
         with torch.no_grad():
             if not self.gpu:
+                if done is not None:
+                    before = done.clone()
+                    done0 = lambda: before.numpy()  # noqa: E731
                 if job.ctl is not None:
                     t.state[t.sampling_state].copy_(torch.from_numpy(job.ctl))
+                if job.stop is not None:
+                    t.state[t.stopping_state].copy_(torch.from_numpy(job.stop))
                 if x_in is not None:
                     v.x.copy_(torch.from_numpy(x_in.copy()).view(v.x.shape))
                 v.outputs = outs = v.model(v.x)
                 if gen:
                     toks = [fed(outs).clone()]
                     for _ in range(job.steps - 1):
+                        if done is not None and bool((done != 0).all()):   # checked after every step
+                            break
                         v.x.copy_(toks[-1].reshape(v.x.shape))
                         v.outputs = outs = v.model(v.x)
                         toks.append(fed(outs).clone())
+                    job.steps_run = len(toks)
                     outs = [torch.stack(toks)]
                     job.want_outputs = [0]
                 fetch = [lambda o=o: _host_array(o) for o in self._selected(outs, job.want_outputs)]
@@ -1172,6 +1249,11 @@ class PodServer:
                         hb = _pinned(t.host, "sampling", ctl.shape, ctl.dtype)
                         hb.numpy()[:] = job.ctl
                         ctl.copy_(hb, non_blocking=True)
+                    if job.stop is not None:   # and its stopping words, alike
+                        ctl = t.state[t.stopping_state]
+                        hb = _pinned(t.host, "stopping", ctl.shape, ctl.dtype)
+                        hb.numpy()[:] = job.stop
+                        ctl.copy_(hb, non_blocking=True)
                     if x_in is not None:
                         if str(v.x.dtype)[6:] == str(x_in.dtype):
                             # through a pinned buffer: an in-stream copy, no blocking pageable one
@@ -1180,8 +1262,13 @@ class PodServer:
                             v.x.copy_(hb, non_blocking=True)
                         else:
                             v.x.copy_(torch.from_numpy(x_in.copy()).view(v.x.shape).to(v.x.dtype), non_blocking=False)
+                    if done is not None:   # queued ahead of the first replay, read behind the lane's synchronisation
+                        hb0 = _pinned(t.host, ("done", "before"), done.shape, done.dtype)
+                        hb0.copy_(done, non_blocking=True)
+                        done0 = lambda: hb0.numpy()  # noqa: E731
                     solo = alone and v.solo_graph is not None
-                    toks = None
+                    toks = window = None
+                    every = self.stop_check_every
                     for i in range(job.steps if gen else 1):
                         if i:   # generate: the previous run's ids are this run's input, on the device
                             v.x.copy_(o.reshape(v.x.shape))
@@ -1199,8 +1286,23 @@ class PodServer:
                             if toks is None:
                                 toks = torch.empty((job.steps,) + tuple(o.shape), dtype=o.dtype, device=o.device)
                             toks[i].copy_(o)
+                            job.steps_run = i + 1
+                        if done is not None and (i + 1) % every == 0 and i + 1 < job.steps:
+                            # window j's flags: a queued copy and an event, looked at only after window
+                            # j + 1 is queued -- the lane never waits with nothing behind it on the GPU
+                            k = (i // every) & 1
+                            hb = _pinned(t.host, ("done", k), done.shape, done.dtype)
+                            hb.copy_(done, non_blocking=True)
+                            ev = t.host.get(("done_event", k)) or t.host.setdefault(("done_event", k),
+                                                                                    torch.cuda.Event())
+                            ev.record(s)
+                            prev, window = window, (ev, hb)
+                            if prev is not None:
+                                prev[0].synchronize()
+                                if bool((prev[1] != 0).all()):
+                                    break
                     if gen:
-                        fetch = [_fetch_start(toks, v.host, "gen")]
+                        fetch = [_fetch_start(toks[:job.steps_run], v.host, "gen")]
                     else:
                         fetch = [_fetch_start(outs[i], v.host, ("out", solo, i))
                                  for i in self._selected(range(len(outs)), job.want_outputs)]
@@ -1208,6 +1310,9 @@ class PodServer:
                 s.synchronize()
             if job.want_outputs:
                 job.outputs = [f() for f in fetch]
+            if stops:   # trimmed to the step after which every row was done (the window's overrun: pad ids)
+                before = done0() if done0 is not None else None
+                job.outputs = [o[:_steps_until_done(o, stops, before)] for o in job.outputs]
             if t.state:
                 job.state = counters()
                 for name, rows in t.pos_limits.items():
@@ -1233,7 +1338,12 @@ class PodServer:
         import torch
 
         return {k: [int(v) for v in st.cpu().tolist()] for k, st in t.state.items()
-                if st.dtype == torch.int32 and st.numel() <= 64 and k != t.sampling_state}
+                if st.dtype == torch.int32 and st.numel() <= 64 and k not in self._not_counters(t)}
+
+    @staticmethod
+    def _not_counters(t: Tenant) -> tuple:
+        """Small i32 states that are no counters: the control words and (at a tiny vocab) the bitmaps."""
+        return (t.sampling_state, t.stopping_state, t.seen_state)
 
     def _counters_start(self, t: Tenant):
         """``_counters`` behind the lane's one synchronisation: the copies are
@@ -1243,7 +1353,7 @@ class PodServer:
 
         bufs = {}
         for k, st in t.state.items():
-            if st.dtype == torch.int32 and st.numel() <= 64 and k != t.sampling_state:
+            if st.dtype == torch.int32 and st.numel() <= 64 and k not in self._not_counters(t):
                 hb = bufs[k] = _pinned(t.host, ("state", k), st.shape, st.dtype)
                 hb.copy_(st, non_blocking=True)
         return lambda: {k: [int(v) for v in hb.tolist()] for k, hb in bufs.items()}
