@@ -450,7 +450,10 @@ int launch_tile(const void* A, int lda, const void* W, int ldw, const void* bias
   const int tiles_n = (N + CF::BN - 1) / CF::BN;
   int nwg = tiles_m * tiles_n;
   if (max_wg <= 0 && g_persist > 0) max_wg = g_persist * num_cus();
-  if (max_wg > 0 && nwg > max_wg) nwg = max_wg;
+  // the kernel deals workgroup b to XCD chunk b % 8: a grid of fewer than 8
+  // workgroups would leave chunks (and their tiles of C) without one, so a cap
+  // below 8 is raised to min(8, tiles), the smallest grid nos_grid_for returns
+  if (max_wg > 0 && nwg > max_wg) nwg = max_wg >= 8 ? max_wg : (nwg < 8 ? nwg : 8);
   auto Ap = (const unsigned short*)A;
   auto Wp = (const unsigned short*)W;
   auto Bp = (const unsigned short*)bias;
@@ -491,7 +494,8 @@ int launch(const void* A, int lda, const void* W, int ldw, const void* bias, con
 
 // C = act(A . W^T + bias) (+ R).  A [M,K] (row stride lda), W [N,K] (ldw),
 // R/C [M,N] (ldr/ldc), all bf16.  K must be a multiple of 64 and every row
-// start 16-byte aligned.  max_wg > 0 caps the grid (persistent mode).
+// start 16-byte aligned.  max_wg > 0 caps the grid (persistent mode); a cap
+// below 8 runs min(8, tiles) workgroups, one per XCD chunk of the tile range.
 NOS_API int nos_gemm_set_policy(int policy) {
   if (policy < 0 || policy > 4) return (int)hipErrorInvalidValue;
   g_tile_policy = policy;

@@ -94,12 +94,22 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
     if x2.stride(-1) != 1 or weight.stride(-1) != 1 or K % 64 or x.dtype != torch.bfloat16:
         raise ValueError("native linear needs bf16, unit inner stride and K % 64 == 0")
     o2, r2 = _gemm_io(x, weight, out, residual, M, N, K)
+    _check_align16("linear", x=x2, weight=weight, residual=r2, out=o2)
     epi = _epi(bias, act, residual)
     rc = _lib.lib().nos_gemm_bf16(x2.data_ptr(), x2.stride(0), weight.data_ptr(), weight.stride(0),
                                   _ptr(bias), _ptr(r2), r2.stride(0) if r2 is not None else 0,
                                   o2.data_ptr(), o2.stride(0), M, N, K, epi, max_wg, _stream())
     _lib.check(rc, "nos_gemm_bf16")
     return o2.view(*x.shape[:-1], N)
+
+
+def _check_align16(what: str, **ts) -> None:
+    """The bf16 kernels move rows as 16-byte vectors (LDS-DMA, vector loads and
+    stores): next to the stride checks (ld % 8), every base pointer must sit on
+    a 16-byte boundary.  A column slice such as ``x[:, 4:4 + K]`` does not."""
+    for name, t in ts.items():
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"native {what}: {name} must start on a 16-byte boundary")
 
 
 def _epi(bias, act, residual) -> int:
@@ -677,6 +687,7 @@ def linear_ln(x: torch.Tensor, wg: torch.Tensor, c1: torch.Tensor, c2: torch.Ten
     if x2.stride(-1) != 1 or K % 64 or x.dtype != torch.bfloat16:
         raise ValueError("native linear_ln needs bf16, unit inner stride and K % 64 == 0")
     o2, _ = _gemm_io(x, wg, out, None, M, N, K)
+    _check_align16("linear_ln", x=x2, wg=wg, out=o2)
     epi = EPI_GELU if act == "gelu" else (EPI_RELU if act == "relu" else 0)
     rc = _lib.lib().nos_gemm_ln_bf16(x2.data_ptr(), x2.stride(0), wg.data_ptr(), wg.stride(0), c1.data_ptr(),
                                      c2.data_ptr(), o2.data_ptr(), o2.stride(0), M, N, K, epi, float(eps), max_wg,
@@ -698,6 +709,8 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
             raise ValueError(f"native layernorm takes bf16 tensors ({name} is {t.dtype})")
     if gamma.numel() != D or beta.numel() != D or not (gamma.is_contiguous() and beta.is_contiguous()):
         raise ValueError("gamma/beta must be contiguous [D]")
+    if D % 8 or D > 4096:
+        raise ValueError(f"native layernorm needs D % 8 == 0 and D <= 4096, got {D}")
 
     def rows2d(name, t):
         t2 = t.reshape(-1, D)  # a view when the rows are evenly strided, else a copy (never written back)
@@ -716,6 +729,7 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
     o2 = out.view(-1, D)
     r2 = rows2d("residual", residual) if residual is not None else None
     s2 = sum_out.view(-1, D) if sum_out is not None else None
+    _check_align16("layernorm", x=x2, gamma=gamma, beta=beta, residual=r2, out=o2, sum_out=s2)
     rc = _lib.lib().nos_layernorm_bf16(x2.data_ptr(), _ptr(r2), o2.data_ptr(), _ptr(s2), gamma.data_ptr(),
                                        beta.data_ptr(), rows, D, x2.stride(0), o2.stride(0),
                                        r2.stride(0) if r2 is not None else D, s2.stride(0) if s2 is not None else D,
@@ -750,6 +764,8 @@ def attention_qkv(qkv: torch.Tensor, num_heads: int, out: torch.Tensor | None = 
         out = torch.empty((B, S, num_heads * D), dtype=qkv.dtype, device=qkv.device)
     if out.dtype != qkv.dtype or out.stride(-1) != 1 or out.shape != (B, S, num_heads * D):
         raise ValueError("out must be [B, S, H*64] of qkv's dtype with unit inner stride")
+    if qkv.dtype == torch.bfloat16:
+        _check_align16("attention_qkv", qkv=qkv, out=out)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     hd = num_heads * D
     base = qkv.data_ptr()
@@ -966,6 +982,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | 
         raise ValueError("q/k/v must share row and batch strides")
     if out is None:
         out = torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device)
+    _check_align16("attention", q=q, k=k, v=v, out=out)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     rc = _lib.lib().nos_attn_fwd_d64(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H,
                                      Sq, Skv, q.stride(1), q.stride(0), out.stride(1), out.stride(0),

@@ -61,6 +61,13 @@ def test_square_and_forced_policies(pick):
     assert got == ["big", "big", "narrow", "big", "wide", "base"]
 
 
+def test_small_gemms_keep_the_base_tile_under_throughput(pick):
+    # the shapes of tests/test_bf16_kernels_gpu.py: too few 256-row tiles for half the CUs (2 * tiles < CUs), so
+    # its "throughput" runs are the 128x128 tile and its forced policies the other three
+    shapes = [(300, 264), (300, 260), (9, 4), (9, 8), (33, 7), (130, 136), (130, 133), (130, 132), (1100, 1030)]
+    assert pick([(m, n, THROUGHPUT, 256) for m, n in shapes]) == ["base"] * len(shapes)
+
+
 def test_fewer_cus_move_the_threshold(pick):
     # a 32-CU slice is filled by far fewer tiles: the 256-row tiles qualify at batch 1 on it
     assert pick([(B1, 1152, THROUGHPUT, 32)]) == ["wide"]
