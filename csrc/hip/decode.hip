@@ -29,6 +29,9 @@
 //  * nos_seen_mark / nos_penalize / nos_stop_step -- stop ids and the repetition penalty of a
 //    stopping tenant: the bitmap of a row's tokens, the penalised logits, and the closing step
 //    (pad finished rows, hold their counters, mark rows that drew a stop id);
+//  * nos_hist_write / nos_spec_step -- speculative decoding: the token history of each row and a
+//    verify step's close (accept the drafts the model confirmed, advance the counter by that
+//    many, look the next drafts up in the row's own history);
 //  * nos_gemv -- y = act(r x W^T + b) + R for M <= 8 rows (a decode step's
 //    every GEMM): weight-streaming, each wave two output columns, lanes over
 //    K with 16-byte weight loads, x rows in LDS (optionally RMS-normalised in
@@ -758,6 +761,119 @@ __global__ void stop_step_kernel(const int* __restrict__ next, int* __restrict__
     int hit = 0;
     for (int k = 0; k < ns; ++k) hit |= id == ctl[3 + k];
     if (hit) done[b] = d | 1;
+  }
+}
+
+// ------------------------------------------------------------------ speculative decoding (n-gram drafts)
+// hist [B, L]: from base = pos[b] - back on, the first `lead` columns of ids, then the columns of
+// tail [B, T] -- with n only its first n[b], and nothing at all for a row whose n[b] <= 0.  One
+// workgroup per row; every index is checked against [0, L).
+__global__ __launch_bounds__(256) void hist_write_kernel(int* __restrict__ hist, int L, const int* __restrict__ pos,
+                                                         int back, const int* __restrict__ ids, int lead,
+                                                         long long ld_ids, const int* __restrict__ tail, int T,
+                                                         long long ld_tail, const int* __restrict__ n) {
+  const int b = blockIdx.x;
+  int cnt = T;
+  if (n) {
+    const int c = n[b];
+    if (c <= 0) return;
+    cnt = min(c, T);
+  }
+  const long long base = (long long)pos[b] - back;
+  for (int s = threadIdx.x; s < lead + cnt; s += 256) {
+    const long long idx = base + s;
+    if (idx < 0 || idx >= L) continue;
+    hist[(long long)b * L + idx] = s < lead ? ids[b * ld_ids + s] : tail[b * ld_tail + (s - lead)];
+  }
+}
+
+constexpr int kSpecMaxK = 8;
+
+// A verify step's close, one workgroup per row (mode: which parts run; the whole step = 15).
+//  1: m = the step's advance -> n_acc[b].  ids [B, K]: the pending token at p = pos[b] and K - 1
+//     drafts; g [B, K]: the model's draw after each.  a = the leading j in 1 .. K - 1 with
+//     ids[j] == g[j - 1]; m = min(a + 1, L - 1 - p, end - p if end > 0) floored at 0, end = ctl[0];
+//     a p outside [0, L) gives 0.  (Without 1, m is read from n_acc[b].)
+//  2: a row with m > 0 writes hist[p] = ids[0], hist[p + 1 .. p + m] = g[0 .. m - 1]
+//  4: pos[b] = p + m
+//  8: out [B, K] = the next step's input at p' = pos[b] (after 4): the pending token hist[p'],
+//     then K - 1 drafts by n-gram lookup -- for n = 3, 2, 1 (each only if p' >= n) the largest
+//     t < p' with hist[t - n + 1 .. t] == hist[p' - n + 1 .. p']; the first n with a match wins and
+//     draft j is hist[t + j] if t + j <= p', else the pending token (as is every draft without a
+//     match).  The threads share the candidates t; each keys its best as (matched length, t) and a
+//     block-wide max picks the winner.  A p' outside [0, L): zeros.
+// Bounds: m <= L - 1 - p keeps every hist write below L, the lookup reads 0 .. p' < L only, and a
+// row with a counter outside [0, L) is left alone (m = 0: no write, the counter unchanged).  The
+// words this launch writes are read back from LDS, never from memory.
+// The K / V rows p + m .. p + K - 1 the step's body wrote for rejected drafts stay in the caches (int8
+// caches: with their scales): attention reads the keys up to its own position only, the next step's
+// first query sits at p + m, and each of those rows is rewritten, with its scale, by the step that
+// processes its position before any query can reach it.
+__global__ __launch_bounds__(256) void spec_step_kernel(int* hist, int L, int* __restrict__ pos,
+                                                        const int* __restrict__ ids, const int* __restrict__ g,
+                                                        const int* __restrict__ ctl, int* __restrict__ n_acc,
+                                                        int* __restrict__ out, int K, int mode) {
+  __shared__ int s_new[kSpecMaxK + 1];
+  __shared__ int s_at[3];   // p (where s_new starts), the words s_new holds, p'
+  __shared__ int s_best[256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) {
+    const int p = pos[b];
+    const bool ok = p >= 0 && p < L;
+    int m = 0, wrote = 0;
+    if (mode & 1) {
+      if (ok) {
+        int a = 0;
+        while (a + 1 < K && ids[b * K + a + 1] == g[b * K + a]) ++a;
+        m = min(a + 1, L - 1 - p);
+        const int end = ctl[0];
+        if (end > 0) m = min(m, end - p);
+        m = max(m, 0);
+      }
+      n_acc[b] = m;
+    } else if (mode & 4) {
+      m = n_acc[b];
+    }
+    if ((mode & 2) && m > 0) {   // mode 2 comes with 1: 0 <= p, p + m <= L - 1, m <= K
+      s_new[0] = ids[b * K];
+      for (int j = 0; j < m; ++j) s_new[1 + j] = g[b * K + j];
+      wrote = m + 1;
+      for (int j = 0; j < wrote; ++j) hist[(long long)b * L + p + j] = s_new[j];
+    }
+    if ((mode & 4) && m != 0) pos[b] = p + m;
+    s_at[0] = p;
+    s_at[1] = wrote;
+    s_at[2] = (mode & 4) ? p + m : p;
+  }
+  __syncthreads();
+  if (!(mode & 8)) return;
+  const int p0 = s_at[0], wrote = s_at[1], pp = s_at[2];
+  if (pp < 0 || pp >= L) {
+    if (tid < K) out[b * K + tid] = 0;
+    return;
+  }
+  const int* row = hist + (long long)b * L;
+  auto H = [&](int i) { return i >= p0 && i < p0 + wrote ? s_new[i - p0] : row[i]; };   // 0 <= i <= pp
+  const int pend = H(pp);
+  const int nmax = min(3, pp);
+  const int s1 = nmax >= 2 ? H(pp - 1) : 0, s2 = nmax >= 3 ? H(pp - 2) : 0;
+  int best = -1;
+  for (int t = tid; t < pp; t += 256) {
+    if (H(t) != pend) continue;
+    int ml = 1;
+    if (nmax >= 2 && t >= 1 && H(t - 1) == s1) ml = (nmax >= 3 && t >= 2 && H(t - 2) == s2) ? 3 : 2;
+    best = max(best, (ml << 28) | t);   // t < L <= 2^28
+  }
+  s_best[tid] = best;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) s_best[tid] = max(s_best[tid], s_best[tid + w]);
+    __syncthreads();
+  }
+  if (tid < K) {
+    const int key = s_best[0];
+    const int t = key & ((1 << 28) - 1);
+    out[b * K + tid] = (tid == 0 || key < 0 || t + tid > pp) ? pend : H(t + tid);
   }
 }
 
@@ -1687,6 +1803,33 @@ NOS_API int nos_stop_step(const int* next, int* ids_out, int* pos, int* done, co
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(stop_step_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, next, ids_out, pos,
                      done, ctl, B, n, mode);
+  return (int)hipGetLastError();
+}
+
+// hist [B, L] i32 <- ids [B, >= lead] (row stride ld_ids) and tail [B, T] (row stride ld_tail; or
+// null, T = 0) from position pos[b] - back on; n (or null): a count per row (hist_write_kernel)
+NOS_API int nos_hist_write(int* hist, int B, int L, const int* pos, int back, const int* ids, int lead,
+                           long long ld_ids, const int* tail, int T, long long ld_tail, const int* n,
+                           hipStream_t stream) {
+  if (!hist || !pos || B <= 0 || L <= 0 || back < 0 || lead < 0 || T < 0 || lead + T <= 0 || (lead > 0 && !ids) ||
+      (T > 0 && !tail) || ld_ids < (B > 1 ? lead : 0) || ld_tail < (B > 1 ? T : 0))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(hist_write_kernel, dim3((unsigned)B), dim3(256), 0, stream, hist, L, pos, back, ids, lead, ld_ids,
+                     tail, T, ld_tail, n);
+  return (int)hipGetLastError();
+}
+
+// a verify step's close over B rows (spec_step_kernel); mode: 1 the advance m -> n_acc, 4 pos += m
+// (m: n_acc's without 1), 8 the next input -> out [B, K], 15 the whole step, which also writes the
+// accepted tokens into hist.  ids, g, out: contiguous [B, K], 2 <= K <= 8; hist [B, L], L <= 2^28.
+NOS_API int nos_spec_step(int* hist, int B, int L, int* pos, const int* ids, const int* g, const int* ctl, int* n_acc,
+                          int* out, int K, int mode, hipStream_t stream) {
+  if (!pos || B <= 0 || L <= 0 || L > (1 << 28) || K < 2 || K > kSpecMaxK ||
+      (mode != 1 && mode != 4 && mode != 8 && mode != 15) || ((mode & 1) && (!ids || !g || !ctl)) ||
+      ((mode & 5) && !n_acc) || ((mode & 8) && (!hist || !out)))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(spec_step_kernel, dim3((unsigned)B), dim3(256), 0, stream, hist, L, pos, ids, g, ctl, n_acc, out,
+                     K, mode);
   return (int)hipGetLastError();
 }
 

@@ -113,7 +113,7 @@ def llama_program(model, seq: int, batch: int = 1, dtype: str = "fp32",
 def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, dtype: str = "fp32",
                           extend: tuple[int, ...] = (), sampling: bool = False,
                           weights: str = "fp32", kv: str | None = None,
-                          stopping: bool = False) -> tuple[list[dict], bytes]:
+                          stopping: bool = False, speculate: int | None = None) -> tuple[list[dict], bytes]:
     """A STATEFUL generation tenant: ``[prefill, decode, *extends]`` programs
     over one weight payload and one state -- per layer a K and a V cache
     ``[batch, max_len, kv_heads, head_dim]`` plus the position counter
@@ -176,7 +176,53 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     itself is emitted and every later id of the row is the pad id, and a
     finished row's counter -- so its cache rows below it -- never changes
     again.  All-zero control words (a request without the field): exactly the
-    plain tenant's tokens."""
+    plain tenant's tokens.
+
+    ``speculate=K`` (2 <= K <= 8; fp32 tenants, greedy, without stopping):
+    greedy speculative decoding with n-gram drafts looked up in the
+    sequence's own history -- the plain tenant's tokens in fewer steps.  The
+    programs also declare ``hist`` (i32 [batch, max_len]: ``hist[b, t]`` is the
+    token at position t for every t <= ``pos[b]``; ``hist[b, pos[b]]`` is the
+    pending token, drawn but not yet through the model) and the control state
+    ``speculate`` (i32 [4]: ``[end, 0, 0, 0]``, filled by the server from each
+    request's ``"speculate"`` field; no step advances a counter past ``end`` >
+    0).  Every program keeps ``hist`` true (its input ids at ``pos + s``, the
+    drawn id at the new ``pos``), the prefill also outputs ``spec_ids``
+    [batch, K] (the pending token and K - 1 drafts), and a VERIFY program
+    ``[batch, K]`` joins the variants: the extend-K body with the LM head on
+    all K rows, ``g = argmax(logits)``, then ``spec_accept`` (the drafts the
+    model confirmed, plus one), ``hist_write``, ``pos_advance`` and
+    ``spec_draft``.  Its outputs are ``logits`` [batch, K, vocab], ``next_ids``
+    [batch, K] (the next verify step's input) and ``n_acc`` [batch] (the
+    positions the step advanced).  The K / V rows a step wrote past the accepted
+    ones are never attended: attention reads keys up to its own position, and
+    the rows are rewritten (int8 caches: with their scales) when those
+    positions are processed.  With ``weights="int8"`` the verify step's rows must
+    also fit the int8 GEMV's staging (``batch * K * widest in-features * 4 <=
+    GEMV_X_BYTES``), so that no linear dequantizes a transient weight; an fp32
+    tenant past that bound is built, and that linear runs on the fp32 GEMM
+    instead of the GEMV (slower: docs/tenant_programs.md)."""
+    from ..ops.tenant import GEMV_MAX_ROWS, GEMV_X_BYTES
+
+    if speculate is not None:
+        if not isinstance(speculate, int) or isinstance(speculate, bool) or not 2 <= speculate <= 8:
+            raise ValueError(f"speculate must be an int in [2, 8] (the tokens a verify step takes), got {speculate!r}")
+        if batch * speculate > GEMV_MAX_ROWS:
+            raise ValueError(f"speculate: batch * K = {batch * speculate} > {GEMV_MAX_ROWS} (GEMV_MAX_ROWS): every "
+                             f"linear of the verify step must stay one GEMV launch")
+        widest = max(model.config.hidden_size, model.config.intermediate_size)
+        if weights == "int8" and batch * speculate * widest * 4 > GEMV_X_BYTES:
+            raise ValueError(f"speculate: batch * K = {batch * speculate} rows of {widest} inputs are more than the int8 "
+                             f"GEMV stages ({GEMV_X_BYTES} bytes of x rows): that linear of the verify step would "
+                             f"dequantize a transient fp32 weight")
+        if dtype != "fp32":
+            raise ValueError("speculate: dtype must be 'fp32' (a K-row and a 1-row bf16 step may round a near-tie "
+                             "differently; the contract is token equality)")
+        if sampling or stopping:
+            raise ValueError("speculate: greedy only -- sampling=True and stopping=True do not combine with it")
+        if speculate in (prompt_len, *extend):
+            raise ValueError(f"speculate: K = {speculate} is also the prompt length or an extend length; "
+                             f"the server routes variants by input shape")
     if not 0 < prompt_len <= max_len:
         raise ValueError(f"prompt_len must be in [1, {max_len}]")
     if weights not in ("fp32", "int8"):
@@ -198,11 +244,14 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     head = "lm_head.weight" if "lm_head.weight" in sd else "model.embed_tokens.weight"
     cache_dt = "bf16" if dtype == "bf16" else "fp32"
     progs = []
-    chunks = [(prompt_len, True), (1, False)] + [(n, False) for n in extend]
+    chunks = [(prompt_len, True, False), (1, False, False)] + [(n, False, False) for n in extend]
+    if speculate:
+        chunks.append((speculate, False, True))
     payload = b""
-    for seq, reset in chunks:
+    for seq, reset, verify in chunks:
         b = Builder(f"llama-h{d}-l{cfg.num_hidden_layers}-{dtype}{'-q8' if q8 else ''}{'-kvq8' if kvq8 else ''}-"
-                    f"{'stop-' if stopping else ''}{'prefill' if reset else 'step'}{seq}")
+                    f"{'stop-' if stopping else ''}{'spec-' if speculate else ''}"
+                    f"{'prefill' if reset else 'verify' if verify else 'step'}{seq}")
         ids = b.input("input_ids", [batch, seq], "i32")
         P = lambda k: b.param(k, sd[k], dtype)  # noqa: E731
 
@@ -219,6 +268,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
         b.state("pos", [batch], "i32")
         ctl = b.state("sampling", [4], "i32") if sampling else None
         done, seen, sctl = b.stopping_states(batch, cfg.vocab_size) if stopping else (None, None, None)
+        hist, spec_ctl = b.speculate_states(batch, max_len) if speculate else (None, None)
         cshape = [batch, max_len, nkv, hd]
         if kvq8:   # ((K cache, its scales), (V cache, its scales)) per layer
             caches = [(b.cache_q8(f"kc{i}", f"ks{i}", cshape), b.cache_q8(f"vc{i}", f"vs{i}", cshape))
@@ -256,11 +306,22 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
                 g = b.op("linear", y, P(pf + "mlp.gate_proj.weight"))
                 u = b.op("linear", y, P(pf + "mlp.up_proj.weight"))
             h = b.op("add", lin(b.op("mul", b.op("silu", g), u), pf + "mlp.down_proj.weight"), h)
-        if seq > 1:   # only the last token's logits: the LM head runs on one row
+        if seq > 1 and not verify:   # only the last token's logits: the LM head runs on one row
             h = b.op("slice", h, dim=1, start=seq - 1, end=seq)
         h = b.op("rmsnorm", h, P("model.norm.weight"), eps=eps)
         # a tied head reads the embedding table: quantized, it is a copy of its own (the table stays fp32)
         logits = lin(h, "lm_head.weight", head, out="logits") if q8 else lin(h, head, out="logits")
+        if verify:
+            # the draw after every row, the drafts it confirms (+ 1), the history and the counter
+            # advanced by that many, and the next step's input: the new pending token and its drafts
+            g = b.op("argmax", logits)
+            acc = b.op("spec_accept", ids, g, p, spec_ctl, out="n_acc", limit=max_len)
+            hv = b.op("hist_write", hist, p, ids, g, acc, lead=1)
+            nxt = b.op("spec_draft", hv, b.op("pos_advance", p, acc), out="next_ids", k=speculate)
+            prog, w = b.build([logits, nxt, acc])
+            progs.append(prog)
+            payload = w
+            continue
         if stopping:
             # the input ids join the row's bitmap, the seen tokens' logits are penalised (the ``logits``
             # output stays raw), then the draw; a finished row emits the pad id and keeps its counter,
@@ -273,8 +334,13 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
             b.op("done_mark", dn, nxt, sctl)
         else:
             nxt = b.op("sample", logits, ctl, p, out="next_ids") if sampling else b.op("argmax", logits, out="next_ids")
-            b.op("pos_add", p, n=seq)
-        prog, w = b.build([logits, nxt])
+            p2 = b.op("pos_add", p, n=seq)
+        outs = [logits, nxt]
+        if speculate:   # the history: the input ids at pos .. pos + seq - 1, the drawn id at the new pos
+            hv = b.op("hist_write", hist, p2, ids, nxt, back=seq)
+            if reset:
+                outs.append(b.op("spec_draft", hv, p2, out="spec_ids", k=speculate))
+        prog, w = b.build(outs)
         progs.append(prog)
         payload = w
     return progs, payload

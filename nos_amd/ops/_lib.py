@@ -124,6 +124,11 @@ _SIGS = {
     "nos_seen_mark": [c_void_p, c_int, c_int, c_void_p, c_int, c_ll, c_int, c_int, c_void_p],
     "nos_penalize": [c_void_p, c_int, c_int, c_int, c_ll, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p],
     "nos_stop_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    # speculative decoding: the token history and the verify step's close (decode.hip)
+    "nos_hist_write": [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p,
+                       c_void_p],
+    "nos_spec_step": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                      c_void_p],
     "nos_gemv": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                  c_int, c_int, c_int, c_float, c_void_p],
     "nos_gemv_partials": [c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,

@@ -1240,7 +1240,191 @@ def done_mark(done: torch.Tensor, ids: torch.Tensor, ctl: torch.Tensor) -> torch
     return done
 
 
+# ------------------------------------------------------------------ speculative decoding (n-gram drafts)
+SPEC_CTL_WORDS, SPEC_MAX_K, SPEC_NGRAM = 4, 8, 3
+
+
+def speculate_ctl(end: int = 0) -> np.ndarray:
+    """The four i32 control words a speculating tenant's verify step reads from
+    device memory: ``[end, 0, 0, 0]``.  ``end`` > 0: no step advances a row's
+    counter past ``end``; 0: no bound but the cache."""
+    if not isinstance(end, (int, np.integer)) or isinstance(end, bool) or not 0 <= end < 1 << 31:
+        raise ValueError(f"speculate: end must be an int in [0, 2^31), got {end!r}")
+    return np.array([int(end), 0, 0, 0], dtype=np.int32)
+
+
+def _spec_hist(hist: torch.Tensor, what: str) -> torch.Tensor:
+    if hist.dtype != torch.int32 or hist.dim() != 2 or not hist.is_contiguous() or hist.shape[1] > 1 << 28:
+        raise ValueError(f"{what}: hist must be a contiguous i32 [B, L <= 2^28] tensor, got {hist.dtype} "
+                         f"{tuple(hist.shape)}")
+    return hist
+
+
+def _spec_ids(t: torch.Tensor, B: int, like: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != B or t.device != like.device:
+        raise ValueError(f"{what} must be i32 [{B}, n] on the operands' device, got {t.dtype} {tuple(t.shape)}")
+    return t if t.stride(1) == 1 or t.shape[1] == 1 else t.contiguous()
+
+
+def hist_write(hist: torch.Tensor, pos: torch.Tensor, ids: torch.Tensor, tail: torch.Tensor | None = None,
+               n: torch.Tensor | None = None, back: int = 0, lead: int | None = None) -> torch.Tensor:
+    """hist [B, L] (i32: the tokens of each row's sequence by position), in
+    place: from ``base = pos[b] - back`` on, the first ``lead`` (default: all)
+    columns of ``ids`` [B, S], then the columns of ``tail`` [B, T] -- with
+    ``n`` [B] only its first ``n[b]``, and nothing at all for a row whose
+    ``n[b]`` is 0.  Every index outside [0, L) is dropped.  Returns ``hist``."""
+    _spec_hist(hist, "hist_write")
+    B, L = hist.shape
+    _i32_pos(pos, B)
+    ids = _spec_ids(ids, B, hist, "hist_write: ids")
+    lead = ids.shape[1] if lead is None else int(lead)
+    if not 0 <= lead <= ids.shape[1] or back < 0:
+        raise ValueError(f"hist_write: lead {lead} of {ids.shape[1]} columns, back {back}")
+    T = 0
+    if tail is not None:
+        tail = _spec_ids(tail, B, hist, "hist_write: tail")
+        T = tail.shape[1]
+    if n is not None:
+        _i32_pos(n, B)
+    if not hist.is_cuda:
+        for b in range(B):
+            cnt = T
+            if n is not None:
+                if int(n[b]) <= 0:
+                    continue
+                cnt = min(int(n[b]), T)
+            vals = ids[b, :lead].tolist() + (tail[b, :cnt].tolist() if cnt else [])
+            base = int(pos[b]) - back
+            for s, v in enumerate(vals):
+                if 0 <= base + s < L:
+                    hist[b, base + s] = v
+        return hist
+    _lib.check(_lib.lib().nos_hist_write(hist.data_ptr(), B, L, pos.data_ptr(), int(back), ids.data_ptr(), lead,
+                                         ids.stride(0), _ptr(tail), T, tail.stride(0) if T else 0, _ptr(n),
+                                         _stream()), "nos_hist_write")
+    return hist
+
+
+def _spec_launch(mode, hist, pos, ids, g, ctl, n_acc, out, B, L, K):
+    _lib.check(_lib.lib().nos_spec_step(_ptr(hist), B, L, pos.data_ptr(), _ptr(ids), _ptr(g), _ptr(ctl), _ptr(n_acc),
+                                        _ptr(out), K, mode, _stream()), "nos_spec_step")
+
+
+def _spec_pair(ids: torch.Tensor, g: torch.Tensor, pos: torch.Tensor, ctl: torch.Tensor, what: str):
+    B = pos.numel()
+    _i32_pos(pos, B)
+    if ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[0] != B or not 2 <= ids.shape[1] <= SPEC_MAX_K:
+        raise ValueError(f"{what}: ids must be i32 [{B}, 2 <= K <= {SPEC_MAX_K}], got {ids.dtype} {tuple(ids.shape)}")
+    if g.dtype != torch.int32 or g.shape != ids.shape:
+        raise ValueError(f"{what}: the drawn ids must be i32 {tuple(ids.shape)}, got {g.dtype} {tuple(g.shape)}")
+    if (ctl.dtype != torch.int32 or ctl.numel() != SPEC_CTL_WORDS or not ctl.is_contiguous()
+            or not ctl.device == pos.device == ids.device == g.device):
+        raise ValueError(f"{what}: ctl must be {SPEC_CTL_WORDS} contiguous i32 control words on the operands' device")
+    return ids.contiguous(), g.contiguous()
+
+
+def spec_accept(ids: torch.Tensor, g: torch.Tensor, pos: torch.Tensor, ctl: torch.Tensor, limit: int) -> torch.Tensor:
+    """How far a verify step advances each row, ``m`` [B] (i32).  ``ids`` [B,
+    K]: the pending token at position ``p = pos[b]`` and K - 1 drafts for p +
+    1 ..; ``g`` [B, K]: the model's draw after each of them.  ``a`` = the
+    leading j in 1 .. K - 1 with ``ids[b, j] == g[b, j - 1]`` (a match after
+    a mismatch does not count); ``m = min(a + 1, limit - 1 - p, end - p if end
+    > 0)`` floored at 0, ``end = ctl[0]``; a ``p`` outside [0, limit) gives 0."""
+    ids, g = _spec_pair(ids, g, pos, ctl, "spec_accept")
+    B, K = ids.shape
+    if limit < 1:
+        raise ValueError(f"spec_accept: limit {limit}")
+    if not pos.is_cuda:
+        end = int(ctl[0])
+        out = torch.zeros(B, dtype=torch.int32)
+        for b in range(B):
+            p = int(pos[b])
+            if not 0 <= p < limit:
+                continue
+            a = 0
+            while a + 1 < K and int(ids[b, a + 1]) == int(g[b, a]):
+                a += 1
+            m = min(a + 1, limit - 1 - p)
+            if end > 0:
+                m = min(m, end - p)
+            out[b] = max(m, 0)
+        return out
+    out = torch.empty(B, dtype=torch.int32, device=pos.device)
+    _spec_launch(1, None, pos, ids, g, ctl, out, None, B, int(limit), K)
+    return out
+
+
+def pos_advance(pos: torch.Tensor, n: torch.Tensor) -> torch.Tensor:
+    """``pos[b] += n[b]`` in place (a verify step's data-dependent advance); returns ``pos``."""
+    B = pos.numel()
+    _i32_pos(pos, B)
+    _i32_pos(n, B)
+    if not pos.is_cuda:
+        return pos.add_(n)
+    _spec_launch(4, None, pos, None, None, None, n, None, B, 1, 2)
+    return pos
+
+
+def spec_draft(hist: torch.Tensor, pos: torch.Tensor, k: int) -> torch.Tensor:
+    """The next verify step's input [B, k] (i32) by n-gram lookup in the row's
+    own history.  ``p = pos[b]``; column 0 is the pending token ``hist[b,
+    p]``.  For n = 3, 2, 1 (each only if p >= n): the largest ``t < p`` with
+    ``hist[t - n + 1 .. t] == hist[p - n + 1 .. p]``; the first n with a match
+    wins and draft j (1 .. k - 1) is ``hist[t + j]`` if ``t + j <= p``, else
+    the pending token.  No match: every draft is the pending token.  A ``p``
+    outside [0, L): zeros."""
+    _spec_hist(hist, "spec_draft")
+    B, L = hist.shape
+    _i32_pos(pos, B)
+    if not 2 <= k <= SPEC_MAX_K or pos.device != hist.device:
+        raise ValueError(f"spec_draft: k must be in [2, {SPEC_MAX_K}] (got {k}), pos on hist's device")
+    if not hist.is_cuda:
+        out = torch.zeros((B, k), dtype=torch.int32)
+        for b in range(B):
+            p = int(pos[b])
+            if not 0 <= p < L:
+                continue
+            h = hist[b, :p + 1].tolist()
+            out[b] = h[p]
+            for n in range(min(SPEC_NGRAM, p), 0, -1):
+                t = next((t for t in range(p - 1, n - 2, -1) if h[t - n + 1:t + 1] == h[p - n + 1:p + 1]), None)
+                if t is not None:
+                    for j in range(1, k):
+                        if t + j <= p:
+                            out[b, j] = h[t + j]
+                    break
+        return out
+    out = torch.empty((B, k), dtype=torch.int32, device=hist.device)
+    _spec_launch(8, hist, pos, None, None, None, None, out, B, L, k)
+    return out
+
+
+def spec_step(hist: torch.Tensor, pos: torch.Tensor, ids: torch.Tensor, g: torch.Tensor,
+              ctl: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """A verify step's close in one launch, a workgroup per row:
+    ``m = spec_accept(ids, g, pos, ctl, L)``; a row with m > 0 writes
+    ``hist[b, p] = ids[b, 0]``, ``hist[b, p + 1 .. p + m] = g[b, 0 .. m - 1]``
+    and ``pos[b] = p + m`` (both in place; m = 0 leaves the row alone); then
+    ``spec_draft(hist, pos, K)``.  Returns (the next input [B, K], m [B])."""
+    _spec_hist(hist, "spec_step")
+    B, L = hist.shape
+    ids, g = _spec_pair(ids, g, pos, ctl, "spec_step")
+    if pos.numel() != B or hist.device != pos.device:
+        raise ValueError(f"spec_step: hist {tuple(hist.shape)} and pos {tuple(pos.shape)} must share rows and device")
+    K = ids.shape[1]
+    if not hist.is_cuda:
+        m = spec_accept(ids, g, pos, ctl, L)
+        hist_write(hist, pos, ids, g, m, lead=1)
+        pos_advance(pos, m)
+        return spec_draft(hist, pos, K), m
+    m = torch.empty(B, dtype=torch.int32, device=hist.device)
+    out = torch.empty((B, K), dtype=torch.int32, device=hist.device)
+    _spec_launch(15, hist, pos, ids, g, ctl, m, out, B, L, K)
+    return out, m
+
+
 GEMV_MAX_ROWS = 8
+GEMV_X_BYTES = 65536   # the x rows the GEMV kernels stage in LDS: rows * K * 4 bytes at the most (gemv_ok, gemv_q8_ok)
 EPI_SILU = 64 # csrc/hip/epilogue.h; decode.hip's GEMV: SiLU epilogue
 EPI_GLU = 256  # decode.hip's GEMV: W = [gate; up], y = silu(gate) * up
 

@@ -194,7 +194,8 @@ class PodClient:
     def generate(self, prompt: np.ndarray, max_new_tokens: int, next_output: int = -1,
                  server_loop: bool = True, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  seed: int = 0, eos_token_id: int | list | None = None, pad_token_id: int | None = None,
-                 repetition_penalty: float = 1.0) -> tuple[np.ndarray, dict]:
+                 repetition_penalty: float = 1.0, speculate: bool = False,
+                 prefill_len: int | None = None) -> tuple[np.ndarray, dict]:
         """Generation on a stateful decoder tenant
         (models/llama_program.llama_decode_programs): the prompt ids [B, P]
         go to the prefill variant, then the decode variant runs once per new
@@ -223,9 +224,42 @@ class PodClient:
         when the prefill draws every row's stop id); the prefill's round
         trip, every decode step's (server loop: the loop's time / steps),
         ``steps_run`` (the decode steps the server ran: with stop ids up to
-        two check windows more than n - 1) and the server's final counters."""
+        two check windows more than n - 1) and the server's final counters.
+
+        ``speculate``, for a tenant registered with a verify program
+        (``llama_decode_programs(..., speculate=K)``; greedy, no stop ids):
+        the prefill, then ONE ``generate`` request over the verify variant
+        (:meth:`speculate_loop`) -- the same ``max_new_tokens`` ids as the
+        plain tenant's in fewer steps; the timings also carry ``n_acc``
+        [steps_run, B], the positions each verify step advanced.
+        ``prefill_len`` (with ``speculate``; default: the whole prompt): only
+        the prompt's first that many ids go to the prefill variant, the rest
+        one decode step each -- for a prompt as long as the verify step is
+        wide, whose shape would name two variants."""
         prompt = np.asarray(prompt)
         B = prompt.shape[0]
+        if speculate:
+            if temperature != 0.0 or top_k or top_p != 1.0 or eos_token_id is not None or repetition_penalty != 1.0:
+                raise ValueError("generate: speculate is greedy only, without stop ids or a repetition penalty")
+            t0 = time.monotonic()
+            head = prompt.shape[1] if prefill_len is None else int(prefill_len)
+            if not 0 < head <= prompt.shape[1]:
+                raise ValueError(f"generate: prefill_len must lie in [1, {prompt.shape[1]}]")
+            outs, rep = self.infer(prompt[:, :head], outputs=[1, 2])   # next_ids, spec_ids (the pending token, drafts)
+            for s in range(head, prompt.shape[1]):   # the drafts after single steps: the pending token repeated
+                o, rep = self.infer(prompt[:, s:s + 1], outputs=[1])
+                outs = [o[0], np.repeat(o[0].reshape(B, 1), outs[1].reshape(B, -1).shape[1], axis=1)]
+            t1 = time.monotonic()
+            if max_new_tokens <= 1:
+                return outs[0].reshape(B, 1).astype(np.int32), {"prefill_s": t1 - t0, "step_s": [], "steps_run": 0,
+                                                                "state": rep.get("state"), "n_acc": np.zeros((0, B), np.int32)}
+            s0 = time.monotonic()
+            toks, acc, rep = self.speculate_loop(outs[1].reshape(B, -1).astype(np.int32), max_new_tokens - 1,
+                                                 prompt.shape[1] + max_new_tokens - 1)
+            dt = time.monotonic() - s0
+            run = int(rep["steps_run"])
+            return toks, {"prefill_s": t1 - t0, "step_s": [dt / run] * run, "state": rep.get("state"),
+                          "steps_run": run, "n_acc": acc}
         given = {"temperature": temperature, "top_k": top_k, "top_p": top_p, "seed": seed}
         sampling = {k: v for k, v in given.items() if v != _GREEDY[k]}   # older servers keep serving greedy clients
         stops = [] if eos_token_id is None else ([eos_token_id] if isinstance(eos_token_id, (int, np.integer))
@@ -274,6 +308,26 @@ class PodClient:
                     break
         return np.stack(toks, axis=1), {"prefill_s": t1 - t0, "step_s": steps, "state": rep.get("state"),
                                         "steps_run": run}
+
+    def speculate_loop(self, ids: np.ndarray, steps: int, end: int) -> tuple[np.ndarray, np.ndarray, dict]:
+        """A speculating tenant's verify loop as ONE ``generate`` request.
+        ``ids`` [B, K]: the pending token of each row (the last id drawn, at
+        position ``pos``) and K - 1 drafts (any valid ids; a prefill's
+        ``spec_ids``, or the pending token repeated after single decode
+        steps).  The server replays the verify variant, feeding its
+        ``next_ids``, until every row's counter is at ``end`` -- ``steps`` =
+        ``end - pos`` runs at the most.  Returns (the tokens at positions
+        ``end - steps .. end`` [B, steps + 1], the pending one first; each
+        step's advance ``n_acc`` [steps_run, B]; the reply, with
+        ``steps_run`` and the final counters)."""
+        ids = np.asarray(ids)
+        B = ids.shape[0]
+        wire = _wire(ids, self.input_dtype, "input")
+        req = {"op": "generate", "steps": int(steps), "output": 1, "shape": [int(d) for d in ids.shape],
+               "dtype": "i32" if wire.dtype == np.int32 else "f32", "speculate": {"end": int(end)}}
+        rep, data = self._call(req, wire.tobytes())
+        toks, acc = P.unpack_arrays(rep["outputs"], data)
+        return toks.reshape(B, -1).astype(np.int32), acc.reshape(-1, B).astype(np.int32), rep
 
     def train_step(self, x: np.ndarray, target: np.ndarray) -> dict:
         """One optimisation step of a training tenant on (x, target): the

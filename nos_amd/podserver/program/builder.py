@@ -105,6 +105,14 @@ class Builder:
         return (self.state(done, [batch], "i32"), self.state(seen, [batch, -(-vocab // 32)], "i32"),
                 self.state(ctl, [8], "i32"))
 
+    def speculate_states(self, batch: int, max_len: int, hist: str = "hist",
+                         ctl: str = "speculate") -> tuple[str, str]:
+        """The two states of a speculating program: the rows' token history ``hist`` i32 [batch,
+        max_len] (``hist[b, t]``: the token at position t, for every t up to and including the
+        pending one at ``pos[b]``) and the control words ``ctl`` i32 [4] the server fills from each
+        request's ``"speculate"`` field (``ops.tenant.speculate_ctl``)."""
+        return self.state(hist, [batch, max_len], "i32"), self.state(ctl, [4], "i32")
+
     def op(self, op: str, *inputs: str, out: str | None = None, **attrs) -> str:
         self._n += 1
         out = out or f"%{self._n}"

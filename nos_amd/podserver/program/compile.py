@@ -9,7 +9,7 @@ import os
 from dataclasses import dataclass, field
 
 from .graph import Program
-from .ir import BINARY, NATIVE_KINDS, NEVER_FOLD, STATE_WRITERS, STOP_KINDS, UNARY, ProgramError, torch_dtype
+from .ir import BINARY, NATIVE_KINDS, NEVER_FOLD, SPEC_KINDS, STATE_WRITERS, STOP_KINDS, UNARY, ProgramError, torch_dtype
 from .reference import _eager
 
 
@@ -80,6 +80,8 @@ class Lowered:
                 steps = self._fuse_argmax_pos(steps)
             if "stop_step" not in skip:
                 steps = self._fuse_stop_step(steps)
+            if "spec_step" not in skip:
+                steps = self._fuse_spec_step(steps)
             steps = self._fuse_gemv_glu(steps)
             if "combine_gemv" not in skip:
                 steps = self._fold_combine_into_gemv(steps)
@@ -100,6 +102,10 @@ class Lowered:
         if "stop_steps_fused" in self.stats:   # a stopping program: the launches its stopping ops cost
             self.stats["stop_launches"] = sum(1 for s in self.steps if s.kind in STOP_KINDS
                                               or (s.kind == "pos_add" and len(s.inputs) == 2))
+
+        if "spec_steps_fused" in self.stats:   # a verify program: the launches that close it (the accept,
+            # the history, the counter, the next drafts) -- what it has beyond an extend step of as many tokens
+            self.stats["spec_launches"] = sum(1 for s in self.steps if s.kind in SPEC_KINDS)
 
     def _memo(self, tag: str, sources: list, extra, make):
         """``make()`` once per recipe: ``tag`` + the identities of the source
@@ -1175,6 +1181,8 @@ class Lowered:
         if any(s.kind == "sample" for s in steps):
             self.stats["pos_add_into_sample"] = 0
         uses = self._consumers(steps, self.outputs)
+        # a speculating tenant's history steps read the advanced counter (the executor hands it on)
+        spec_reads = lambda v: sum(s.inputs.count(v) for s in steps if s.kind in ("hist_write", "spec_draft"))  # noqa: E731
         for k, p in enumerate(steps):
             if p.kind != "pos_add" or k == 0 or len(p.inputs) != 1:   # pos_add(pos, done): _fuse_stop_step's
                 continue
@@ -1182,7 +1190,7 @@ class Lowered:
             shp = tuple(self._shape(a.inputs[0])) if a.kind in ("argmax", "sample") else ()
             pshape = tuple(self._shape(p.inputs[0]))
             if (not shp or a.attrs.get("pos_out") or len(pshape) != 1
-                    or math.prod(shp[:-1]) != pshape[0] or uses.get(p.output, 0) != 0
+                    or math.prod(shp[:-1]) != pshape[0] or uses.get(p.output, 0) != spec_reads(p.output)
                     or self._dtype(p.inputs[0]) != "i32" or (a.kind == "sample" and a.inputs[2] != p.inputs[0])):
                 continue
             if a.kind == "argmax":
@@ -1213,6 +1221,30 @@ class Lowered:
             break
         if any(s.kind in STOP_KINDS for s in steps):
             self.stats["stop_steps_fused"] = n
+        return steps
+
+    def _fuse_spec_step(self, steps: list[_Step]) -> list[_Step]:
+        """A verify program's close -- ``spec_accept(ids, g, pos, ctl)``, ``hist_write(hist, pos, ids,
+        g, n_acc, lead=1)``, ``pos_advance(pos, n_acc)``, ``spec_draft(hist, pos)``, adjacent, over one
+        history, counter and advance -- becomes ONE ``spec_step``: a workgroup per row accepts, writes
+        the history and the counter and looks the next drafts up (``ops.tenant.spec_step``)."""
+        n = 0
+        for k in range(len(steps) - 3):
+            a, h, p, d = steps[k:k + 4]
+            if ([s.kind for s in (a, h, p, d)] != ["spec_accept", "hist_write", "pos_advance", "spec_draft"]
+                    or len(h.inputs) != 5 or h.inputs[1:] != [a.inputs[2], a.inputs[0], a.inputs[1], a.output]
+                    or h.attrs.get("lead") != 1 or h.attrs.get("back", 0) != 0
+                    or p.inputs != [a.inputs[2], a.output] or d.inputs != [h.output, p.output]
+                    or int(a.attrs["limit"]) != self._shape(h.inputs[0])[1]
+                    or int(d.attrs["k"]) != self._shape(a.inputs[0])[1]):
+                continue
+            fused = _Step("spec_step", [h.inputs[0], a.inputs[2], a.inputs[0], a.inputs[1], a.inputs[3]], d.output,
+                          {"n_acc_out": a.output, "hist_out": h.output, "pos_out": p.output})
+            steps = steps[:k] + [fused] + steps[k + 4:]
+            n = 1
+            break
+        if any(s.kind == "spec_accept" for s in steps) or n:
+            self.stats["spec_steps_fused"] = n
         return steps
 
     def _prep_conv_weights(self, steps: list[_Step]) -> None:

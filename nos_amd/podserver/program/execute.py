@@ -156,6 +156,9 @@ class CompiledProgram(Lowered):
             elif k == "stop_step":   # pos_add(pos, done) / stop_ids / done_mark: next ids, pos, done, ctl
                 y = T.stop_step(a[0], a[1], a[2], a[3], n=int(s.attrs["n"]), mode=7)
                 env[s.attrs["pos_out"]], env[s.attrs["done_out"]] = a[1], a[2]
+            elif k == "spec_step":   # spec_accept / hist_write / pos_advance / spec_draft: hist, pos, ids, drawn ids, ctl
+                y, env[s.attrs["n_acc_out"]] = T.spec_step(a[0], a[1], a[2], a[3], a[4])
+                env[s.attrs["hist_out"]], env[s.attrs["pos_out"]] = a[0], a[1]
             elif k == "pos_add" and len(a) == 2:   # finished rows (done) keep their counter
                 T.stop_step(None, a[0], a[1], None, n=int(s.attrs["n"]), mode=2)
                 y = a[0]

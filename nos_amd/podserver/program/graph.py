@@ -76,6 +76,8 @@ class Program:
     stopping_state: str | None = None    # the i32 [8] state its stopping ops read (stop ids, pad id, penalty; per request)
     done_state: str | None = None        # the i32 [B] flags ``done_mark`` sets (a row that drew a stop id)
     seen_state: str | None = None        # the i32 [B, ceil(vocab / 32)] bitmap ``seen_mark`` fills
+    speculate_state: str | None = None   # the i32 [4] state ``spec_accept`` reads (the token budget's end; per request)
+    hist_state: str | None = None        # the i32 [B, L] token history ``hist_write`` keeps (a speculating tenant)
 
     # ------------------------------------------------------------ accounting
     @property

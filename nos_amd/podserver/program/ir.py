@@ -131,6 +131,14 @@ MAX_STOP_IDS = 4
 STOP_OPS = ("seen_mark", "penalize", "stop_ids", "done_mark")
 STATE_OPS = STATE_OPS + STOP_OPS
 STATE_WRITERS = STATE_WRITERS + ("seen_mark", "done_mark")
+# speculative decoding (a speculating tenant): hist_write(hist, pos, ids[, tail[, n]]) keeps the
+# rows' token history, spec_accept(ids, g, pos, ctl) is a verify step's advance per row,
+# pos_advance(pos, n) adds it to the counters, spec_draft(hist, pos) looks the next drafts up
+SPEC_CTL_WORDS = 4           # [end, 0, 0, 0] (ops.tenant.speculate_ctl)
+SPEC_MIN_K, SPEC_MAX_K = 2, 8
+SPEC_OPS = ("hist_write", "spec_accept", "pos_advance", "spec_draft")
+STATE_OPS = STATE_OPS + SPEC_OPS
+STATE_WRITERS = STATE_WRITERS + ("hist_write", "pos_advance")
 STATE_DTYPES = ("fp32", "bf16", "i32", "i8")
 MAX_STATE = 1024
 OPS = OPS + STATE_OPS
@@ -139,7 +147,10 @@ NEVER_FOLD = ("attention", "sdpa", "linear_q8", *STATE_OPS)
 # step kinds that run a gfx950 kernel of libnos_hip.so (CompiledProgram.stats["kernels"])
 NATIVE_KINDS = ("linear", "linear_ln", "linear_rms", "ln_qkv_attention", "attention", "layernorm", "conv2d", "matmul",
                 "softmax", "embedding", "rmsnorm", "rotary", "sdpa", "patches", "unary", "kv_write", "sdpa_cache",
-                "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu", "linear_q8", *STOP_OPS, "stop_step")
+                "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu", "linear_q8", *STOP_OPS, "stop_step", *SPEC_OPS, "spec_step")
+# the steps a speculating tenant's verify program closes with (CompiledProgram.stats["spec_launches"]);
+# spec_step: spec_accept / hist_write / pos_advance / spec_draft fused into one launch
+SPEC_KINDS = (*SPEC_OPS, "spec_step")
 # the steps a stopping program adds to a plain one (CompiledProgram.stats["stop_launches"]); stop_step:
 # the pos_add(pos, done) / stop_ids / done_mark trio fused into one launch
 STOP_KINDS = (*STOP_OPS, "stop_step")

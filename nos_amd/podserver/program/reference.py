@@ -132,6 +132,15 @@ def _eager(op: str, args: list, attrs: dict, ref: bool = False):
         return T.stop_ids(args[0], args[1], args[2])
     if op == "done_mark":
         return T.done_mark(args[0], args[1], args[2])
+    if op == "hist_write":
+        return T.hist_write(args[0], args[1], args[2], args[3] if len(args) > 3 else None,
+                            args[4] if len(args) > 4 else None, back=int(attrs.get("back", 0)), lead=attrs.get("lead"))
+    if op == "spec_accept":
+        return T.spec_accept(args[0], args[1], args[2], args[3], int(attrs["limit"]))
+    if op == "pos_advance":
+        return T.pos_advance(args[0], args[1])
+    if op == "spec_draft":
+        return T.spec_draft(args[0], args[1], int(attrs["k"]))
     if op == "pos_set":
         return args[0].fill_(int(attrs["value"]))
     if op == "argmax":

@@ -7,8 +7,8 @@ import math
 
 from .graph import Program
 from .ir import (FLOAT_DTYPES, FORMAT, MAX_NUMEL, MAX_PARAMS, MAX_NODES, MAX_RANK, MAX_STATE, MAX_VARIANTS, OPS,
-                 PARAM_DTYPES, STATE_DTYPES, STATE_WRITERS, STOP_CTL_WORDS, ACTS, BINARY,
-                 INTERP_MODES, UNARY, WIRE_DTYPES, Node, ProgramError, Value, _broadcast, _eps, _int, _name,
+                 PARAM_DTYPES, SPEC_CTL_WORDS, SPEC_MAX_K, SPEC_MIN_K, STATE_DTYPES, STATE_WRITERS, STOP_CTL_WORDS, ACTS,
+                 BINARY, INTERP_MODES, UNARY, WIRE_DTYPES, Node, ProgramError, Value, _broadcast, _eps, _int, _name,
                  _pair, _req, _shape)
 
 
@@ -413,7 +413,62 @@ def _infer(node: Node, ins: list[Value], gpu: bool) -> tuple[tuple[int, ...], st
         _done_vector(done, ids.numel, what)
         _stop_ctl(ctl, what)
         return done.shape, "i32"
+    if op == "hist_write":
+        # hist [B, L] <- ids[:, :lead] then tail (with n: its first n[b] columns; nothing for n[b] = 0)
+        # from position pos[b] - back on; indices outside [0, L) are dropped
+        only("back", "lead")
+        arity(3, 5)
+        hist, p, ids = ins[:3]
+        _hist_state(hist, what)
+        _pos_vector(p, hist.shape[0], what)
+        for v, name in zip(ins[2:4], ("ids", "tail")):
+            _req(v.dtype == "i32" and len(v.shape) == 2 and v.shape[0] == hist.shape[0],
+                 f"{what}: {name} must be i32 [{hist.shape[0]}, S], got {v.dtype} {list(v.shape)}")
+        if len(ins) == 5:
+            _req(ins[4].dtype == "i32" and ins[4].shape == (hist.shape[0],),
+                 f"{what}: n must be an i32 [{hist.shape[0]}] (a count per row), got {ins[4].dtype} {list(ins[4].shape)}")
+        back, lead = a.get("back", 0), a.get("lead", ids.shape[1])
+        _req(isinstance(back, int) and not isinstance(back, bool) and 0 <= back <= 1 << 24,
+             f"{what}: back must be an int in [0, 2^24]")
+        _req(isinstance(lead, int) and not isinstance(lead, bool) and 0 <= lead <= ids.shape[1],
+             f"{what}: lead must be an int in [0, {ids.shape[1]}] (ids' columns)")
+        return hist.shape, "i32"
+    if op == "spec_accept":
+        # a verify step's advance per row (ops.tenant.spec_accept): ids and the drawn g [B, K], pos, ctl
+        only("limit")
+        arity(4, 4)
+        ids, g, p, ctl = ins
+        _req(ids.dtype == g.dtype == "i32" and len(ids.shape) == 2 and ids.shape == g.shape
+             and SPEC_MIN_K <= ids.shape[1] <= SPEC_MAX_K,
+             f"{what}: ids and the drawn ids must both be i32 [B, {SPEC_MIN_K} <= K <= {SPEC_MAX_K}], got "
+             f"{ids.dtype} {list(ids.shape)} and {g.dtype} {list(g.shape)}")
+        _pos_vector(p, ids.shape[0], what)
+        _req(ctl.kind == "state" and ctl.dtype == "i32" and ctl.shape == (SPEC_CTL_WORDS,),
+             f"{what}: the speculation control words must be an i32 [{SPEC_CTL_WORDS}] state, got {ctl.kind} "
+             f"{ctl.name!r} {ctl.dtype} {list(ctl.shape)}")
+        _int(a.get("limit"), f"{what}: limit", 1)
+        return (ids.shape[0],), "i32"
+    if op == "pos_advance":
+        only()
+        arity(2, 2)
+        _req(ins[0].dtype == "i32" and len(ins[0].shape) == 1, f"{what}: takes an i32 [B] position state")
+        _req(ins[1].dtype == "i32" and ins[1].shape == ins[0].shape,
+             f"{what}: the advance must be an i32 {list(ins[0].shape)}, got {ins[1].dtype} {list(ins[1].shape)}")
+        return ins[0].shape, "i32"
+    if op == "spec_draft":
+        only("k")
+        arity(2, 2)
+        _hist_state(ins[0], what)
+        _pos_vector(ins[1], ins[0].shape[0], what)
+        k = _int(a.get("k"), f"{what}: k", SPEC_MIN_K)
+        _req(k <= SPEC_MAX_K, f"{what}: k must be <= {SPEC_MAX_K}")
+        return (ins[0].shape[0], k), "i32"
     raise ProgramError(f"{what}: op {op!r} is not one the pod server runs (whitelist: {' '.join(OPS)})")
+
+
+def _hist_state(h: Value, what: str) -> None:
+    _req(h.dtype == "i32" and len(h.shape) == 2 and h.shape[1] <= 1 << 28,
+         f"{what}: hist must be an i32 [B, L <= 2^28] state (the rows' token history), got {h.dtype} {list(h.shape)}")
 
 
 def _pos_vector(p: Value, b: int, what: str) -> None:
@@ -446,7 +501,9 @@ _Q8_CACHE_SLOTS = {"kv_write": {0: 3}, "sdpa_cache": {1: 4, 2: 5}}   # op -> {ca
 # the states a stopping program's ops name: op -> ((role, input slot), ...); a program has one of each
 _STOP_ROLES = {"seen_mark": (("seen", 0),), "penalize": (("seen", 1), ("stopping", 2)),
                "stop_ids": (("done", 1), ("stopping", 2)), "done_mark": (("done", 0), ("stopping", 2)),
-               "pos_add": (("done", 1),)}   # the mask of pos_add(pos, done): the flags stop_ids / done_mark name
+               "pos_add": (("done", 1),),   # the mask of pos_add(pos, done): the flags stop_ids / done_mark name
+               # a speculating program's: the token history and the control words (the budget's end)
+               "hist_write": (("hist", 0),), "spec_draft": (("hist", 0),), "spec_accept": (("speculate", 3),)}
 
 
 def parse_variants(objs: list, payload: bytes | memoryview = b"", gpu: bool = False) -> list[Program]:
@@ -471,9 +528,10 @@ def parse_variants(objs: list, payload: bytes | memoryview = b"", gpu: bool = Fa
         _req(p.inputs[0].shape not in seen, f"two variants take the input shape {list(p.inputs[0].shape)}")
         seen.add(p.inputs[0].shape)
     _req(len({p.sampling_state for p in progs} - {None}) <= 1, "variants must share one sampling control state")
-    for what in ("stopping_state", "done_state", "seen_state"):
+    for what in ("stopping_state", "done_state", "seen_state", "speculate_state", "hist_state"):
         _req(len({getattr(p, what) for p in progs} - {None}) <= 1,
-             f"variants must share one {what.replace('_', ' ')} (the stopping control words, the done flags, the bitmap)")
+             f"variants must share one {what.replace('_', ' ')} (the stopping control words, the done flags, the "
+             f"bitmap; the speculation control words, the token history)")
     return progs
 
 
@@ -538,7 +596,10 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     root_of = {k: k for k in state}
     dead: set[str] = set()
     sampling = None   # the control state of the program's sample nodes
-    stop = {"stopping": None, "done": None, "seen": None}   # a stopping program's control words, flags and bitmap
+    # a stopping program's control words, flags and bitmap; a speculating program's history and control words
+    stop = {"stopping": None, "done": None, "seen": None, "hist": None, "speculate": None}
+    cache_rows: dict[int, str] = {}     # the lengths L of the caches [B, L, Hkv, D] the kv_writes fill -> a node
+    spec_limits: dict[int, str] = {}    # the ``limit`` of every spec_accept -> a node
     scales_of: dict[str, str] = {}      # a scales state -> the i8 cache (root) whose row scales it holds
     cache_scales: dict[str, str] = {}   # and back
     other_use: dict[str, str] = {}      # a state -> the first node naming it as anything but a cache's scales
@@ -609,6 +670,10 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
             _req(stop[role] in (None, root), f"node {n.output!r} ({op}): a program has one {role} state; "
                  f"{stop[role]!r} and {root!r} are two")
             stop[role] = root
+        if op == "kv_write":
+            cache_rows.setdefault(values[refs[0]].shape[1], f"node {n.output!r} ({op})")
+        if op == "spec_accept":
+            spec_limits.setdefault(attrs["limit"], f"node {n.output!r} ({op})")
         define(Value(n.output, shape, dt, "node"))
         nodes.append(n)
     outs = obj.get("outputs")
@@ -621,9 +686,20 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
         _req(s_ not in other_use, f"{other_use.get(s_)}: {s_!r} holds the scales of the i8 cache {scales_of[s_]!r}; "
              f"a scales state is named only beside that cache in kv_write / sdpa_cache")
         _req(s_ not in outs, f"the scales state {s_!r} of the i8 cache {scales_of[s_]!r} cannot be an output")
+    # the control states: at most one of each kind, and each its own state
+    ctls = [c for c in (sampling, stop["stopping"], stop["speculate"]) if c is not None]
+    _req(len(set(ctls)) == len(ctls), f"the control states of different kinds must be different states, got {ctls}")
+    if stop["hist"] is not None:   # positions index the history as they index the caches
+        L = state[stop["hist"]].shape[1]
+        for rows, where in {**cache_rows, **spec_limits}.items():
+            _req(rows == L, f"{where}: the token history {stop['hist']!r} has {L} positions, the "
+                 f"{'caches have' if rows in cache_rows else 'limit is'} {rows}: hist must be [batch, L] with L the caches' length")
+    else:
+        _req(not spec_limits, "a spec_accept needs the program's token history (a hist_write or spec_draft node)")
     _req(not any(o in root_of for o in outs), "a state (or a version of one) cannot be an output: it is mutable")
     _req(not any(values[o].dtype == "i8" for o in outs), "an i8 param cannot be an output")
     return Program(name, inputs, params, layout, nodes, list(outs), values, payload, state=state,
                    state_root={k: v for k, v in root_of.items() if k != v}, sampling_state=sampling,
-                   stopping_state=stop["stopping"], done_state=stop["done"], seen_state=stop["seen"])
+                   stopping_state=stop["stopping"], done_state=stop["done"], seen_state=stop["seen"],
+                   speculate_state=stop["speculate"], hist_state=stop["hist"])
 

@@ -119,6 +119,8 @@ class Tenant:
     stopping_state: str | None = None               # the control state of its programs' stopping ops (stop ids, penalty)
     done_state: str | None = None                   # ... the rows' done flags (replied; the server loop's early exit)
     seen_state: str | None = None                   # ... the rows' token bitmaps (never replied)
+    speculate_state: str | None = None              # the control state of its verify program (the token budget's end)
+    hist_state: str | None = None                   # ... the rows' token history (a speculating generate's tokens)
 
 
 @dataclass
@@ -155,6 +157,7 @@ class _Job:
     ctl: np.ndarray | None = None  # the sampling control words written before the run (sampling tenants)
     stop: np.ndarray | None = None  # the stopping control words written before the run (stopping tenants)
     steps_run: int = 0             # "generate": the runs made (fewer than ``steps`` once every row was done)
+    spec: np.ndarray | None = None  # the speculation control words written before the run (speculating tenants)
 
 
 class AdmissionError(RuntimeError):
@@ -204,6 +207,24 @@ def _stopping_words(req: dict, tenant: Tenant) -> np.ndarray | None:
     return stopping_ctl(**s, id_bound=tenant.id_bound)
 
 
+def _speculate_words(req: dict, tenant: Tenant) -> np.ndarray | None:
+    """The control words a request's optional ``"speculate"`` object asks for:
+    ``{"end": int}`` -- no verify step advances a row's counter past ``end``
+    (``ops.tenant.speculate_ctl``).  A speculating tenant's request without
+    one gets zeros: no bound but the cache.  None for a tenant whose programs
+    have no verify step."""
+    s = req.get("speculate")
+    if s is None:
+        return np.zeros(4, dtype=np.int32) if tenant.speculate_state else None
+    if not tenant.speculate_state:
+        raise ValueError("speculate: the tenant's programs have no verify step (register with speculate=K)")
+    if not isinstance(s, dict) or set(s) - {"end"}:
+        raise ValueError("speculate must be an object with the key 'end'")
+    from ..ops.tenant import speculate_ctl
+
+    return speculate_ctl(**s)
+
+
 def _stop_ids_of(words: np.ndarray | None) -> list[int]:
     """The stop ids the control words arm ([] without any)."""
     return [] if words is None else [int(v) for v in words[3:3 + int(words[2])]]
@@ -245,7 +266,7 @@ def _sampling_state(progs) -> str | None:
 def _stop_states(progs) -> dict:
     """The states of the programs' stopping ops (variants share them), as Tenant fields."""
     return {k: next((getattr(p, k) for p in progs if getattr(p, k)), None)
-            for k in ("stopping_state", "done_state", "seen_state")}
+            for k in ("stopping_state", "done_state", "seen_state", "speculate_state", "hist_state")}
 
 
 def _target_wire(trainer) -> str:
@@ -670,7 +691,7 @@ class PodServer:
                         else:
                             want = bool(want)
                         job = _Job(tenant, payload, want, shp, ctl=_sampling_words(req, tenant),
-                                   stop=_stopping_words(req, tenant))
+                                   stop=_stopping_words(req, tenant), spec=_speculate_words(req, tenant))
                         self._jobs.put(job, hi=tenant.latency)
                         job.done.wait()
                         if job.error:
@@ -694,7 +715,8 @@ class PodServer:
                         shp = tuple(int(d) for d in shp) if isinstance(shp, list) and len(shp) <= 8 else None
                         _check_wire_dtype(req.get("dtype"), _wire_dtype(tenant.x), "input")
                         job = _Job(tenant, payload, [feed], shp, kind="generate", steps=n, feed=feed,
-                                   ctl=_sampling_words(req, tenant), stop=_stopping_words(req, tenant))
+                                   ctl=_sampling_words(req, tenant), stop=_stopping_words(req, tenant),
+                                   spec=_speculate_words(req, tenant))
                         self._jobs.put(job, hi=tenant.latency)
                         job.done.wait()
                         if job.error:
@@ -1215,6 +1237,26 @@ class PodServer:
         # that point would only emit pad ids; a finished row's counter and cache rows never change)
         stops = _stop_ids_of(job.stop) if gen else []
         done = t.state.get(t.done_state) if stops else None
+        # a speculating generate (``"speculate": {"end": E}``): the verify variant replayed back to back, its
+        # ``next_ids`` fed on the device and each step's ``n_acc`` (the last output) collected there; the
+        # loop leaves once every row's counter is at E, after at most ``steps`` = n - 1 runs (a step
+        # past that point advances by 0 and changes nothing), and the tokens are hist[:, E - steps : E + 1]
+        end = int(job.spec[0]) if gen and job.spec is not None else 0
+        spos = None
+        if end:
+            if len(t.pos_limits) != 1 or end - job.steps < 1 or end >= t.state[t.hist_state].shape[1]:
+                raise ValueError(f"speculate: end {end} with {job.steps} steps needs one position state, a prompt of "
+                                 f"end - steps >= 1 tokens and end < {t.state[t.hist_state].shape[1]} (the cache)")
+            spos = t.state[next(iter(t.pos_limits))]
+
+        def n_acc_of(outs):
+            a = outs[-1]
+            if a.dtype != torch.int32 or tuple(a.shape) != tuple(spos.shape):
+                raise ValueError(f"speculate: the variant's last output must be n_acc, i32 {list(spos.shape)}")
+            return a
+
+        def spec_tokens():
+            return t.state[t.hist_state][:, end - job.steps:end + 1]
         done0 = None   # the flags before the loop's first step: a row the prefill finished emits only pad ids in it
         with torch.no_grad():
             if not self.gpu:
@@ -1225,10 +1267,21 @@ class PodServer:
                     t.state[t.sampling_state].copy_(torch.from_numpy(job.ctl))
                 if job.stop is not None:
                     t.state[t.stopping_state].copy_(torch.from_numpy(job.stop))
+                if job.spec is not None:
+                    t.state[t.speculate_state].copy_(torch.from_numpy(job.spec))
                 if x_in is not None:
                     v.x.copy_(torch.from_numpy(x_in.copy()).view(v.x.shape))
                 v.outputs = outs = v.model(v.x)
-                if gen:
+                if end:
+                    accs = [n_acc_of(outs).clone()]
+                    while len(accs) < job.steps and not bool((spos >= end).all()):   # checked after every step
+                        v.x.copy_(fed(outs).reshape(v.x.shape))
+                        v.outputs = outs = v.model(v.x)
+                        accs.append(n_acc_of(outs).clone())
+                    job.steps_run = len(accs)
+                    outs = [spec_tokens().clone(), torch.stack(accs)]
+                    job.want_outputs = [0, 1]
+                elif gen:
                     toks = [fed(outs).clone()]
                     for _ in range(job.steps - 1):
                         if done is not None and bool((done != 0).all()):   # checked after every step
@@ -1254,6 +1307,11 @@ class PodServer:
                         hb = _pinned(t.host, "stopping", ctl.shape, ctl.dtype)
                         hb.numpy()[:] = job.stop
                         ctl.copy_(hb, non_blocking=True)
+                    if job.spec is not None:   # and its speculation words
+                        ctl = t.state[t.speculate_state]
+                        hb = _pinned(t.host, "speculate", ctl.shape, ctl.dtype)
+                        hb.numpy()[:] = job.spec
+                        ctl.copy_(hb, non_blocking=True)
                     if x_in is not None:
                         if str(v.x.dtype)[6:] == str(x_in.dtype):
                             # through a pinned buffer: an in-stream copy, no blocking pageable one
@@ -1269,6 +1327,10 @@ class PodServer:
                     solo = alone and v.solo_graph is not None
                     toks = window = None
                     every = self.stop_check_every
+                    # what the loop looks at every window: the done flags (all set), or a speculating
+                    # generate's counters (all at the budget's end)
+                    watch = done if done is not None else spos
+                    over = (lambda h: bool((h != 0).all())) if done is not None else (lambda h: bool((h >= end).all()))
                     for i in range(job.steps if gen else 1):
                         if i:   # generate: the previous run's ids are this run's input, on the device
                             v.x.copy_(o.reshape(v.x.shape))
@@ -1283,25 +1345,31 @@ class PodServer:
                             v.outputs = outs = v.model(v.x)
                         if gen:
                             o = fed(outs)
+                            kept = n_acc_of(outs) if end else o   # per step: the advance, or the ids themselves
                             if toks is None:
-                                toks = torch.empty((job.steps,) + tuple(o.shape), dtype=o.dtype, device=o.device)
-                            toks[i].copy_(o)
+                                toks = torch.empty((job.steps,) + tuple(kept.shape), dtype=kept.dtype,
+                                                   device=kept.device)
+                            toks[i].copy_(kept)
                             job.steps_run = i + 1
-                        if done is not None and (i + 1) % every == 0 and i + 1 < job.steps:
+                        if watch is not None and (i + 1) % every == 0 and i + 1 < job.steps:
                             # window j's flags: a queued copy and an event, looked at only after window
                             # j + 1 is queued -- the lane never waits with nothing behind it on the GPU
                             k = (i // every) & 1
-                            hb = _pinned(t.host, ("done", k), done.shape, done.dtype)
-                            hb.copy_(done, non_blocking=True)
+                            hb = _pinned(t.host, ("done", k), watch.shape, watch.dtype)
+                            hb.copy_(watch, non_blocking=True)
                             ev = t.host.get(("done_event", k)) or t.host.setdefault(("done_event", k),
                                                                                     torch.cuda.Event())
                             ev.record(s)
                             prev, window = window, (ev, hb)
                             if prev is not None:
                                 prev[0].synchronize()
-                                if bool((prev[1] != 0).all()):
+                                if over(prev[1]):
                                     break
-                    if gen:
+                    if end:
+                        fetch = [_fetch_start(spec_tokens().contiguous(), v.host, "spec_tokens"),
+                                 _fetch_start(toks[:job.steps_run], v.host, "gen")]
+                        job.want_outputs = [0, 1]
+                    elif gen:
                         fetch = [_fetch_start(toks[:job.steps_run], v.host, "gen")]
                     else:
                         fetch = [_fetch_start(outs[i], v.host, ("out", solo, i))
@@ -1343,7 +1411,7 @@ class PodServer:
     @staticmethod
     def _not_counters(t: Tenant) -> tuple:
         """Small i32 states that are no counters: the control words and (at a tiny vocab) the bitmaps."""
-        return (t.sampling_state, t.stopping_state, t.seen_state)
+        return (t.sampling_state, t.stopping_state, t.seen_state, t.speculate_state, t.hist_state)
 
     def _counters_start(self, t: Tenant):
         """``_counters`` behind the lane's one synchronisation: the copies are
