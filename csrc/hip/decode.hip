@@ -1206,6 +1206,66 @@ __device__ __forceinline__ float4 gemv_x4(const Parts& pt, const void* x, int xb
   return pt.ws ? parts_x4(pt, m, k) : ld4(x, (long long)m * ldx + k, xbf);
 }
 
+// The adapter operand of a GEMV (the LoRA expand): output (m, n) gets + sum_j B[a_m - 1][n][j] t[m][j]
+// before bias, activation, GLU or residual, with a_m = sel[m / rps]; rows whose a_m is outside [1, n]
+// (0: the base model) skip the sum and are the plain kernel's bit for bit.  t [M][R] comes from
+// nos_lora_shrink; B [n][N][R] has the adapter stride bsb and the row stride ldb.
+struct Lora {
+  const float* t = nullptr;
+  const float* B = nullptr;
+  const int* sel = nullptr;
+  long long bsb = 0;
+  int ldb = 0, R = 0, n = 0, rps = 1;
+};
+constexpr int LORA_MAX_R = 64;   // a lane per j: the R-long sum is one wave reduction
+template <bool L>
+struct LoraArg {
+  int none = 0;
+};
+template <>
+struct LoraArg<true> {
+  Lora lo;
+};
+// t beside x in LDS (nothing in the plain instantiations)
+template <bool L, int M>
+struct LoraLds {};
+template <int M>
+struct LoraLds<true, M> {
+  float t[M * LORA_MAX_R];
+};
+
+template <int M>
+__device__ __forceinline__ void lora_stage(LoraLds<true, M>& ll, const Lora& lo, int tid) {
+  for (int e = tid; e < M * lo.R; e += 256) ll.t[e] = lo.t[e];
+}
+
+// the rows' adapters (0: none, the base model), read at the kernel's start: wave-uniform registers
+template <int M>
+__device__ __forceinline__ void lora_rows(const Lora& lo, int (&am)[M]) {
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const int a = lo.sel[m / lo.rps];
+    am[m] = (a >= 1 && a <= lo.n) ? a : 0;
+  }
+}
+
+// lane j's B[a - 1][n][j] of the delta of (a row with adapter a, weight row n): it depends on sel and
+// n alone, so it is issued with the weight loads (the first group's with the weight prefetch, ahead
+// of the x staging); times t[m][j] it is summed over the wave after the main product
+__device__ __forceinline__ float lora_b(const Lora& lo, int a, int n, int lane) {
+  return (a != 0 && lane < lo.R) ? lo.B[(long long)(a - 1) * lo.bsb + (long long)n * lo.ldb + lane] : 0.f;
+}
+
+// the scaled product v of (m, a weight row) plus the row's summed adapter delta d; a base row adds
+// nothing (the plain kernel's bits), and the plain instantiations return v
+template <bool L>
+__device__ __forceinline__ float lora_add(float v, int a, float d) {
+  if constexpr (L) {
+    if (a != 0) v += d;
+  }
+  return v;
+}
+
 // one finished output (m, n) of a GEMV: v = the scaled product; bias in bbf's dtype, y / R in xbf's
 __device__ __forceinline__ void gemv_finish(float v, int m, int n, int epi, const void* bias, int bbf, const void* res,
                                             int ldr, void* y, int ldy, int xbf) {
@@ -1227,15 +1287,16 @@ __device__ __forceinline__ void gemv_finish_glu(float g, float u, int m, int n, 
   stf(y, (long long)m * ldy + n, g / (1.f + __expf(-g)) * u, xbf);
 }
 
-template <int M, int WBF, int KU>
+template <int M, int WBF, int KU, bool LORA>
 __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ x, int xbf, int ldx,
                                                    const void* __restrict__ w, int /*wbf = WBF*/, int ldw,
                                                    const void* __restrict__ bias, const void* __restrict__ res,
                                                    int ldr, void* __restrict__ y, int ldy, int N, int K, int epi,
-                                                   float rms_eps, Parts pt) {
+                                                   float rms_eps, Parts pt, LoraArg<LORA> la) {
   constexpr int wbf = WBF;  // the weight dtype fixed at compile time: no per-load dtype branch
   extern __shared__ __attribute__((aligned(16))) float xs[];  // [M][K] fp32
   __shared__ float rsc[M];
+  __shared__ LoraLds<LORA, M> ll;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const bool glu = (epi & EPI_GLU) != 0;
   const int Nh = N / 2;                                          // GLU: output columns
@@ -1265,10 +1326,29 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ x, i
     rows_of(blockIdx.x, n0, w0, w1);
     load_chunk(w0, w1, lane * 4, pa, pc);
   }
+  [[maybe_unused]] int am[M];        // LORA: the rows' adapters
+  [[maybe_unused]] float pb[2][M];   // LORA: the first group's B values, in flight with its weights
+  // LORA: the weight rows (n0's pair) the delta of column group n0 reads, as rows_of clamps them
+  auto lora_rows_of = [&](int n0, int (&nr)[2]) {
+    nr[0] = glu ? min(n0, Nh - 1) : min(n0, N - 1);
+    nr[1] = glu ? min(n0, Nh - 1) + Nh : min(n0 + 1, N - 1);
+  };
+  if constexpr (LORA) {
+    lora_rows<M>(la.lo, am);
+    if ((int)blockIdx.x < ngrp) {
+      int nr[2];
+      lora_rows_of(glu ? blockIdx.x * 4 + wid : blockIdx.x * 8 + wid * 2, nr);
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int m = 0; m < M; ++m) pb[c][m] = lora_b(la.lo, am[m], nr[c], lane);
+    }
+  }
   for (int e = tid * 4; e < M * K; e += 1024) {
     const int m = e / K, k = e % K;
     *reinterpret_cast<float4*>(&xs[e]) = gemv_x4(pt, x, xbf, ldx, m, k);
   }
+  if constexpr (LORA) lora_stage<M>(ll, la.lo, tid);
   __syncthreads();
   if (rms_eps > 0.f) {  // RMSNorm of each row, gamma folded into W
     for (int m = wid; m < M; m += 4) {
@@ -1290,6 +1370,18 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ x, i
     for (int c = 0; c < 2; ++c)
 #pragma unroll
       for (int m = 0; m < M; ++m) acc[c][m] = 0.f;
+    float dl[2][M] = {};   // LORA: the adapter delta of (m, row c), a term per lane until it is summed
+    if constexpr (LORA) {
+      int nr[2];
+      lora_rows_of(n0, nr);
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+          const float b = grp == (int)blockIdx.x ? pb[c][m] : lora_b(la.lo, am[m], nr[c], lane);
+          dl[c][m] = (am[m] != 0 && lane < la.lo.R) ? b * ll.t[m * la.lo.R + lane] : 0.f;
+        }
+    }
     // KU K steps' weight loads issued together (2 KU float4 in flight per lane): the
     // one-step loop waited a full memory latency per 256 columns of K; KU = 12 takes
     // K <= 3072 (a down projection) in one batch (the same summation order as KU = 4)
@@ -1322,11 +1414,19 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ x, i
     for (int c = 0; c < 2; ++c)
 #pragma unroll
       for (int m = 0; m < M; ++m) acc[c][m] = nos::wave_sum(acc[c][m]);
+    if constexpr (LORA) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+          if (am[m] != 0) dl[c][m] = nos::wave_sum(dl[c][m]);
+    }
     if (glu) {  // lane m finishes output (m, n0): silu(gate) * up
 #pragma unroll
       for (int m = 0; m < M; ++m)
         if (lane == m && n0 < Nh)
-          gemv_finish_glu(acc[0][m] * rsc[m], acc[1][m] * rsc[m], m, n0, Nh, epi, bias, wbf, y, ldy, xbf);
+          gemv_finish_glu(lora_add<LORA>(acc[0][m] * rsc[m], am[m], dl[0][m]),
+                          lora_add<LORA>(acc[1][m] * rsc[m], am[m], dl[1][m]), m, n0, Nh, epi, bias, wbf, y, ldy, xbf);
       continue;
     }
     // lane (c * M + m) finishes output (m, n0 + c)
@@ -1336,7 +1436,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ x, i
       for (int m = 0; m < M; ++m) {
         const int n = n0 + c;
         if (lane == c * M + m && n < N)
-          gemv_finish(acc[c][m] * rsc[m], m, n, epi, bias, wbf, res, ldr, y, ldy, xbf);
+          gemv_finish(lora_add<LORA>(acc[c][m] * rsc[m], am[m], dl[c][m]), m, n, epi, bias, wbf, res, ldr, y, ldy, xbf);
       }
   }
 }
@@ -1355,17 +1455,19 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ x, i
 // leave no room to fold it into W) multiplies x on its way into LDS.
 constexpr int Q8_R = 4;   // weight rows per wave: 16 per workgroup pass (GLU: 8 gate + 8 up)
 
-template <int M, int KU>
+template <int M, int KU, bool LORA>
 __global__ __launch_bounds__(256) void gemv_q8_kernel(const float* __restrict__ x, int ldx,
                                                       const signed char* __restrict__ w, int ldw,
                                                       const float* __restrict__ wscale,
                                                       const float* __restrict__ gamma, const float* __restrict__ bias,
                                                       const float* __restrict__ res, int ldr, float* __restrict__ y,
-                                                      int ldy, int N, int K, int epi, float rms_eps, Parts pt) {
+                                                      int ldy, int N, int K, int epi, float rms_eps, Parts pt,
+                                                      LoraArg<LORA> la) {
   static_assert(Q8_R == 4, "the 4 x 4 word table below and the GLU pairing are written for four rows");
   extern __shared__ __attribute__((aligned(16))) float xs[];  // [M][K] fp32, each row permuted as above
   __shared__ float rsc[M];
   __shared__ float sqp[4][M];   // the waves' sums of squares of each x row
+  __shared__ LoraLds<LORA, M> ll;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const bool glu = (epi & EPI_GLU) != 0;
   const int Nh = N / 2;
@@ -1396,6 +1498,22 @@ __global__ __launch_bounds__(256) void gemv_q8_kernel(const float* __restrict__ 
     long long wr[Q8_R];
     rows_of(blockIdx.x, n0, wr);
     load_chunk(wr, 0, pa);
+  }
+  [[maybe_unused]] int am[M];           // LORA: the rows' adapters
+  [[maybe_unused]] float pb[Q8_R][M];   // LORA: the first group's B values, in flight with its weights
+  // LORA: the weight row of the wave's row c of column group n0, as rows_of clamps it
+  auto lora_row_of = [&](int n0, int c) {
+    return glu ? min(n0 + (c & 1), Nh - 1) + (c >> 1) * Nh : min(n0 + c, N - 1);
+  };
+  if constexpr (LORA) {
+    lora_rows<M>(la.lo, am);
+    if ((int)blockIdx.x < ngrp) {
+      const int n0 = glu ? blockIdx.x * 8 + wid * 2 : blockIdx.x * 16 + wid * Q8_R;
+#pragma unroll
+      for (int c = 0; c < Q8_R; ++c)
+#pragma unroll
+        for (int m = 0; m < M; ++m) pb[c][m] = lora_b(la.lo, am[m], lora_row_of(n0, c), lane);
+    }
   }
   float sq[M];
 #pragma unroll
@@ -1441,6 +1559,7 @@ __global__ __launch_bounds__(256) void gemv_q8_kernel(const float* __restrict__ 
       if (lane == 0) sqp[wid][m] = t;
     }
   }
+  if constexpr (LORA) lora_stage<M>(ll, la.lo, tid);
   __syncthreads();
   if (tid < M)
     rsc[tid] = rms_eps > 0.f
@@ -1456,6 +1575,16 @@ __global__ __launch_bounds__(256) void gemv_q8_kernel(const float* __restrict__ 
     for (int c = 0; c < Q8_R; ++c)
 #pragma unroll
       for (int m = 0; m < M; ++m) acc[c][m] = 0.f;
+    float dl[Q8_R][M] = {};   // LORA: the adapter delta of (m, row c), a term per lane until it is summed
+    if constexpr (LORA) {
+#pragma unroll
+      for (int c = 0; c < Q8_R; ++c)
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+          const float b = grp == (int)blockIdx.x ? pb[c][m] : lora_b(la.lo, am[m], lora_row_of(n0, c), lane);
+          dl[c][m] = (am[m] != 0 && lane < la.lo.R) ? b * ll.t[m * la.lo.R + lane] : 0.f;
+        }
+    }
     for (int kb = 0; kb < K; kb += 1024 * KU) {
       uint4 ra[Q8_R][KU];
       if (kb == 0) {   // prefetched; the workgroup's next group's first chunk goes out before this one's math
@@ -1501,6 +1630,13 @@ __global__ __launch_bounds__(256) void gemv_q8_kernel(const float* __restrict__ 
     for (int c = 0; c < Q8_R; ++c)
 #pragma unroll
       for (int m = 0; m < M; ++m) acc[c][m] = nos::wave_sum(acc[c][m]);
+    if constexpr (LORA) {
+#pragma unroll
+      for (int c = 0; c < Q8_R; ++c)
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+          if (am[m] != 0) dl[c][m] = nos::wave_sum(dl[c][m]);
+    }
     if (glu) {  // lane (c * M + m), c < 2, finishes output (m, n0 + c) from gate row c and up row c + 2
 #pragma unroll
       for (int c = 0; c < 2; ++c)
@@ -1508,8 +1644,9 @@ __global__ __launch_bounds__(256) void gemv_q8_kernel(const float* __restrict__ 
         for (int m = 0; m < M; ++m) {
           const int n = n0 + c;
           if (lane == c * M + m && n < Nh)
-            gemv_finish_glu(acc[c][m] * wscale[n] * rsc[m], acc[c + 2][m] * wscale[n + Nh] * rsc[m], m, n, Nh, epi,
-                            bias, 0, y, ldy, 0);
+            gemv_finish_glu(lora_add<LORA>(acc[c][m] * wscale[n] * rsc[m], am[m], dl[c][m]),
+                            lora_add<LORA>(acc[c + 2][m] * wscale[n + Nh] * rsc[m], am[m], dl[c + 2][m]), m, n, Nh,
+                            epi, bias, 0, y, ldy, 0);
         }
       continue;
     }
@@ -1520,8 +1657,70 @@ __global__ __launch_bounds__(256) void gemv_q8_kernel(const float* __restrict__ 
       for (int m = 0; m < M; ++m) {
         const int n = n0 + c;
         if (lane == c * M + m && n < N)
-          gemv_finish(acc[c][m] * wscale[n] * rsc[m], m, n, epi, bias, 0, res, ldr, y, ldy, 0);
+          gemv_finish(lora_add<LORA>(acc[c][m] * wscale[n] * rsc[m], am[m], dl[c][m]), m, n, epi, bias, 0, res, ldr, y,
+                      ldy, 0);
       }
+  }
+}
+
+// ------------------------------------------------------------------ LoRA shrink (M <= 8)
+// t[m][j] = sum_k A[a_m - 1][j][k] xn[m][k], a_m = sel[m / rps]: the low-rank activations the GEMV after
+// it expands (Lora).  xn is the x that GEMV multiplies: read with its staging helper (gemv_x4: an
+// O-projection's x combined from the decode partials in the same arithmetic) and, under an RMSNorm
+// prologue, normalised with the row's statistic and gamma.  A workgroup per (m, four rows j of A), its
+// four waves splitting K: x is read once for four 16-byte streams of A, a 1024-wide row is ONE load
+// per lane and stream (a down projection's 2816: three, issued together), and the waves' partial
+// sums meet in LDS.  A row whose a_m is outside [1, n] writes zeros and reads nothing.
+__global__ __launch_bounds__(256) void lora_shrink_kernel(const float* __restrict__ x, int ldx,
+                                                          const float* __restrict__ A, long long bsa, int lda,
+                                                          const int* __restrict__ sel, int n, int rps,
+                                                          const float* __restrict__ gamma, float rms_eps,
+                                                          float* __restrict__ t, int M, int R, int K, Parts pt) {
+  __shared__ float part[4][5];   // each wave's four partial dot products and its sum of squares
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int nq = R / 4;
+  const int m = blockIdx.x / nq, j0 = (blockIdx.x % nq) * 4;   // grid: M x R / 4 workgroups
+  const int a = sel[m / rps];
+  float* out = t + (long long)m * R + j0;
+  if (a < 1 || a > n) {   // the whole workgroup: no barrier is left behind
+    if (tid < 4) out[tid] = 0.f;
+    return;
+  }
+  const float* Ar = A + (long long)(a - 1) * bsa + (long long)j0 * lda;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  float q = 0.f;
+#pragma unroll 3
+  for (int k = tid * 4; k < K; k += 1024) {
+    float4 av[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) av[c] = *reinterpret_cast<const float4*>(Ar + (long long)c * lda + k);
+    float4 xv = gemv_x4(pt, x, 0, ldx, m, k);
+    if (rms_eps > 0.f) {
+      q = fmaf(xv.x, xv.x, fmaf(xv.y, xv.y, fmaf(xv.z, xv.z, fmaf(xv.w, xv.w, q))));
+      if (gamma != nullptr) {
+        const float4 g = *reinterpret_cast<const float4*>(gamma + k);
+        xv = float4{xv.x * g.x, xv.y * g.y, xv.z * g.z, xv.w * g.w};
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      acc[c] = fmaf(av[c].x, xv.x, fmaf(av[c].y, xv.y, fmaf(av[c].z, xv.z, fmaf(av[c].w, xv.w, acc[c]))));
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) acc[c] = nos::wave_sum(acc[c]);
+  q = nos::wave_sum(q);
+  if (lane == 0) {
+    part[wid][0] = acc[0];
+    part[wid][1] = acc[1];
+    part[wid][2] = acc[2];
+    part[wid][3] = acc[3];
+    part[wid][4] = q;
+  }
+  __syncthreads();
+  if (tid < 4) {
+    const float v = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+    const float qs = (part[0][4] + part[1][4]) + (part[2][4] + part[3][4]);
+    out[tid] = rms_eps > 0.f ? v * rsqrtf(qs / (float)K + rms_eps) : v;
   }
 }
 
@@ -1840,7 +2039,20 @@ NOS_API int nos_spec_step(int* hist, int B, int L, int* pos, const int* ids, con
 // walk the N / 8 column groups.
 static int gemv_launch(const void* x, int xbf, int ldx, const void* w, int wbf, int ldw, const void* bias,
                        const void* res, int ldr, void* y, int ldy, int M, int N, int K, int epi, float rms_eps,
-                       Parts pt, hipStream_t stream);
+                       Parts pt, hipStream_t stream, const Lora* lo = nullptr);
+
+// the adapter operand of a GEMV over M rows and N weight rows (Lora), checked before any launch
+static bool lora_ok(const Lora& lo, int M, int N) {
+  return lo.t && lo.B && lo.sel && lo.R >= 4 && lo.R <= LORA_MAX_R && (lo.R % 4) == 0 && lo.n >= 1 && lo.rps >= 1 &&
+         lo.ldb >= lo.R && lo.bsb >= (long long)(N - 1) * lo.ldb + lo.R && M >= 1 && N >= 1 &&
+         !((uintptr_t)lo.t & 15) && !((uintptr_t)lo.B & 15);
+}
+
+// the decode partials as a GEMV's x (nos_gemv_partials): K = Hkv x G x D columns of M sequences
+static bool parts_ok(const float* ws, long long ws_n, int NS, int R, int G, int Hkv, int D, int M, int K) {
+  return ws && NS > 0 && G > 0 && Hkv > 0 && (D == 64 || D == 128) && R == G && K == Hkv * G * D && M > 0 && M <= 8 &&
+         ws_n >= (long long)M * Hkv * NS * R * (D + 2);
+}
 
 NOS_API int nos_gemv(const void* x, int xbf, int ldx, const void* w, int wbf, int ldw, const void* bias,
                      const void* res, int ldr, void* y, int ldy, int M, int N, int K, int epi, float rms_eps,
@@ -1880,7 +2092,7 @@ NOS_API int nos_gemv_partials(const float* ws, long long ws_n, int NS, int R, in
 
 static int gemv_launch(const void* x, int xbf, int ldx, const void* w, int wbf, int ldw, const void* bias,
                        const void* res, int ldr, void* y, int ldy, int M, int N, int K, int epi, float rms_eps,
-                       Parts pt, hipStream_t stream) {
+                       Parts pt, hipStream_t stream, const Lora* lo) {
   const int ngrp = (epi & EPI_GLU) ? (N / 2 + 3) / 4 : (N + 7) / 8;
   // every column group its own workgroup up to 16 per CU: a vocabulary head (4000 groups) no
   // longer walks 4 groups per workgroup one memory round trip after another
@@ -1888,10 +2100,19 @@ static int gemv_launch(const void* x, int xbf, int ldx, const void* w, int wbf, 
   const unsigned grid = (unsigned)(ngrp < cap ? ngrp : cap);
   const size_t lds = (size_t)M * K * 4;
 #define NOS_GEMV_KU(m, b, ku)                                                                                         \
-  hipLaunchKernelGGL((gemv_kernel<m, b, ku>), dim3(grid), dim3(256), lds, stream, x, xbf, ldx, w, wbf, ldw, bias, res, \
-                     ldr, y, ldy, N, K, epi, rms_eps, pt)
+  hipLaunchKernelGGL((gemv_kernel<m, b, ku, false>), dim3(grid), dim3(256), lds, stream, x, xbf, ldx, w, wbf, ldw,    \
+                     bias, res, ldr, y, ldy, N, K, epi, rms_eps, pt, LoraArg<false>{})
+  // the adapter instantiations: fp32 x and W (adapters are an fp32 tenant's)
+#define NOS_GEMV_LORA_KU(m, ku)                                                                                        \
+  hipLaunchKernelGGL((gemv_kernel<m, 0, ku, true>), dim3(grid), dim3(256), lds, stream, x, xbf, ldx, w, wbf, ldw, bias, \
+                     res, ldr, y, ldy, N, K, epi, rms_eps, pt, LoraArg<true>{*lo})
 #define NOS_GEMV(m)                                                                                                   \
-  if (K > 1024) {                                                                                                     \
+  if (lo != nullptr) {                                                                                                \
+    if (K > 1024)                                                                                                     \
+      NOS_GEMV_LORA_KU(m, 12);                                                                                        \
+    else                                                                                                              \
+      NOS_GEMV_LORA_KU(m, 4);                                                                                         \
+  } else if (K > 1024) {                                                                                                     \
     if (wbf)                                                                                                          \
       NOS_GEMV_KU(m, 1, 12);                                                                                          \
     else                                                                                                              \
@@ -1912,6 +2133,7 @@ static int gemv_launch(const void* x, int xbf, int ldx, const void* w, int wbf, 
     default: NOS_GEMV(8); break;
   }
 #undef NOS_GEMV
+#undef NOS_GEMV_LORA_KU
 #undef NOS_GEMV_KU
   return (int)hipGetLastError();
 }
@@ -1922,7 +2144,7 @@ static int gemv_launch(const void* x, int xbf, int ldx, const void* w, int wbf, 
 // per CU walk the N / 16 column groups.
 static int gemv_q8_launch(const float* x, int ldx, const void* wq, int ldw, const float* wscale, const float* gamma,
                           const float* bias, const float* res, int ldr, float* y, int ldy, int M, int N, int K,
-                          int epi, float rms_eps, Parts pt, hipStream_t stream) {
+                          int epi, float rms_eps, Parts pt, hipStream_t stream, const Lora* lo = nullptr) {
   if (!wq || !wscale || !y || M <= 0 || M > 8 || N <= 0 || K <= 0 || (K % 16) || ldw < K || (ldw % 16) ||
       ((uintptr_t)wq & 15) || (long long)M * K * 4 > 65536 || ((epi & EPI_BIAS) && !bias) ||
       ((epi & EPI_RESID) && (!res || ldr < N)) || ldy < ((epi & EPI_GLU) ? N / 2 : N) ||
@@ -1936,17 +2158,23 @@ static int gemv_q8_launch(const float* x, int ldx, const void* wq, int ldw, cons
   const int cap = 3 * nos_effective_cus();
   const unsigned grid = (unsigned)(ngrp < cap ? ngrp : cap);
   const size_t lds = (size_t)M * K * 4;
-#define NOS_GEMV_Q8_KU(m, ku)                                                                                  \
-  hipLaunchKernelGGL((gemv_q8_kernel<m, ku>), dim3(grid), dim3(256), lds, stream, x, ldx,                      \
-                     static_cast<const signed char*>(wq), ldw, wscale, gamma, bias, res, ldr, y, ldy, N, K, epi, \
-                     rms_eps, pt)
+#define NOS_GEMV_Q8_KU(m, ku)                                                                                     \
+  if (lo != nullptr)                                                                                              \
+    hipLaunchKernelGGL((gemv_q8_kernel<m, ku, true>), dim3(grid), dim3(256), lds, stream, x, ldx,                 \
+                       static_cast<const signed char*>(wq), ldw, wscale, gamma, bias, res, ldr, y, ldy, N, K, epi, \
+                       rms_eps, pt, LoraArg<true>{*lo});                                                          \
+  else                                                                                                            \
+    hipLaunchKernelGGL((gemv_q8_kernel<m, ku, false>), dim3(grid), dim3(256), lds, stream, x, ldx,                \
+                       static_cast<const signed char*>(wq), ldw, wscale, gamma, bias, res, ldr, y, ldy, N, K, epi, \
+                       rms_eps, pt, LoraArg<false>{})
   // K <= 1024: the whole row in one batch of Q8_R loads per lane; longer rows (a down projection's
   // 2816) in batches of 3 x Q8_R
 #define NOS_GEMV_Q8(m)      \
-  if (K > 1024)             \
+  if (K > 1024) {           \
     NOS_GEMV_Q8_KU(m, 3);   \
-  else                      \
-    NOS_GEMV_Q8_KU(m, 1)
+  } else {                  \
+    NOS_GEMV_Q8_KU(m, 1);   \
+  }
   switch (M) {
     case 1: NOS_GEMV_Q8(1); break;
     case 2: NOS_GEMV_Q8(2); break;
@@ -1986,6 +2214,105 @@ NOS_API int nos_gemv_q8_partials(const float* ws, long long ws_n, int NS, int R,
   pt.Hkv = Hkv;
   pt.D = D;
   return gemv_q8_launch(nullptr, K, wq, ldw, wscale, nullptr, bias, res, ldr, y, ldy, M, N, K, epi, 0.f, pt, stream);
+}
+
+// The LoRA shrink in front of an adapted GEMV (lora_shrink_kernel): t [M, R] fp32 (contiguous) from x
+// [M, K] fp32 -- or, with ws, from the decode partials (as nos_gemv_partials; x is then unused, rps 1
+// and no RMSNorm) -- and A [n, R, K] fp32 (adapter stride bsa, row stride lda, 16-byte rows).  M <= 8,
+// 4 <= R <= 64 with R % 4 == 0, K % 4 == 0, M x K x 4 <= 64 KiB (the GEMV's own bound); gamma (or
+// null) only with rms_eps > 0.  sel holds at least ceil(M / rps) ids.
+NOS_API int nos_lora_shrink(const float* x, int ldx, const float* ws, long long ws_n, int NS, int G, int Hkv, int D,
+                            const float* A, long long bsa, int lda, const int* sel, int n, int rps, const float* gamma,
+                            float rms_eps, float* t, int M, int R, int K, hipStream_t stream) {
+  if (!A || !sel || !t || M <= 0 || M > 8 || R < 4 || R > LORA_MAX_R || (R % 4) || K <= 0 || (K % 4) || n < 1 ||
+      rps < 1 || lda < K || (lda % 4) || bsa < (long long)(R - 1) * lda + K || (bsa % 4) || ((uintptr_t)A & 15) ||
+      ((uintptr_t)t & 15) || (long long)M * K * 4 > 65536 || (gamma && (!(rms_eps > 0.f) || ((uintptr_t)gamma & 15))))
+    return (int)hipErrorInvalidValue;
+  Parts pt;
+  if (ws != nullptr) {
+    if (!parts_ok(ws, ws_n, NS, G, G, Hkv, D, M, K) || rps != 1 || rms_eps > 0.f) return (int)hipErrorInvalidValue;
+    pt.ws = ws;
+    pt.NS = NS;
+    pt.R = G;
+    pt.G = G;
+    pt.Hkv = Hkv;
+    pt.D = D;
+    ldx = K;
+  } else if (!x || ldx < K || (ldx % 4) || ((uintptr_t)x & 15)) {
+    return (int)hipErrorInvalidValue;
+  }
+  hipLaunchKernelGGL(lora_shrink_kernel, dim3((unsigned)(M * (R / 4))), dim3(256), 0, stream, x, ldx, A, bsa, lda,
+                     sel, n, rps, gamma, rms_eps, t, M, R, K, pt);
+  return (int)hipGetLastError();
+}
+
+// nos_gemv / nos_gemv_partials (ws != null: x is unused) of fp32 x and W with the adapter epilogue
+// (Lora): y gets + sum_j B[sel[m / rps] - 1][n][j] t[m][j] before bias, activation, GLU or residual.
+NOS_API int nos_gemv_lora(const float* x, int ldx, const float* ws, long long ws_n, int NS, int G, int Hkv, int D,
+                          const float* w, int ldw, const float* bias, const float* res, int ldr, float* y, int ldy,
+                          int M, int N, int K, int epi, float rms_eps, const float* t, const float* B, long long bsb,
+                          int ldb, const int* sel, int R, int n, int rps, hipStream_t stream) {
+  Lora lo;
+  lo.t = t;
+  lo.B = B;
+  lo.sel = sel;
+  lo.bsb = bsb;
+  lo.ldb = ldb;
+  lo.R = R;
+  lo.n = n;
+  lo.rps = rps;
+  if (!w || !y || M <= 0 || M > 8 || N <= 0 || K <= 0 || (K % 4) || ldw < K || (ldw % 4) || ((uintptr_t)w & 15) ||
+      ldy < ((epi & EPI_GLU) ? N / 2 : N) || (long long)M * K * 4 > 65536 || ((epi & EPI_BIAS) && !bias) ||
+      ((epi & EPI_RESID) && (!res || ldr < N)) || !lora_ok(lo, M, N))
+    return (int)hipErrorInvalidValue;
+  if ((epi & EPI_GLU) && ((N % 2) || (epi & (EPI_RESID | EPI_GELU | EPI_RELU | EPI_SILU)))) return (int)hipErrorInvalidValue;
+  Parts pt;
+  if (ws != nullptr) {
+    if (!parts_ok(ws, ws_n, NS, G, G, Hkv, D, M, K) || (epi & EPI_GLU) || rps != 1 || rms_eps > 0.f)
+      return (int)hipErrorInvalidValue;
+    pt.ws = ws;
+    pt.NS = NS;
+    pt.R = G;
+    pt.G = G;
+    pt.Hkv = Hkv;
+    pt.D = D;
+    return gemv_launch(nullptr, 0, K, w, 0, ldw, bias, res, ldr, y, ldy, M, N, K, epi, 0.f, pt, stream, &lo);
+  }
+  if (!x || ldx < K || (ldx % 4) || ((uintptr_t)x & 15)) return (int)hipErrorInvalidValue;
+  return gemv_launch(x, 0, ldx, w, 0, ldw, bias, res, ldr, y, ldy, M, N, K, epi, rms_eps, pt, stream, &lo);
+}
+
+// nos_gemv_q8 / nos_gemv_q8_partials (ws != null: x is unused) with the adapter epilogue, as nos_gemv_lora
+NOS_API int nos_gemv_q8_lora(const float* x, int ldx, const float* ws, long long ws_n, int NS, int G, int Hkv, int D,
+                             const void* wq, int ldw, const float* wscale, const float* gamma, const float* bias,
+                             const float* res, int ldr, float* y, int ldy, int M, int N, int K, int epi, float rms_eps,
+                             const float* t, const float* B, long long bsb, int ldb, const int* sel, int R, int n,
+                             int rps, hipStream_t stream) {
+  Lora lo;
+  lo.t = t;
+  lo.B = B;
+  lo.sel = sel;
+  lo.bsb = bsb;
+  lo.ldb = ldb;
+  lo.R = R;
+  lo.n = n;
+  lo.rps = rps;
+  if (M <= 0 || M > 8 || N <= 0 || !lora_ok(lo, M, N)) return (int)hipErrorInvalidValue;
+  Parts pt;
+  if (ws != nullptr) {
+    if (!parts_ok(ws, ws_n, NS, G, G, Hkv, D, M, K) || (epi & EPI_GLU) || rps != 1 || rms_eps > 0.f || gamma)
+      return (int)hipErrorInvalidValue;
+    pt.ws = ws;
+    pt.NS = NS;
+    pt.R = G;
+    pt.G = G;
+    pt.Hkv = Hkv;
+    pt.D = D;
+    return gemv_q8_launch(nullptr, K, wq, ldw, wscale, nullptr, bias, res, ldr, y, ldy, M, N, K, epi, 0.f, pt, stream,
+                          &lo);
+  }
+  if (!x || ldx < K || (ldx % 4) || ((uintptr_t)x & 15)) return (int)hipErrorInvalidValue;
+  return gemv_q8_launch(x, ldx, wq, ldw, wscale, gamma, bias, res, ldr, y, ldy, M, N, K, epi, rms_eps, pt, stream, &lo);
 }
 
 // out [N, K] fp32 (row stride ldo) = (float)q [N, K] int8 * wscale [N], bit-exact: the weight of an

@@ -110,10 +110,76 @@ def llama_program(model, seq: int, batch: int = 1, dtype: str = "fp32",
     return b.build([logits])
 
 
+# the projections an adapter may target, grouped by the activation they read: a group's adapters are
+# stacked into ONE lora node (its A rows [A_q; A_k; A_v], its B block-structured over the merged columns)
+_LORA_GROUPS = (("self_attn.qkv_proj", ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj")),
+                ("self_attn.o_proj", ("self_attn.o_proj",)),
+                ("mlp.gate_up_proj", ("mlp.gate_proj", "mlp.up_proj")),
+                ("mlp.down_proj", ("mlp.down_proj",)))
+LORA_MAX_RANK = 64   # the stacked rank of one activation (ops.tenant.LORA_MAX_RANK)
+
+
+def _stack_adapters(adapters, model) -> dict:
+    """``adapters`` (a list of {module name: (A [r, in], B [out, r], scale)}) checked and stacked per
+    adapted activation: {``model.layers.i.<group>``: (A [n, R, in], B [n, N, R], member modules)} with
+    N the merged projections' output columns, R = r x (targeted members), ``scale`` folded into B and
+    zero blocks where a member is not targeted or a column belongs to another member."""
+    cfg = model.config
+    if not isinstance(adapters, (list, tuple)) or not adapters or not all(isinstance(a, dict) and a for a in adapters):
+        raise ValueError("adapters must be a non-empty list of {module name: (A, B, scale)} dicts")
+    sd = model.state_dict()
+    valid = {f"model.layers.{i}.{m}" for i in range(cfg.num_hidden_layers) for _, ms in _LORA_GROUPS for m in ms}
+    targets = set(adapters[0])
+    rank = None
+    for k, ad in enumerate(adapters):
+        unknown = sorted(set(ad) - valid)
+        if unknown:
+            raise ValueError(f"adapters[{k}]: unknown module name {unknown[0]!r}; an adapter targets "
+                             f"model.layers.<i>.self_attn.{{q,k,v,o}}_proj and model.layers.<i>.mlp.{{gate,up,down}}_proj")
+        if set(ad) != targets:
+            raise ValueError(f"adapters[{k}] targets other modules than adapters[0]: all adapters of one tenant share "
+                             f"one target set (differing: {sorted(set(ad) ^ targets)[:4]})")
+        for name, (A, B, _scale) in ad.items():
+            w = sd[name + ".weight"]
+            A, B = np.asarray(A), np.asarray(B)
+            if A.ndim != 2 or B.ndim != 2 or A.shape[1] != w.shape[1] or B.shape[0] != w.shape[0] or B.shape[1] != A.shape[0]:
+                raise ValueError(f"adapters[{k}][{name!r}]: A [r, {w.shape[1]}] and B [{w.shape[0]}, r] required, got "
+                                 f"{A.shape} and {B.shape}")
+            if rank not in (None, A.shape[0]):
+                raise ValueError(f"adapters[{k}][{name!r}] has rank {A.shape[0]}, others {rank}: all adapters of one "
+                                 f"tenant share one rank")
+            rank = A.shape[0]
+    out = {}
+    for i in range(cfg.num_hidden_layers):
+        for group, members in _LORA_GROUPS:
+            hit = [m for m in members if f"model.layers.{i}.{m}" in targets]
+            if not hit:
+                continue
+            R = rank * len(hit)
+            if R > LORA_MAX_RANK or R % 4:
+                raise ValueError(f"model.layers.{i}.{group}: the stacked rank R = {rank} x {len(hit)} = {R} must be a "
+                                 f"multiple of 4 and at most {LORA_MAX_RANK} (the adapters of the projections that read "
+                                 f"one activation are stacked)")
+            widths = [sd[f"model.layers.{i}.{m}.weight"].shape[0] for m in members]
+            K = sd[f"model.layers.{i}.{members[0]}.weight"].shape[1]
+            As = np.zeros((len(adapters), R, K), np.float32)
+            Bs = np.zeros((len(adapters), sum(widths), R), np.float32)
+            for k, ad in enumerate(adapters):
+                for j, m in enumerate(hit):
+                    A, B, scale = ad[f"model.layers.{i}.{m}"]
+                    row = sum(widths[:members.index(m)])
+                    As[k, j * rank:(j + 1) * rank] = np.asarray(A, np.float32)
+                    Bs[k, row:row + widths[members.index(m)], j * rank:(j + 1) * rank] = \
+                        np.float32(scale) * np.asarray(B, np.float32)
+            out[f"model.layers.{i}.{group}"] = (As, Bs, members)
+    return out
+
+
 def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, dtype: str = "fp32",
                           extend: tuple[int, ...] = (), sampling: bool = False,
                           weights: str = "fp32", kv: str | None = None,
-                          stopping: bool = False, speculate: int | None = None) -> tuple[list[dict], bytes]:
+                          stopping: bool = False, speculate: int | None = None,
+                          adapters: list | None = None) -> tuple[list[dict], bytes]:
     """A STATEFUL generation tenant: ``[prefill, decode, *extends]`` programs
     over one weight payload and one state -- per layer a K and a V cache
     ``[batch, max_len, kv_heads, head_dim]`` plus the position counter
@@ -201,8 +267,27 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     also fit the int8 GEMV's staging (``batch * K * widest in-features * 4 <=
     GEMV_X_BYTES``), so that no linear dequantizes a transient weight; an fp32
     tenant past that bound is built, and that linear runs on the fp32 GEMM
-    instead of the GEMV (slower: docs/tenant_programs.md)."""
+    instead of the GEMV (slower: docs/tenant_programs.md).
+
+    ``adapters`` (fp32 tenants; with every option above): N LoRA fine-tunes of
+    the model as ONE tenant -- the base weights once, and per adapter a dict
+    from module name (``model.layers.{i}.self_attn.q_proj``, ..., ``mlp.down_proj``:
+    any subset of q k v o gate up down, the same for every adapter, at one
+    rank) to ``(A [r, in], B [out, r], scale)``.  The programs also declare the
+    control state ``adapter`` (i32 [batch], filled by the server from each
+    request's ``"adapter"`` field: the adapter of each sequence, 1 .. N; 0: the
+    base model) and hold ``add(linear(x, W), lora(x, A, B, adapter))`` for
+    every adapted activation -- q / k / v (and gate / up) as one merged linear
+    with one stacked A ``[A_q; A_k; A_v]`` and a B block-structured over the
+    merged columns (``scale`` folded in, zero blocks stored), the stacked rank
+    at most 64 and a multiple of 4.  :func:`adapted_llama` is the model such a
+    tenant computes for one adapter.  Adapters are fixed at registration."""
     from ..ops.tenant import GEMV_MAX_ROWS, GEMV_X_BYTES
+
+    if adapters is not None and dtype != "fp32":
+        raise ValueError("adapters are an fp32 tenant's (fp32 A and B beside fp32 or int8 weights): dtype must be 'fp32', "
+                         "dtype='bf16' is not taken")
+    stacked = _stack_adapters(adapters, model) if adapters is not None else {}
 
     if speculate is not None:
         if not isinstance(speculate, int) or isinstance(speculate, bool) or not 2 <= speculate <= 8:
@@ -250,7 +335,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     payload = b""
     for seq, reset, verify in chunks:
         b = Builder(f"llama-h{d}-l{cfg.num_hidden_layers}-{dtype}{'-q8' if q8 else ''}{'-kvq8' if kvq8 else ''}-"
-                    f"{'stop-' if stopping else ''}{'spec-' if speculate else ''}"
+                    f"{'stop-' if stopping else ''}{'spec-' if speculate else ''}{'lora-' if stacked else ''}"
                     f"{'prefill' if reset else 'verify' if verify else 'step'}{seq}")
         ids = b.input("input_ids", [batch, seq], "i32")
         P = lambda k: b.param(k, sd[k], dtype)  # noqa: E731
@@ -264,8 +349,24 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
             wq, sc = b.param_q8(name, np.concatenate([sd[k] for k in keys or (name,)], axis=0))
             return b.op("linear_q8", x, wq, sc, out=out)
 
+        def adapted(y, x, group):
+            """y (the group's merged linear of x) plus its adapters' delta, where the group has any."""
+            if group not in stacked:
+                return y
+            As, Bs, _ = stacked[group]
+            return b.op("add", y, b.op("lora", x, b.param(group + ".lora_A", As), b.param(group + ".lora_B", Bs), sel))
+
+        def merged(x, group):
+            """An adapted group's projections as ONE linear over the members' rows (the arrangement int8
+            weights use): merging and adapters commute, so the delta is added to the merged output."""
+            keys = [group.rsplit(".", 2)[0] + "." + m + ".weight" for m in stacked[group][2]]
+            if q8 or len(keys) == 1:
+                return lin(x, group + ".weight" if len(keys) > 1 else keys[0], *(keys if len(keys) > 1 else ()))
+            return b.op("linear", x, b.param(group + ".weight", np.concatenate([sd[k] for k in keys], axis=0), dtype))
+
         rc, rs = b.param("rope.cos", cos, "fp32"), b.param("rope.sin", sin, "fp32")
         b.state("pos", [batch], "i32")
+        sel = b.adapter_state(batch) if stacked else None
         ctl = b.state("sampling", [4], "i32") if sampling else None
         done, seen, sctl = b.stopping_states(batch, cfg.vocab_size) if stopping else (None, None, None)
         hist, spec_ctl = b.speculate_states(batch, max_len) if speculate else (None, None)
@@ -281,8 +382,11 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
         for i in range(cfg.num_hidden_layers):
             pf = f"model.layers.{i}."
             y = b.op("rmsnorm", h, P(pf + "input_layernorm.weight"), eps=eps)
-            if q8:
-                qkv = lin(y, pf + "self_attn.qkv_proj.weight", *(pf + f"self_attn.{t}_proj.weight" for t in "qkv"))
+            if q8 or pf + "self_attn.qkv_proj" in stacked:
+                if pf + "self_attn.qkv_proj" in stacked:
+                    qkv = adapted(merged(y, pf + "self_attn.qkv_proj"), y, pf + "self_attn.qkv_proj")
+                else:
+                    qkv = lin(y, pf + "self_attn.qkv_proj.weight", *(pf + f"self_attn.{t}_proj.weight" for t in "qkv"))
                 ends = (0, nh * hd, (nh + nkv) * hd, (nh + 2 * nkv) * hd)
                 proj = lambda t: b.op("slice", qkv, dim=-1, start=ends[t], end=ends[t + 1])  # noqa: E731
             else:
@@ -295,17 +399,21 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
             kc = b.op("kv_write", kc0, k, p, *ks)
             vc = b.op("kv_write", vc0, v, p, *vs)
             o = b.op("reshape", b.op("sdpa_cache", q, kc, vc, p, *ks, *vs), shape=[batch, seq, nh * hd])
-            h = b.op("add", lin(o, pf + "self_attn.o_proj.weight"), h)
+            h = b.op("add", adapted(lin(o, pf + "self_attn.o_proj.weight"), o, pf + "self_attn.o_proj"), h)
             y = b.op("rmsnorm", h, P(pf + "post_attention_layernorm.weight"), eps=eps)
-            if q8:
-                gu = lin(y, pf + "mlp.gate_up_proj.weight", pf + "mlp.gate_proj.weight", pf + "mlp.up_proj.weight")
+            if q8 or pf + "mlp.gate_up_proj" in stacked:
+                if pf + "mlp.gate_up_proj" in stacked:
+                    gu = adapted(merged(y, pf + "mlp.gate_up_proj"), y, pf + "mlp.gate_up_proj")
+                else:
+                    gu = lin(y, pf + "mlp.gate_up_proj.weight", pf + "mlp.gate_proj.weight", pf + "mlp.up_proj.weight")
                 inter = sd[pf + "mlp.gate_proj.weight"].shape[0]
                 g = b.op("slice", gu, dim=-1, start=0, end=inter)
                 u = b.op("slice", gu, dim=-1, start=inter, end=2 * inter)
             else:
                 g = b.op("linear", y, P(pf + "mlp.gate_proj.weight"))
                 u = b.op("linear", y, P(pf + "mlp.up_proj.weight"))
-            h = b.op("add", lin(b.op("mul", b.op("silu", g), u), pf + "mlp.down_proj.weight"), h)
+            act = b.op("mul", b.op("silu", g), u)
+            h = b.op("add", adapted(lin(act, pf + "mlp.down_proj.weight"), act, pf + "mlp.down_proj"), h)
         if seq > 1 and not verify:   # only the last token's logits: the LM head runs on one row
             h = b.op("slice", h, dim=1, start=seq - 1, end=seq)
         h = b.op("rmsnorm", h, P("model.norm.weight"), eps=eps)
@@ -369,6 +477,35 @@ def dequantized_llama(model):
     return m
 
 
+def adapted_llama(model, adapter: dict):
+    """A deep copy of the HF model whose targeted ``nn.Linear`` modules (``adapter``: {module name:
+    (A [r, in], B [out, r], scale)}) compute ``base(x) + scale * (x @ A.T) @ B.T``, unmerged and in
+    that order of operations: the model an adapter tenant computes for the sequences that select this
+    adapter (``llama_decode_programs(adapters=[...])``), for tests and users to compare against."""
+    import copy
+
+    import torch
+
+    class LoraLinear(torch.nn.Module):
+        def __init__(self, base, A, B, scale):
+            super().__init__()
+            self.base, self.scale = base, float(scale)
+            self.lora_A = torch.nn.Parameter(torch.as_tensor(np.asarray(A, np.float32)).to(base.weight.dtype), False)
+            self.lora_B = torch.nn.Parameter(torch.as_tensor(np.asarray(B, np.float32)).to(base.weight.dtype), False)
+
+        def forward(self, x):
+            return self.base(x) + self.scale * ((x @ self.lora_A.T) @ self.lora_B.T)
+
+    m = copy.deepcopy(model)
+    for name, (A, B, scale) in adapter.items():
+        parent, _, leaf = name.rpartition(".")
+        base = m.get_submodule(name)
+        if not isinstance(base, torch.nn.Linear):
+            raise ValueError(f"adapted_llama: {name!r} is no nn.Linear of the model")
+        setattr(m.get_submodule(parent), leaf, LoraLinear(base, A, B, scale))
+    return m.eval()
+
+
 def kv_q8_roundtrip_cache():
     """A ``transformers`` cache for ``model(..., past_key_values=...)`` whose
     ``update()`` replaces the incoming K (already rotated) and V by
@@ -400,4 +537,4 @@ def llama_tenant(dtype: str = "fp32", seed: int = 0, small: bool = True, seq: in
 
 
 __all__ = ["llama_config", "llama_model", "llama_program", "llama_decode_programs", "llama_tenant", "rope_tables",
-           "dequantized_llama", "kv_q8_roundtrip_cache"]
+           "dequantized_llama", "kv_q8_roundtrip_cache", "adapted_llama"]

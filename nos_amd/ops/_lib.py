@@ -139,6 +139,15 @@ _SIGS = {
     "nos_gemv_q8_partials": [c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                              c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "nos_dequant_q8": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    # decode.hip: multi-adapter LoRA (the shrink launch, the GEMVs with the adapter epilogue)
+    "nos_lora_shrink": [c_void_p, c_int, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_void_p, c_ll, c_int, c_void_p,
+                        c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p],
+    "nos_gemv_lora": [c_void_p, c_int, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                      c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_ll, c_int,
+                      c_void_p, c_int, c_int, c_int, c_void_p],
+    "nos_gemv_q8_lora": [c_void_p, c_int, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                         c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                         c_void_p, c_void_p, c_ll, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
     "nos_attn_h3g_workspace": [c_int, c_int, c_int, c_int, c_int, c_int],
     # LayerNorm hand-off (gemm_f32h.hip): producer row statistics, LN in the consumer's A load
     "nos_gemm_f32h3_stats": [c_void_p, c_int, c_ll, c_void_p, c_float, c_void_p, c_int, c_ll, c_void_p, c_void_p,

@@ -511,11 +511,21 @@ def _pad_k_len(k: int) -> int:
 
 
 def linear_rms(x: torch.Tensor, wg: torch.Tensor, bias: torch.Tensor | None = None, act: str | None = None,
-               eps: float = 1e-6, glu: bool = False) -> torch.Tensor:
+               eps: float = 1e-6, glu: bool = False, lora: tuple | None = None) -> torch.Tensor:
     """act(RMSNorm(x) @ (W * gamma)^T + b): the row statistics in the h3 split
     pre-pass (``nos_split_rows_h3`` mode 2), gamma folded into ``wg``.
     ``glu``: ``wg`` is a merged [gate; up] weight and the result is
-    silu(gate) * up (the GEMV's epilogue for decode rows)."""
+    silu(gate) * up (the GEMV's epilogue for decode rows).  ``lora``: the
+    adapter operand of :func:`gemv` -- decode rows on the GEMV only (an error otherwise)."""
+    if lora is not None:
+        x2l = x.reshape(-1, x.shape[-1])
+        if x2l.stride(-1) != 1 or x2l.stride(0) % 4 or x2l.data_ptr() % 16:
+            x2l = x2l.contiguous()
+        if not gemv_ok(x2l, wg) or x2l.dtype != torch.float32:
+            raise ValueError(f"linear_rms: the adapter epilogue exists on the GEMV only; x {tuple(x.shape)} {x.dtype} and "
+                             f"W {tuple(wg.shape)} are not a product it takes (gemv_ok)")
+        out = gemv(x2l, wg, bias, act, rms_eps=float(eps) or 1e-30, glu=glu, lora=lora)
+        return out.view(*x.shape[:-1], wg.shape[0] // 2 if glu else wg.shape[0])
     if glu:
         x2g = _f32(x).reshape(-1, x.shape[-1])
         if not (x.is_cuda and x2g.shape[0] <= GEMV_MAX_ROWS and gemv_ok(x2g.contiguous(), wg)):
@@ -1429,6 +1439,107 @@ EPI_SILU = 64 # csrc/hip/epilogue.h; decode.hip's GEMV: SiLU epilogue
 EPI_GLU = 256  # decode.hip's GEMV: W = [gate; up], y = silu(gate) * up
 
 
+# ------------------------------------------------------------------ multi-adapter LoRA
+LORA_MAX_RANK = 64   # the stacked rank R of one adapted activation (decode.hip LORA_MAX_R)
+
+
+def _lora_rows(sel: torch.Tensor, n: int, M: int, rps: int):
+    """Per row m of M: (a valid adapter?, its index a - 1 clamped) for a = sel[m // rps]; no host read."""
+    a = sel.to(torch.long).repeat_interleave(int(rps))[:M]
+    return (a >= 1) & (a <= n), (a - 1).clamp(0, n - 1)
+
+
+def lora_ref(x, A, B, sel, dtype: torch.dtype | None = None):
+    """What ``lora(x, A, B, sel)`` means: for sequence b of x [batch, S, K] with a = ``sel[b]``,
+    ``(x[b] @ A[a - 1].T) @ B[a - 1].T`` when a lies in [1, n] and zeros otherwise (0: the base
+    model); A [n, R, K], B [n, N, R].  In ``dtype`` arithmetic (default: x's); the adapter is chosen
+    by ``index_select`` on ``sel``, never read on the host."""
+    dt = dtype or x.dtype
+    n = A.shape[0]
+    ok, idx = _lora_rows(sel, n, x.shape[0], 1)
+    rows = []
+    for b in range(x.shape[0]):
+        Ab = A.index_select(0, idx[b:b + 1])[0].to(dt)
+        Bb = B.index_select(0, idx[b:b + 1])[0].to(dt)
+        rows.append((x[b].to(dt) @ Ab.T) @ Bb.T)
+    y = torch.stack(rows)
+    return torch.where(ok.view(-1, 1, 1), y, torch.zeros_like(y))
+
+
+def lora_shrink_ref(x2, A, sel, rows_per_seq: int = 1, rms_eps: float = 0.0, gamma=None,
+                    dtype: torch.dtype = torch.float32):
+    """:func:`lora_shrink` in ``dtype`` arithmetic: t [M, R], row m = A[a_m - 1] @ x'[m] with
+    ``a_m = sel[m // rows_per_seq]`` (zeros for an a_m outside [1, n]) and x' = x, RMS-normalised and
+    times ``gamma`` when ``rms_eps`` > 0."""
+    xf = x2.to(dtype)
+    if rms_eps:
+        xf = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + rms_eps)
+        if gamma is not None:
+            xf = xf * gamma.to(dtype)
+    ok, idx = _lora_rows(sel, A.shape[0], xf.shape[0], rows_per_seq)
+    t = torch.bmm(A.index_select(0, idx).to(dtype), xf.unsqueeze(-1)).squeeze(-1)
+    return torch.where(ok.view(-1, 1), t, torch.zeros_like(t))
+
+
+def lora_expand_ref(t, B, sel, rows_per_seq: int = 1, dtype: torch.dtype = torch.float32):
+    """The adapter epilogue's delta [M, N]: row m = B[a_m - 1] @ t[m], zeros for a base row."""
+    ok, idx = _lora_rows(sel, B.shape[0], t.shape[0], rows_per_seq)
+    d = torch.bmm(B.index_select(0, idx).to(dtype), t.to(dtype).unsqueeze(-1)).squeeze(-1)
+    return torch.where(ok.view(-1, 1), d, torch.zeros_like(d))
+
+
+def _parts_args(p: "DecodePartials | None") -> tuple:
+    return (None, 0, 0, 0, 0, 0) if p is None else (p.ws.data_ptr(), p.ws.numel(), p.NS, p.G, p.Hkv, p.D)
+
+
+def lora_shrink(x, A: torch.Tensor, sel: torch.Tensor, rows_per_seq: int = 1, rms_eps: float = 0.0,
+                gamma: torch.Tensor | None = None) -> torch.Tensor:
+    """t [M, R] fp32 of the GEMV that follows: ``t[m] = A[sel[m // rows_per_seq] - 1] @ x'[m]`` for x [M, K]
+    fp32 (M <= 8; a :class:`DecodePartials`: the decode attention's output, combined as that GEMV
+    combines it) and A [n, R, K] fp32 -- one launch per adapted activation (decode.hip
+    ``nos_lora_shrink``); x' is x under the GEMV's RMSNorm prologue (``rms_eps`` > 0, ``gamma``).
+    Rows whose adapter is outside [1, n] are zeros.  CPU tensors: :func:`lora_shrink_ref`."""
+    parts = x if isinstance(x, DecodePartials) else None
+    n, R, K = A.shape
+    if parts is None and not x.is_cuda:
+        return lora_shrink_ref(x.reshape(-1, K), A, sel, rows_per_seq, rms_eps, gamma)
+    if parts is not None:
+        M = parts.shape[0]
+        if parts.shape[2] * parts.shape[3] != K:
+            raise ValueError(f"lora_shrink: A {tuple(A.shape)} for partials of {parts.shape}")
+        x2 = None
+    else:
+        x2 = x.reshape(-1, K)
+        if x2.stride(-1) != 1 or x2.stride(0) % 4 or x2.data_ptr() % 16:
+            x2 = x2.contiguous()
+        M = x2.shape[0]
+        if x2.dtype != torch.float32:
+            raise ValueError(f"lora_shrink takes an fp32 x, got {x2.dtype}")
+    if (A.dtype != torch.float32 or A.stride(-1) != 1 or sel.dtype != torch.int32 or not sel.is_contiguous()
+            or sel.numel() * int(rows_per_seq) < M or M > GEMV_MAX_ROWS or R % 4 or not 4 <= R <= LORA_MAX_RANK):
+        raise ValueError(f"lora_shrink: A {tuple(A.shape)} {A.dtype} (fp32 [n, R <= {LORA_MAX_RANK}, K], R % 4 == 0), "
+                         f"sel {tuple(sel.shape)} {sel.dtype} (i32, an id per {rows_per_seq} of the {M} <= "
+                         f"{GEMV_MAX_ROWS} rows)")
+    g = None if gamma is None else gamma.float().contiguous()
+    t = torch.empty((M, R), dtype=torch.float32, device=A.device)
+    _lib.check(_lib.lib().nos_lora_shrink(_ptr(x2), x2.stride(0) if x2 is not None else K, *_parts_args(parts),
+                                          A.data_ptr(), A.stride(0), A.stride(1), sel.data_ptr(), n, int(rows_per_seq),
+                                          _ptr(g), float(rms_eps), t.data_ptr(), M, R, K, _stream()), "nos_lora_shrink")
+    return t
+
+
+def _lora_args(lora: tuple, M: int, N: int) -> tuple:
+    """The adapter operand ``(t [M, R], B [n, N, R], sel, rows_per_seq)`` of a GEMV as the entry points take it."""
+    t, B, sel, rps = lora
+    if (t.dtype != torch.float32 or B.dtype != torch.float32 or sel.dtype != torch.int32 or B.dim() != 3
+            or B.shape[1] != N or tuple(t.shape) != (M, B.shape[2]) or not t.is_contiguous() or B.stride(-1) != 1
+            or not sel.is_contiguous() or sel.numel() * int(rps) < M):
+        raise ValueError(f"lora: t {tuple(t.shape)} {t.dtype}, B {tuple(B.shape)} {B.dtype} and sel {tuple(sel.shape)} "
+                         f"{sel.dtype} are not the adapter operand of a [{M}, {N}] GEMV (t [M, R] and B [n, N, R] "
+                         f"fp32, sel i32 with an id per {rps} rows)")
+    return (t.data_ptr(), B.data_ptr(), B.stride(0), B.stride(1), sel.data_ptr(), B.shape[2], B.shape[0], int(rps))
+
+
 def gemv_ok(x2: torch.Tensor, w: torch.Tensor) -> bool:
     """Whether the skinny-GEMM kernel takes this [M, K] x [N, K] product."""
     M, K = x2.shape
@@ -1440,11 +1551,14 @@ def gemv_ok(x2: torch.Tensor, w: torch.Tensor) -> bool:
 
 def gemv(x2: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, act: str | None = None,
          residual: torch.Tensor | None = None, out: torch.Tensor | None = None, rms_eps: float = 0.0,
-         glu: bool = False) -> torch.Tensor:
+         glu: bool = False, lora: tuple | None = None) -> torch.Tensor:
     """y [M, N] = act(rms(x) [M, K] W^T + b) + R for M <= 8 (:func:`gemv_ok`):
     the weight-streaming kernel of a decode step, exact fp32 math; y, R in
     x's dtype, bias in W's.  ``rms_eps`` > 0: x rows RMS-normalised first
-    (RMSNorm folded into the GEMM, gamma in W)."""
+    (RMSNorm folded into the GEMM, gamma in W).  ``lora`` = (t, B, sel,
+    rows_per_seq), fp32 x and W: the product gets ``+ B[sel[m // rows_per_seq]
+    - 1] @ t[m]`` before anything else of the epilogue (t: :func:`lora_shrink`;
+    a row whose adapter is 0 is the plain call's bit for bit)."""
     M, K = x2.shape
     N = w.shape[0]
     y = out if out is not None else torch.empty((M, N // 2 if glu else N), dtype=x2.dtype, device=x2.device)
@@ -1456,14 +1570,49 @@ def gemv(x2: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, ac
         r = r.contiguous()
     if y.dtype != x2.dtype or y.stride(-1) != 1:
         raise ValueError("gemv: out must be x's dtype with unit inner stride")
+    if lora is not None:
+        if x2.dtype != torch.float32 or w.dtype != torch.float32:
+            raise ValueError("gemv: the adapter epilogue takes fp32 x and W")
+        _lib.check(_lib.lib().nos_gemv_lora(x2.data_ptr(), x2.stride(0), *_parts_args(None), w.data_ptr(), w.stride(0),
+                                            _ptr(b), _ptr(r), r.stride(0) if r is not None else 0, y.data_ptr(),
+                                            y.stride(0), M, N, K, epi, float(rms_eps), *_lora_args(lora, M, N),
+                                            _stream()), "nos_gemv_lora")
+        return y
     _lib.check(_lib.lib().nos_gemv(x2.data_ptr(), _bf(x2), x2.stride(0), w.data_ptr(), _bf(w), w.stride(0), _ptr(b),
                                    _ptr(r), r.stride(0) if r is not None else 0, y.data_ptr(), y.stride(0), M, N, K,
                                    epi, float(rms_eps), _stream()), "nos_gemv")
     return y
 
 
+def linear_lora(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, act: str | None = None,
+                residual: torch.Tensor | None = None, lora: tuple | None = None) -> torch.Tensor:
+    """act(x @ W^T + B[sel] @ t + b) + R for fp32 decode rows x [..., K]: :func:`gemv` with the adapter
+    epilogue.  Rows the GEMV does not take are an error (the adapter epilogue exists nowhere else)."""
+    K, N = x.shape[-1], w.shape[0]
+    x2 = x.reshape(-1, K)
+    if x2.stride(-1) != 1 or x2.stride(0) % 4 or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    if not gemv_ok(x2, w) or x2.dtype != torch.float32 or w.dtype != torch.float32:
+        raise ValueError(f"linear_lora: x {tuple(x.shape)} {x.dtype} and W {tuple(w.shape)} {w.dtype} are not a product "
+                         f"the fp32 GEMV takes (gemv_ok)")
+    return gemv(x2, w, bias, act, residual, lora=lora).view(*x.shape[:-1], N)
+
+
+def lora(x: torch.Tensor, A: torch.Tensor, B: torch.Tensor, sel: torch.Tensor) -> torch.Tensor:
+    """``lora(x, A, B, sel)`` (:func:`lora_ref`) of fp32 x [batch, S, K] on the device, for steps of more
+    rows than the GEMVs take (a prefill): each sequence's A and B gathered by ``index_select`` on
+    ``sel``, two ``bmm`` and a mask for the base rows -- stream-ordered, no host read of ``sel``.  CPU
+    tensors: the reference."""
+    if not x.is_cuda:
+        return lora_ref(x, A, B, sel)
+    ok, idx = _lora_rows(sel, A.shape[0], x.shape[0], 1)
+    t = torch.bmm(x, A.index_select(0, idx).transpose(1, 2))
+    y = torch.bmm(t, B.index_select(0, idx).transpose(1, 2))
+    return y * ok.view(-1, 1, 1).to(y.dtype)
+
+
 def gemv_partials(p: DecodePartials, w: torch.Tensor, bias: torch.Tensor | None = None, act: str | None = None,
-                  residual: torch.Tensor | None = None) -> torch.Tensor:
+                  residual: torch.Tensor | None = None, lora: tuple | None = None) -> torch.Tensor:
     """:func:`gemv` whose x [B, H x D] is the decode attention's output,
     combined from its split partials in the kernel's x staging
     (decode.hip ``parts_x4``, the combine kernel's arithmetic): y [B, N] fp32."""
@@ -1479,6 +1628,13 @@ def gemv_partials(p: DecodePartials, w: torch.Tensor, bias: torch.Tensor | None 
     r = None if residual is None else residual.reshape(B, N).float()
     if r is not None and r.stride(-1) != 1:
         r = r.contiguous()
+    if lora is not None:   # the adapter epilogue (as gemv's), fp32 W
+        if w.dtype != torch.float32:
+            raise ValueError("gemv_partials: the adapter epilogue takes an fp32 W")
+        _lib.check(_lib.lib().nos_gemv_lora(None, K, *_parts_args(p), w.data_ptr(), w.stride(0), _ptr(b), _ptr(r),
+                                            r.stride(0) if r is not None else 0, y.data_ptr(), y.stride(0), B, N, K,
+                                            epi, 0.0, *_lora_args(lora, B, N), _stream()), "nos_gemv_lora")
+        return y
     _lib.check(_lib.lib().nos_gemv_partials(p.ws.data_ptr(), p.ws.numel(), p.NS, p.G, p.G, p.Hkv, D, 0, w.data_ptr(),
                                             _bf(w), w.stride(0), _ptr(b), _ptr(r), r.stride(0) if r is not None else 0,
                                             y.data_ptr(), y.stride(0), B, N, K, epi, _stream()), "nos_gemv_partials")
@@ -1492,7 +1648,7 @@ def _q8_epi(bias, act, residual, glu) -> int:
 
 
 def linear_q8_ref(x, wq, wscale, bias=None, act=None, residual=None, rms_eps: float = 0.0, gamma=None,
-                  glu: bool = False, dtype: torch.dtype = torch.float32):
+                  glu: bool = False, dtype: torch.dtype = torch.float32, lora: tuple | None = None):
     """What an int8 weight-only linear means, in ``dtype`` arithmetic:
     ``act(x' @ (wq.float() * wscale[:, None]).T + bias) + residual`` with
     ``x' = rmsnorm(x) * gamma`` when ``rms_eps`` > 0, ``silu(gate) * up`` of
@@ -1506,6 +1662,8 @@ def linear_q8_ref(x, wq, wscale, bias=None, act=None, residual=None, rms_eps: fl
         if gamma is not None:
             xf = xf * gamma.to(dtype)
     y = F.linear(xf, wf, None if bias is None else bias.to(dtype))
+    if lora is not None:   # (t, B, sel, rows_per_seq): the adapter delta joins the product before the bias
+        y = y + lora_expand_ref(lora[0], lora[1], lora[2], lora[3], dtype).reshape(y.shape)
     if glu:
         h = y.shape[-1] // 2
         y = F.silu(y[..., :h]) * y[..., h:]
@@ -1537,7 +1695,7 @@ def _q8_operands(wscale, gamma, bias, residual, M, N, K=None):
 
 def gemv_q8(x2: torch.Tensor, wq: torch.Tensor, wscale: torch.Tensor, bias: torch.Tensor | None = None,
             act: str | None = None, residual: torch.Tensor | None = None, rms_eps: float = 0.0,
-            gamma: torch.Tensor | None = None, glu: bool = False) -> torch.Tensor:
+            gamma: torch.Tensor | None = None, glu: bool = False, lora: tuple | None = None) -> torch.Tensor:
     """y [M, N] = act(x' [M, K] (wq * wscale)^T + b) + R for M <= 8
     (:func:`gemv_q8_ok`; :func:`linear_q8_ref` defines x' and ``glu``): the
     weight-streaming kernel of an int8 tenant's decode step, one byte of HBM
@@ -1549,6 +1707,13 @@ def gemv_q8(x2: torch.Tensor, wq: torch.Tensor, wscale: torch.Tensor, bias: torc
         raise ValueError(f"gemv_q8: x {tuple(x2.shape)} {x2.dtype} and W {tuple(wq.shape)} {wq.dtype} are not a "
                          f"product the int8 GEMV takes (gemv_q8_ok)")
     sc, g, b, r = _q8_operands(wscale, gamma, bias, residual, M, N, K)
+    if lora is not None:   # the adapter epilogue (as gemv's)
+        _lib.check(_lib.lib().nos_gemv_q8_lora(x2.data_ptr(), x2.stride(0), *_parts_args(None), wq.data_ptr(),
+                                               wq.stride(0), sc.data_ptr(), _ptr(g), _ptr(b), _ptr(r),
+                                               r.stride(0) if r is not None else 0, y.data_ptr(), y.stride(0), M, N, K,
+                                               _q8_epi(b, act, r, glu), float(rms_eps), *_lora_args(lora, M, N),
+                                               _stream()), "nos_gemv_q8_lora")
+        return y
     _lib.check(_lib.lib().nos_gemv_q8(x2.data_ptr(), x2.stride(0), wq.data_ptr(), wq.stride(0), sc.data_ptr(), _ptr(g),
                                       _ptr(b), _ptr(r), r.stride(0) if r is not None else 0, y.data_ptr(), y.stride(0),
                                       M, N, K, _q8_epi(b, act, r, glu), float(rms_eps), _stream()), "nos_gemv_q8")
@@ -1556,7 +1721,8 @@ def gemv_q8(x2: torch.Tensor, wq: torch.Tensor, wscale: torch.Tensor, bias: torc
 
 
 def gemv_q8_partials(p: DecodePartials, wq: torch.Tensor, wscale: torch.Tensor, bias: torch.Tensor | None = None,
-                     act: str | None = None, residual: torch.Tensor | None = None) -> torch.Tensor:
+                     act: str | None = None, residual: torch.Tensor | None = None,
+                     lora: tuple | None = None) -> torch.Tensor:
     """:func:`gemv_q8` whose x [B, H x D] is the decode attention's output,
     combined from its split partials in the kernel's x staging (as
     :func:`gemv_partials`): y [B, N] fp32."""
@@ -1568,6 +1734,12 @@ def gemv_q8_partials(p: DecodePartials, wq: torch.Tensor, wscale: torch.Tensor, 
         raise ValueError(f"gemv_q8_partials: W {tuple(wq.shape)} {wq.dtype} for x [{B}, {K}]")
     y = torch.empty((B, N), dtype=torch.float32, device=wq.device)
     sc, _, b, r = _q8_operands(wscale, None, bias, residual, B, N)
+    if lora is not None:   # the adapter epilogue (as gemv's)
+        _lib.check(_lib.lib().nos_gemv_q8_lora(None, K, *_parts_args(p), wq.data_ptr(), wq.stride(0), sc.data_ptr(), None,
+                                               _ptr(b), _ptr(r), r.stride(0) if r is not None else 0, y.data_ptr(),
+                                               y.stride(0), B, N, K, _q8_epi(b, act, r, False), 0.0,
+                                               *_lora_args(lora, B, N), _stream()), "nos_gemv_q8_lora")
+        return y
     _lib.check(_lib.lib().nos_gemv_q8_partials(p.ws.data_ptr(), p.ws.numel(), p.NS, p.G, p.G, p.Hkv, D, wq.data_ptr(),
                                                wq.stride(0), sc.data_ptr(), _ptr(b), _ptr(r),
                                                r.stride(0) if r is not None else 0, y.data_ptr(), y.stride(0), B, N, K,
@@ -1592,15 +1764,16 @@ def dequant_q8(wq: torch.Tensor, wscale: torch.Tensor) -> torch.Tensor:
 
 def linear_q8(x: torch.Tensor, wq: torch.Tensor, wscale: torch.Tensor, bias: torch.Tensor | None = None,
               act: str | None = None, residual: torch.Tensor | None = None, rms_eps: float = 0.0,
-              gamma: torch.Tensor | None = None, glu: bool = False) -> torch.Tensor:
+              gamma: torch.Tensor | None = None, glu: bool = False, lora: tuple | None = None) -> torch.Tensor:
     """The int8 weight-only linear (:func:`linear_q8_ref`) of fp32 x [..., K]:
     at most :data:`GEMV_MAX_ROWS` rows on :func:`gemv_q8`; more rows
     dequantize the weight into a transient fp32 buffer (freed with the
     call's other intermediates, never cached) for the run-time-split h3
     product, after the ``rmsnorm`` kernel when there is a prologue.  CPU
-    tensors: the reference."""
+    tensors: the reference.  ``lora``: the adapter operand of :func:`gemv` -- on the GPU for rows the
+    int8 GEMV takes only (an error otherwise)."""
     if not x.is_cuda:
-        return linear_q8_ref(x, wq, wscale, bias, act, residual, rms_eps, gamma, glu)
+        return linear_q8_ref(x, wq, wscale, bias, act, residual, rms_eps, gamma, glu, lora=lora)
     if x.dtype != torch.float32:
         raise ValueError(f"linear_q8 takes an fp32 x, got {x.dtype}")
     K, N = x.shape[-1], wq.shape[0]
@@ -1610,7 +1783,10 @@ def linear_q8(x: torch.Tensor, wq: torch.Tensor, wscale: torch.Tensor, bias: tor
     M = x2.shape[0]
     shape = (*x.shape[:-1], N // 2 if glu else N)
     if M <= GEMV_MAX_ROWS and gemv_q8_ok(x2, wq):
-        return gemv_q8(x2, wq, wscale, bias, act, residual, rms_eps, gamma, glu).view(shape)
+        return gemv_q8(x2, wq, wscale, bias, act, residual, rms_eps, gamma, glu, lora=lora).view(shape)
+    if lora is not None:
+        raise ValueError(f"linear_q8: the adapter epilogue exists on the int8 GEMV only; x {tuple(x.shape)} and W "
+                         f"{tuple(wq.shape)} are not a product it takes (gemv_q8_ok)")
     if rms_eps:
         x2 = rmsnorm(x2, gamma if gamma is not None else torch.ones(K, dtype=torch.float32, device=x.device), rms_eps)
     r = None if residual is None else residual.reshape(M, N).float().contiguous()
@@ -1638,7 +1814,8 @@ def set_attention_h3g_kvsplit(n: int) -> None:
 
 __all__ = ["glu", "kv_write", "rotary_at", "sdpa_cache", "pos_update", "argmax", "sample", "sample_row_ref",
            "sampling_ctl", "philox4x32", "gemv", "gemv_ok", "gemv_partials", "gemv_q8", "gemv_q8_ok", "gemv_q8_partials",
-           "dequant_q8", "linear_q8", "linear_q8_ref",
+           "dequant_q8", "linear_q8", "linear_q8_ref", "lora", "lora_ref", "lora_shrink", "lora_shrink_ref", "lora_expand_ref", "linear_lora",
+           "LORA_MAX_RANK",
            "DecodePartials", "conv2d", "matmul", "sdpa", "linear_rms", "embedding", "rmsnorm", "softmax", "rotary", "conv2d_ref",
            "sdpa_ref", "rope_ref", "rmsnorm_ref", "linear_rms_ref", "set_attention_h3g_kvsplit", "EPI_BIAS_ROW",
            "sdpa_lse", "sdpa_bwd", "sdpa_lse_ref", "sdpa_bwd_ref", "sdpa_bwd_workspace_bytes"]

@@ -53,6 +53,13 @@ def _connect(path: str, timeout_s: float) -> socket.socket:
             time.sleep(0.1)
 
 
+def _adapter_field(adapter) -> int | list:
+    """A request's ``"adapter"``: an int (every row) or a list of ints (the server checks the values)."""
+    if isinstance(adapter, (int, np.integer)) and not isinstance(adapter, bool):
+        return int(adapter)
+    return [int(a) if isinstance(a, np.integer) else a for a in adapter]
+
+
 def _wire(a, want: str | None, what: str) -> np.ndarray:
     """``a`` as the bytes the tenant reads: the registered program's type
     (``want``, from the register reply) decides, not the array's -- a uint8
@@ -153,7 +160,8 @@ class PodClient:
         raise PodServerGone(f"pod server did not come back within {self.reconnect_s} s: {last}")
 
     def infer(self, x: np.ndarray | None = None, outputs: bool | list = False,
-              sampling: dict | None = None, stopping: dict | None = None) -> tuple[list[np.ndarray], dict]:
+              sampling: dict | None = None, stopping: dict | None = None,
+              adapter: int | list | None = None) -> tuple[list[np.ndarray], dict]:
         """One inference on the pod's model; ``x`` replaces the resident input
         (one of the registered input shapes; without ``x`` the primary
         shape's resident input runs).  ``outputs``: return every output
@@ -164,8 +172,13 @@ class PodClient:
         request is greedy.  ``stopping``: ``{"stop_ids", "pad_id",
         "repetition_penalty"}`` (any subset) for a tenant registered with
         stopping programs; the reply's ``state`` then carries the rows'
-        ``done`` flags beside ``pos``."""
+        ``done`` flags beside ``pos``.  ``adapter``, for a tenant registered with
+        LoRA adapters (``llama_decode_programs(..., adapters=[...])``): the
+        adapter of every row (an int) or of each row (a list), 1 .. N, 0 or
+        nothing: the base model."""
         req = {"op": "infer", "outputs": outputs}
+        if adapter is not None:
+            req["adapter"] = _adapter_field(adapter)
         if sampling:
             req["sampling"] = dict(sampling)
         if stopping:
@@ -195,7 +208,7 @@ class PodClient:
                  server_loop: bool = True, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  seed: int = 0, eos_token_id: int | list | None = None, pad_token_id: int | None = None,
                  repetition_penalty: float = 1.0, speculate: bool = False,
-                 prefill_len: int | None = None) -> tuple[np.ndarray, dict]:
+                 prefill_len: int | None = None, adapter: int | list | None = None) -> tuple[np.ndarray, dict]:
         """Generation on a stateful decoder tenant
         (models/llama_program.llama_decode_programs): the prompt ids [B, P]
         go to the prefill variant, then the decode variant runs once per new
@@ -235,9 +248,14 @@ class PodClient:
         ``prefill_len`` (with ``speculate``; default: the whole prompt): only
         the prompt's first that many ids go to the prefill variant, the rest
         one decode step each -- for a prompt as long as the verify step is
-        wide, whose shape would name two variants."""
+        wide, whose shape would name two variants.
+
+        ``adapter`` (an int, or a list of one int per row), for a tenant
+        registered with LoRA adapters: it goes with every request of the
+        generation, on either path and with ``speculate``."""
         prompt = np.asarray(prompt)
         B = prompt.shape[0]
+        lora = {} if adapter is None else {"adapter": _adapter_field(adapter)}
         if speculate:
             if temperature != 0.0 or top_k or top_p != 1.0 or eos_token_id is not None or repetition_penalty != 1.0:
                 raise ValueError("generate: speculate is greedy only, without stop ids or a repetition penalty")
@@ -245,9 +263,9 @@ class PodClient:
             head = prompt.shape[1] if prefill_len is None else int(prefill_len)
             if not 0 < head <= prompt.shape[1]:
                 raise ValueError(f"generate: prefill_len must lie in [1, {prompt.shape[1]}]")
-            outs, rep = self.infer(prompt[:, :head], outputs=[1, 2])   # next_ids, spec_ids (the pending token, drafts)
+            outs, rep = self.infer(prompt[:, :head], outputs=[1, 2], **lora)   # next_ids, spec_ids (the pending token, drafts)
             for s in range(head, prompt.shape[1]):   # the drafts after single steps: the pending token repeated
-                o, rep = self.infer(prompt[:, s:s + 1], outputs=[1])
+                o, rep = self.infer(prompt[:, s:s + 1], outputs=[1], **lora)
                 outs = [o[0], np.repeat(o[0].reshape(B, 1), outs[1].reshape(B, -1).shape[1], axis=1)]
             t1 = time.monotonic()
             if max_new_tokens <= 1:
@@ -255,7 +273,7 @@ class PodClient:
                                                                 "state": rep.get("state"), "n_acc": np.zeros((0, B), np.int32)}
             s0 = time.monotonic()
             toks, acc, rep = self.speculate_loop(outs[1].reshape(B, -1).astype(np.int32), max_new_tokens - 1,
-                                                 prompt.shape[1] + max_new_tokens - 1)
+                                                 prompt.shape[1] + max_new_tokens - 1, adapter=adapter)
             dt = time.monotonic() - s0
             run = int(rep["steps_run"])
             return toks, {"prefill_s": t1 - t0, "step_s": [dt / run] * run, "state": rep.get("state"),
@@ -271,7 +289,7 @@ class PodClient:
             stopping["pad_id"] = int(pad_token_id) if isinstance(pad_token_id, np.integer) else pad_token_id
         if repetition_penalty != 1.0:
             stopping["repetition_penalty"] = repetition_penalty
-        extra = {**({"sampling": sampling} if sampling else {}), **({"stopping": stopping} if stopping else {})}
+        extra = {**({"sampling": sampling} if sampling else {}), **({"stopping": stopping} if stopping else {}), **lora}
 
         def ended(rep) -> bool:
             done = (rep.get("state") or {}).get("done")
@@ -309,7 +327,8 @@ class PodClient:
         return np.stack(toks, axis=1), {"prefill_s": t1 - t0, "step_s": steps, "state": rep.get("state"),
                                         "steps_run": run}
 
-    def speculate_loop(self, ids: np.ndarray, steps: int, end: int) -> tuple[np.ndarray, np.ndarray, dict]:
+    def speculate_loop(self, ids: np.ndarray, steps: int, end: int,
+                       adapter: int | list | None = None) -> tuple[np.ndarray, np.ndarray, dict]:
         """A speculating tenant's verify loop as ONE ``generate`` request.
         ``ids`` [B, K]: the pending token of each row (the last id drawn, at
         position ``pos``) and K - 1 drafts (any valid ids; a prefill's
@@ -325,6 +344,8 @@ class PodClient:
         wire = _wire(ids, self.input_dtype, "input")
         req = {"op": "generate", "steps": int(steps), "output": 1, "shape": [int(d) for d in ids.shape],
                "dtype": "i32" if wire.dtype == np.int32 else "f32", "speculate": {"end": int(end)}}
+        if adapter is not None:
+            req["adapter"] = _adapter_field(adapter)
         rep, data = self._call(req, wire.tobytes())
         toks, acc = P.unpack_arrays(rep["outputs"], data)
         return toks.reshape(B, -1).astype(np.int32), acc.reshape(-1, B).astype(np.int32), rep

@@ -61,7 +61,9 @@ block-diagonal GEMMs (``blockdiag``), RMSNorm folding, cast + activation as
 one ``unary`` pass (``cast_unary``), rotary fused into ``sdpa``, a cat
 written in place by its GEMM (``cat_buffer``), fp16-plane and LayerNorm
 hand-offs between h3 kernels (``cat_stats``: layer 0's statistics from the
-patch GEMM plus build-time constant rows), conv weight preparation.
+patch GEMM plus build-time constant rows), conv weight preparation, and for
+adapter tenants ``add(linear | linear_q8, lora)`` at decode rows as the GEMV
+with the adapter epilogue plus one ``lora_shrink`` step (``_fuse_lora``).
 
 The compiled program is a callable ``(x) -> tuple(outputs)``, captured into a
 HIP graph by the server exactly like a built-in model.  :meth:`Program.reference`

@@ -113,6 +113,12 @@ class Builder:
         request's ``"speculate"`` field (``ops.tenant.speculate_ctl``)."""
         return self.state(hist, [batch, max_len], "i32"), self.state(ctl, [4], "i32")
 
+    def adapter_state(self, batch: int, name: str = "adapter") -> str:
+        """The control state of an adapter program: i32 [batch], the LoRA adapter of each sequence
+        (1 .. n; 0 or anything out of range: the base model), which the server fills from each
+        request's ``"adapter"`` field and every ``lora`` node reads as its ``sel``."""
+        return self.state(name, [batch], "i32")
+
     def op(self, op: str, *inputs: str, out: str | None = None, **attrs) -> str:
         self._n += 1
         out = out or f"%{self._n}"

@@ -22,6 +22,12 @@ class _Step:
     release: list[str] = field(default_factory=list)   # values whose last use this is
 
 
+def _reads(s: _Step) -> list[str]:
+    """Every value a step reads: its inputs and, for a GEMV with the adapter epilogue, the adapter
+    operand ``attrs["lora"]`` = [t, B, sel] (kept out of ``inputs``, whose slots the passes index)."""
+    return s.inputs + s.attrs.get("lora", [])
+
+
 class Lowered:
     """A parsed program lowered onto the nos-amd ops for one device: the
     passes below turn its nodes into ``self.steps`` (the package docstring
@@ -63,6 +69,7 @@ class Lowered:
             steps = self._merge_parallel_linears(steps)
             if "blockdiag" not in skip:
                 steps = self._merge_blockdiag_linears(steps)
+            steps = self._fuse_lora(steps)
             steps = self._fold_layernorm(steps)
             steps = self._fold_rmsnorm(steps)
             steps = self._fuse_epilogues(steps)
@@ -91,7 +98,7 @@ class Lowered:
             steps = self._mark_ln_handoffs(steps)
             self._prep_conv_weights(steps)
             self.steps = self._plan_releases(steps)
-            used = {i for s in self.steps for i in s.inputs} | set(self.outputs)
+            used = {i for s in self.steps for i in _reads(s)} | set(self.outputs)
             for k in [k for k in self.consts if k not in used]:  # e.g. weights replaced by their LN-folded form
                 del self.consts[k]
         # the memo holds its recipes' SOURCE tensors (raw weights a fold replaced): only the
@@ -796,7 +803,7 @@ class Lowered:
     def _consumers(steps: list[_Step], outputs: list[str]) -> dict[str, int]:
         c: dict[str, int] = {}
         for s in steps:
-            for i in s.inputs:
+            for i in _reads(s):
                 c[i] = c.get(i, 0) + 1
         for o in outputs:
             c[o] = c.get(o, 0) + 1
@@ -828,6 +835,64 @@ class Lowered:
         self.stats["layernorm_folded"] = n
         return [s for s in steps if s.output not in drop]
 
+    def _fuse_lora(self, steps: list[_Step]) -> list[_Step]:
+        """GPU, decode rows (at most ``GEMV_MAX_ROWS``, known statically): ``add(linear | linear_q8,
+        lora)`` over one activation becomes that linear with the adapter epilogue (``attrs["lora"]`` =
+        [t, B, sel]; the GEMV adds ``B[sel] @ t`` to its product before anything else of its epilogue)
+        plus ONE ``lora_shrink`` step in front, which computes t from the x the GEMV reads.  The passes
+        after this one see an ordinary linear: the RMSNorm prologue, the SwiGLU and residual epilogues
+        and the decode partials fold as in a plain tenant, and take the shrink step along.  More rows (a
+        prefill), or the CPU: the ``lora`` step stays and runs as PyTorch ops on the device."""
+        from ...ops.tenant import GEMV_MAX_ROWS, GEMV_X_BYTES
+
+        self.stats["lora_shrinks"] = self.stats["lora_fused"] = 0
+        if not self.gpu or not any(s.kind == "lora" for s in steps):
+            return steps
+        uses = self._consumers(steps, self.outputs)
+        by_out = {s.output: s for s in steps}
+        drop: set[int] = set()
+        rename: dict[str, str] = {}
+        for s in steps:
+            if s.kind != "add":
+                continue
+            for ia, ib in ((0, 1), (1, 0)):
+                lin, lo = by_out.get(s.inputs[ia]), by_out.get(s.inputs[ib])
+                if (lin is None or lo is None or lin.kind not in ("linear", "linear_q8") or lo.kind != "lora"
+                        or lin.attrs or lin.inputs[0] != lo.inputs[0] or uses.get(lin.output) != 1
+                        or uses.get(lo.output) != 1
+                        or not all(i in self.consts for i in lin.inputs[1:] + lo.inputs[1:3])):
+                    continue
+                xs = tuple(self._shape(lo.inputs[0]))
+                # only where the GEMVs take the product (their rows and their 64 KiB of x): elsewhere the
+                # linear runs on a GEMM, which has no adapter epilogue, and the lora step stays
+                if (math.prod(xs[:-1]) > GEMV_MAX_ROWS or math.prod(xs) * 4 > GEMV_X_BYTES or xs[-1] % 16
+                        or self._dtype(lo.inputs[0]) != "fp32" or self._dtype(lin.inputs[1]) not in ("fp32", "i8")):
+                    continue
+                t = lo.output + "::t"
+                self._new_shapes[t] = (math.prod(xs[:-1]), self._shape(lo.inputs[1])[1])
+                self._new_dtypes[t] = "fp32"
+                lin.attrs = {"lora": [t, lo.inputs[2], lo.inputs[3]], "lora_rps": xs[1]}
+                lo.kind, lo.inputs, lo.output, lo.attrs = "lora_shrink", [lo.inputs[0], lo.inputs[1], lo.inputs[3]], t, \
+                    {"rps": xs[1]}
+                by_out[t] = lo
+                rename[s.output] = lin.output
+                drop.add(id(s))
+                self.stats["lora_shrinks"] += 1
+                self.stats["lora_fused"] += 1
+                break
+        out = []
+        for s in steps:
+            if id(s) in drop:
+                continue
+            s.inputs = [rename.get(i, i) for i in s.inputs]
+            out.append(s)
+        self.outputs = [rename.get(o, o) for o in self.outputs]   # an output that was the add
+        return self._reorder(out)
+
+    def _shrink_of(self, lin: _Step, by_out: dict) -> _Step | None:
+        """The ``lora_shrink`` step of a linear with the adapter epilogue (None: a plain linear)."""
+        return by_out.get(lin.attrs["lora"][0]) if lin.attrs.get("lora") else None
+
     def _fold_rmsnorm(self, steps: list[_Step]) -> list[_Step]:
         """rmsnorm -> linear (its only consumer, constant weights) becomes one
         ``linear_rms``: gamma folded into the weight, the row statistics in
@@ -842,9 +907,13 @@ class Lowered:
             if s.kind not in ("linear", "linear_q8") or s.inputs[0] not in by_out:
                 continue
             rn = by_out[s.inputs[0]]
-            if rn.kind != "rmsnorm" or uses.get(rn.output) != 1 or not all(i in self.consts for i in
-                                                                              s.inputs[1:] + rn.inputs[1:]):
+            sh = self._shrink_of(s, by_out)   # an adapted linear's shrink reads the norm too, and folds with it
+            if rn.kind != "rmsnorm" or uses.get(rn.output) != 1 + (sh is not None) or not all(
+                    i in self.consts for i in s.inputs[1:] + rn.inputs[1:]):
                 continue
+            if sh is not None:   # the same statistic and gamma in the shrink's x (gamma as a pointer)
+                sh.inputs = [rn.inputs[0]] + sh.inputs[1:] + [rn.inputs[1]]
+                sh.attrs = {**sh.attrs, "eps": rn.attrs.get("eps", 1e-5), "gamma": True}
             if s.kind == "linear_q8":
                 s.inputs = [rn.inputs[0]] + s.inputs[1:] + [rn.inputs[1]]
                 s.attrs = {**s.attrs, "eps": rn.attrs.get("eps", 1e-5), "gamma": True}
@@ -857,7 +926,8 @@ class Lowered:
                 "rms", [w, g], None, lambda w=w, g=g: (w.float() * g.float()[None, :]).to(w.dtype).contiguous())
             s.kind = "linear_rms"
             s.inputs = [rn.inputs[0], base + ".w"] + s.inputs[2:]
-            s.attrs = {"act": s.attrs.get("act"), "eps": rn.attrs.get("eps", 1e-5)}
+            s.attrs = {"act": s.attrs.get("act"), "eps": rn.attrs.get("eps", 1e-5),
+                       **{k: v for k, v in s.attrs.items() if k.startswith("lora")}}
             drop.add(rn.output)
             n += 1
         self.stats["rmsnorm_folded"], self.stats["q8_rms_prologue"] = n, nq
@@ -925,7 +995,7 @@ class Lowered:
         out, pending = [], list(steps)
         while pending:
             for i, s in enumerate(pending):
-                if all(x in defined for x in s.inputs) and readers_before.get(id(s), set()) <= placed:
+                if all(x in defined for x in _reads(s)) and readers_before.get(id(s), set()) <= placed:
                     out.append(s)
                     defined.add(s.output)
                     defined.add(s.attrs.get("deq_out"))   # an i8 kv_write's second value (or None)
@@ -1151,12 +1221,16 @@ class Lowered:
             if len(shp) != 4 or shp[1] != 1 or shp[0] > 8 or shp[3] not in (64, 128) or self._dtype(s.output) != "fp32":
                 continue
             r = by_input.get(s.output, [None])[0]
-            if r is None or r.kind != "reshape" or uses.get(r.output) != 1:
+            if r is None or r.kind != "reshape":
+                continue
+            readers = by_input.get(r.output, [])
+            lin = next((t for t in readers if t.kind in ("linear", "linear_q8")), None)
+            sh = self._shrink_of(lin, {t.output: t for t in readers}) if lin is not None else None
+            if uses.get(r.output) != 1 + (sh is not None):   # an adapted projection's shrink reads x too
                 continue
             rs = tuple(self._shape(r.output))
             if rs[0] != shp[0] or math.prod(rs[1:]) != shp[2] * shp[3] or rs[-1] != shp[2] * shp[3]:
                 continue
-            lin = by_input.get(r.output, [None])[0]
             if (lin is None or lin.kind not in ("linear", "linear_q8") or lin.inputs[0] != r.output
                     or lin.attrs.get("gamma") or lin.attrs.get("glu") or lin.attrs.get("out_into")
                     or lin.attrs.get("row_stats") or lin.attrs.get("planes_out") or lin.attrs.get("act") == "glu"):
@@ -1164,6 +1238,9 @@ class Lowered:
             s.attrs = {**s.attrs, "partials": True}
             lin.inputs = [s.output] + lin.inputs[1:]
             lin.attrs = {**lin.attrs, "x_partials": True}
+            if sh is not None:   # the shrink combines the partials as the GEMV does
+                sh.inputs = [s.output] + sh.inputs[1:]
+                sh.attrs = {**sh.attrs, "x_partials": True}
             drop.add(id(r))
             n, nq = n + (lin.kind == "linear"), nq + (lin.kind == "linear_q8")
         self.stats["decode_combines_into_gemv"], self.stats["q8_combines_into_gemv"] = n, nq
@@ -1343,7 +1420,7 @@ class Lowered:
     def _plan_releases(self, steps: list[_Step]) -> list[_Step]:
         last: dict[str, int] = {}
         for k, s in enumerate(steps):
-            for i in s.inputs:
+            for i in _reads(s):
                 last[i] = k
         keep = set(self.outputs) | set(self.consts) | {self.input_name} | set(self.state)
         for name, k in last.items():

@@ -25,10 +25,22 @@ class CompiledProgram(Lowered):
         for s in self.steps:
             a = [env[i] for i in s.inputs]
             k = s.kind
-            if k == "linear" and s.attrs.get("x_partials"):   # x = the decode attention's split partials
+            # a GEMV with the adapter epilogue: (t, B, sel, rows per sequence); t from its lora_shrink step
+            lo = s.attrs.get("lora")
+            lora = (env[lo[0]], env[lo[1]], env[lo[2]], int(s.attrs["lora_rps"])) if lo else None
+            if k == "lora_shrink":   # inputs: x (or the decode partials), A, sel, [gamma]
+                y = T.lora_shrink(a[0], a[1], a[2], rows_per_seq=int(s.attrs["rps"]),
+                                  rms_eps=float(s.attrs.get("eps", 0.0)), gamma=a[3] if s.attrs.get("gamma") else None)
+            elif k == "lora":   # more rows than the GEMVs take (a prefill): PyTorch ops, sel read on the device
+                y = T.lora(a[0], a[1], a[2], a[3])
+            elif k == "linear" and s.attrs.get("x_partials"):   # x = the decode attention's split partials
                 res = a.pop() if s.attrs.get("residual") else None
                 y = T.gemv_partials(a[0], a[1], a[2] if len(a) > 2 else None, act=s.attrs.get("act"),
-                                    residual=res).reshape(self._shape(s.output))
+                                    residual=res, lora=lora).reshape(self._shape(s.output))
+            elif k == "linear" and lora is not None:   # decode rows: the GEMV, or an error
+                res = a.pop() if s.attrs.get("residual") else None
+                y = T.linear_lora(a[0], a[1], a[2] if len(a) > 2 else None, act=s.attrs.get("act"), residual=res,
+                                  lora=lora)
             elif k == "linear":
                 res = a.pop() if s.attrs.get("residual") else None
                 rs = bool(s.attrs.get("row_stats")) and ops.ln_handoff_active() and (
@@ -90,17 +102,17 @@ class CompiledProgram(Lowered):
                              residual_first=bool(s.attrs.get("residual_first")), groups=s.attrs.get("groups", 1))
             elif k == "linear_rms":
                 y = T.linear_rms(a[0], a[1], a[2] if len(a) > 2 else None, act=s.attrs.get("act"), eps=s.attrs["eps"],
-                                 glu=bool(s.attrs.get("glu")))
+                                 glu=bool(s.attrs.get("glu")), lora=lora)
             elif k == "linear_q8":   # inputs: x, wq, wscale, [bias], [gamma], [residual]
                 res = a.pop() if s.attrs.get("residual") else None
                 g = a.pop() if s.attrs.get("gamma") else None
                 if s.attrs.get("x_partials"):   # x = the decode attention's split partials
                     y = T.gemv_q8_partials(a[0], a[1], a[2], a[3] if len(a) > 3 else None, act=s.attrs.get("act"),
-                                           residual=res).reshape(self._shape(s.output))
+                                           residual=res, lora=lora).reshape(self._shape(s.output))
                 else:
                     y = T.linear_q8(a[0], a[1], a[2], a[3] if len(a) > 3 else None, act=s.attrs.get("act"),
                                     residual=res, rms_eps=float(s.attrs.get("eps", 0.0)), gamma=g,
-                                    glu=bool(s.attrs.get("glu")))
+                                    glu=bool(s.attrs.get("glu")), lora=lora)
             elif k == "matmul":
                 y = T.matmul(a[0], a[1])
             elif k == "softmax":

@@ -44,6 +44,14 @@ def _workspace(node: Node, ins: list[Value], out: Value, f32_math: str) -> int:
             return 0
         kp = -(-k // 32) * 32
         return n * k * 4 + (m + n) * kp * 12 + out.numel * 4
+    if op == "lora":
+        # decode rows: t [rows, R] between the shrink launch and the GEMV that expands it; more rows
+        # (a prefill) gather each sequence's A and B and hold t and the masked delta beside the output
+        b, s, k = ins[0].shape
+        r, n = ins[1].shape[1], ins[2].shape[1]
+        if b * s <= 8:
+            return b * s * r * 4
+        return b * (r * k + n * r) * 4 + b * s * r * 4 + 2 * out.numel * 4
     if op == "matmul":
         k = ins[0].shape[-1]
         kp = -(-k // 32) * 32
@@ -78,6 +86,12 @@ class Program:
     seen_state: str | None = None        # the i32 [B, ceil(vocab / 32)] bitmap ``seen_mark`` fills
     speculate_state: str | None = None   # the i32 [4] state ``spec_accept`` reads (the token budget's end; per request)
     hist_state: str | None = None        # the i32 [B, L] token history ``hist_write`` keeps (a speculating tenant)
+    adapter_state: str | None = None     # the i32 [B] state its ``lora`` nodes read (an adapter per sequence; per request)
+
+    @property
+    def adapters(self) -> int:
+        """The adapters n its ``lora`` nodes hold (0: none); the server checks a request's ids against it."""
+        return min((self.values[n.inputs[1]].shape[0] for n in self.nodes if n.op == "lora"), default=0)
 
     # ------------------------------------------------------------ accounting
     @property

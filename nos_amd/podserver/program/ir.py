@@ -139,6 +139,10 @@ SPEC_MIN_K, SPEC_MAX_K = 2, 8
 SPEC_OPS = ("hist_write", "spec_accept", "pos_advance", "spec_draft")
 STATE_OPS = STATE_OPS + SPEC_OPS
 STATE_WRITERS = STATE_WRITERS + ("hist_write", "pos_advance")
+# multi-adapter LoRA (an adapter tenant): lora(x, A, B, sel) is the low-rank delta of the adapter each
+# sequence's ``sel`` names (0: none), added to a linear's output; ``sel`` is the program's adapter state
+LORA_MAX_RANK = 64           # the stacked rank R of one lora node (the GEMV epilogue stages t [rows, R] in LDS)
+STATE_OPS = STATE_OPS + ("lora",)
 STATE_DTYPES = ("fp32", "bf16", "i32", "i8")
 MAX_STATE = 1024
 OPS = OPS + STATE_OPS
@@ -147,7 +151,7 @@ NEVER_FOLD = ("attention", "sdpa", "linear_q8", *STATE_OPS)
 # step kinds that run a gfx950 kernel of libnos_hip.so (CompiledProgram.stats["kernels"])
 NATIVE_KINDS = ("linear", "linear_ln", "linear_rms", "ln_qkv_attention", "attention", "layernorm", "conv2d", "matmul",
                 "softmax", "embedding", "rmsnorm", "rotary", "sdpa", "patches", "unary", "kv_write", "sdpa_cache",
-                "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu", "linear_q8", *STOP_OPS, "stop_step", *SPEC_OPS, "spec_step")
+                "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu", "linear_q8", *STOP_OPS, "stop_step", *SPEC_OPS, "spec_step", "lora_shrink")
 # the steps a speculating tenant's verify program closes with (CompiledProgram.stats["spec_launches"]);
 # spec_step: spec_accept / hist_write / pos_advance / spec_draft fused into one launch
 SPEC_KINDS = (*SPEC_OPS, "spec_step")

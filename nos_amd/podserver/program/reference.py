@@ -141,6 +141,8 @@ def _eager(op: str, args: list, attrs: dict, ref: bool = False):
         return T.pos_advance(args[0], args[1])
     if op == "spec_draft":
         return T.spec_draft(args[0], args[1], int(attrs["k"]))
+    if op == "lora":
+        return T.lora_ref(args[0], args[1], args[2], args[3])
     if op == "pos_set":
         return args[0].fill_(int(attrs["value"]))
     if op == "argmax":

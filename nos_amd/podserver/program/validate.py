@@ -6,8 +6,8 @@ from __future__ import annotations
 import math
 
 from .graph import Program
-from .ir import (FLOAT_DTYPES, FORMAT, MAX_NUMEL, MAX_PARAMS, MAX_NODES, MAX_RANK, MAX_STATE, MAX_VARIANTS, OPS,
-                 PARAM_DTYPES, SPEC_CTL_WORDS, SPEC_MAX_K, SPEC_MIN_K, STATE_DTYPES, STATE_WRITERS, STOP_CTL_WORDS, ACTS,
+from .ir import (FLOAT_DTYPES, FORMAT, LORA_MAX_RANK, MAX_NUMEL, MAX_PARAMS, MAX_NODES, MAX_RANK, MAX_STATE,
+                 MAX_VARIANTS, OPS, PARAM_DTYPES, SPEC_CTL_WORDS, SPEC_MAX_K, SPEC_MIN_K, STATE_DTYPES, STATE_WRITERS, STOP_CTL_WORDS, ACTS,
                  BINARY, INTERP_MODES, UNARY, WIRE_DTYPES, Node, ProgramError, Value, _broadcast, _eps, _int, _name,
                  _pair, _req, _shape)
 
@@ -463,6 +463,33 @@ def _infer(node: Node, ins: list[Value], gpu: bool) -> tuple[tuple[int, ...], st
         k = _int(a.get("k"), f"{what}: k", SPEC_MIN_K)
         _req(k <= SPEC_MAX_K, f"{what}: k must be <= {SPEC_MAX_K}")
         return (ins[0].shape[0], k), "i32"
+    if op == "lora":
+        # the low-rank delta of the adapter each sequence's sel names: (x[b] @ A[a - 1].T) @ B[a - 1].T for
+        # a = sel[b] in [1, n], zeros otherwise (ops.tenant.lora_ref); added to a linear's output
+        only()
+        arity(4, 4)
+        x, A, B, sel = ins
+        _req(x.dtype == "fp32" and len(x.shape) == 3,
+             f"{what}: x must be fp32 [batch, S, K] (adapters are an fp32 tenant's; a bf16 x is not taken), got "
+             f"{x.dtype} {list(x.shape)}")
+        _req(sel.kind == "state", f"{what}: sel must be a state (the program's adapter state, which the server "
+             f"fills per request), got {sel.kind} {sel.name!r}")
+        _req(sel.dtype == "i32" and sel.shape == (x.shape[0],),
+             f"{what}: sel must be an i32 [{x.shape[0]}] state (an adapter per sequence), got {sel.dtype} "
+             f"{list(sel.shape)}")
+        _req(A.kind == B.kind == "param" and A.dtype == B.dtype == "fp32" and len(A.shape) == len(B.shape) == 3,
+             f"{what}: A [n, R, K] and B [n, N, R] must be fp32 params, got {A.kind} {A.dtype} {list(A.shape)} and "
+             f"{B.kind} {B.dtype} {list(B.shape)}")
+        _req(A.shape[0] == B.shape[0], f"{what}: A and B must hold the same number of adapters n, got "
+             f"{A.shape[0]} and {B.shape[0]}")
+        _req(A.shape[1] == B.shape[2], f"{what}: A [n, R, K] and B [n, N, R] must share the rank R, got "
+             f"{A.shape[1]} and {B.shape[2]}")
+        _req(A.shape[2] == x.shape[2], f"{what}: A [n, R, K] must have x's K = {x.shape[2]}, got {A.shape[2]}")
+        if gpu:
+            _req(A.shape[1] % 4 == 0 and A.shape[1] <= LORA_MAX_RANK and x.shape[2] % 4 == 0,
+                 f"{what}: the adapter kernels take a rank R <= {LORA_MAX_RANK} with R % 4 == 0 and K % 4 == 0, got "
+                 f"R = {A.shape[1]}, K = {x.shape[2]}")
+        return (x.shape[0], x.shape[1], B.shape[1]), "fp32"
     raise ProgramError(f"{what}: op {op!r} is not one the pod server runs (whitelist: {' '.join(OPS)})")
 
 
@@ -528,6 +555,7 @@ def parse_variants(objs: list, payload: bytes | memoryview = b"", gpu: bool = Fa
         _req(p.inputs[0].shape not in seen, f"two variants take the input shape {list(p.inputs[0].shape)}")
         seen.add(p.inputs[0].shape)
     _req(len({p.sampling_state for p in progs} - {None}) <= 1, "variants must share one sampling control state")
+    _req(len({p.adapter_state for p in progs} - {None}) <= 1, "variants must share one adapter state")
     for what in ("stopping_state", "done_state", "seen_state", "speculate_state", "hist_state"):
         _req(len({getattr(p, what) for p in progs} - {None}) <= 1,
              f"variants must share one {what.replace('_', ' ')} (the stopping control words, the done flags, the "
@@ -598,6 +626,7 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     sampling = None   # the control state of the program's sample nodes
     # a stopping program's control words, flags and bitmap; a speculating program's history and control words
     stop = {"stopping": None, "done": None, "seen": None, "hist": None, "speculate": None}
+    adapter = None    # the state the program's lora nodes read as sel (one per program)
     cache_rows: dict[int, str] = {}     # the lengths L of the caches [B, L, Hkv, D] the kv_writes fill -> a node
     spec_limits: dict[int, str] = {}    # the ``limit`` of every spec_accept -> a node
     scales_of: dict[str, str] = {}      # a scales state -> the i8 cache (root) whose row scales it holds
@@ -670,6 +699,10 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
             _req(stop[role] in (None, root), f"node {n.output!r} ({op}): a program has one {role} state; "
                  f"{stop[role]!r} and {root!r} are two")
             stop[role] = root
+        if op == "lora":
+            _req(adapter in (None, refs[3]), f"node {n.output!r} (lora): a program has one adapter state; "
+                 f"{adapter!r} and {refs[3]!r} are two")
+            adapter = refs[3]
         if op == "kv_write":
             cache_rows.setdefault(values[refs[0]].shape[1], f"node {n.output!r} ({op})")
         if op == "spec_accept":
@@ -687,7 +720,7 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
              f"a scales state is named only beside that cache in kv_write / sdpa_cache")
         _req(s_ not in outs, f"the scales state {s_!r} of the i8 cache {scales_of[s_]!r} cannot be an output")
     # the control states: at most one of each kind, and each its own state
-    ctls = [c for c in (sampling, stop["stopping"], stop["speculate"]) if c is not None]
+    ctls = [c for c in (sampling, stop["stopping"], stop["speculate"], adapter) if c is not None]
     _req(len(set(ctls)) == len(ctls), f"the control states of different kinds must be different states, got {ctls}")
     if stop["hist"] is not None:   # positions index the history as they index the caches
         L = state[stop["hist"]].shape[1]
@@ -696,10 +729,11 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
                  f"{'caches have' if rows in cache_rows else 'limit is'} {rows}: hist must be [batch, L] with L the caches' length")
     else:
         _req(not spec_limits, "a spec_accept needs the program's token history (a hist_write or spec_draft node)")
+    _req(adapter not in outs, f"the adapter state {adapter!r} cannot be an output: it is a control state")
     _req(not any(o in root_of for o in outs), "a state (or a version of one) cannot be an output: it is mutable")
     _req(not any(values[o].dtype == "i8" for o in outs), "an i8 param cannot be an output")
     return Program(name, inputs, params, layout, nodes, list(outs), values, payload, state=state,
                    state_root={k: v for k, v in root_of.items() if k != v}, sampling_state=sampling,
                    stopping_state=stop["stopping"], done_state=stop["done"], seen_state=stop["seen"],
-                   speculate_state=stop["speculate"], hist_state=stop["hist"])
+                   speculate_state=stop["speculate"], hist_state=stop["hist"], adapter_state=adapter)
 

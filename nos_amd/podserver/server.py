@@ -121,6 +121,8 @@ class Tenant:
     seen_state: str | None = None                   # ... the rows' token bitmaps (never replied)
     speculate_state: str | None = None              # the control state of its verify program (the token budget's end)
     hist_state: str | None = None                   # ... the rows' token history (a speculating generate's tokens)
+    adapter_state: str | None = None                # the control state of its programs' ``lora`` nodes (an adapter per row)
+    adapters: int = 0                               # ... the adapters they hold: a request's ids lie in [0, adapters]
 
 
 @dataclass
@@ -158,6 +160,7 @@ class _Job:
     stop: np.ndarray | None = None  # the stopping control words written before the run (stopping tenants)
     steps_run: int = 0             # "generate": the runs made (fewer than ``steps`` once every row was done)
     spec: np.ndarray | None = None  # the speculation control words written before the run (speculating tenants)
+    adapter: np.ndarray | None = None  # the rows' adapter ids written before the run (adapter tenants)
 
 
 class AdmissionError(RuntimeError):
@@ -225,6 +228,27 @@ def _speculate_words(req: dict, tenant: Tenant) -> np.ndarray | None:
     return speculate_ctl(**s)
 
 
+def _adapter_ids(req: dict, tenant: Tenant) -> np.ndarray | None:
+    """The adapter of each row a request's optional ``"adapter"`` asks for: an int (every row) or a
+    list of one int per row, each in [0, the tenant's adapters] (0: the base model).  An adapter
+    tenant's request without one gets zeros: the base model, whatever the request before it set.
+    None for a tenant without adapters."""
+    a = req.get("adapter")
+    if a is None:
+        return np.zeros(tenant.state[tenant.adapter_state].shape, dtype=np.int32) if tenant.adapter_state else None
+    if not tenant.adapter_state:
+        raise ValueError("adapter: the tenant's programs hold no adapters (register with adapters=[...])")
+    rows = int(tenant.state[tenant.adapter_state].shape[0])
+    ids = [a] * rows if isinstance(a, int) and not isinstance(a, bool) else a
+    if (not isinstance(ids, list) or len(ids) != rows
+            or not all(isinstance(i, int) and not isinstance(i, bool) for i in ids)):
+        raise ValueError(f"adapter must be an int or a list of {rows} ints (one per row of the batch)")
+    if not all(0 <= i <= tenant.adapters for i in ids):
+        raise ValueError(f"adapter: ids must lie in [0, {tenant.adapters}] (0: the base model; the tenant holds "
+                         f"{tenant.adapters} adapters), got {ids}")
+    return np.asarray(ids, dtype=np.int32)
+
+
 def _stop_ids_of(words: np.ndarray | None) -> list[int]:
     """The stop ids the control words arm ([] without any)."""
     return [] if words is None else [int(v) for v in words[3:3 + int(words[2])]]
@@ -265,8 +289,9 @@ def _sampling_state(progs) -> str | None:
 
 def _stop_states(progs) -> dict:
     """The states of the programs' stopping ops (variants share them), as Tenant fields."""
-    return {k: next((getattr(p, k) for p in progs if getattr(p, k)), None)
-            for k in ("stopping_state", "done_state", "seen_state", "speculate_state", "hist_state")}
+    return {**{k: next((getattr(p, k) for p in progs if getattr(p, k)), None)
+               for k in ("stopping_state", "done_state", "seen_state", "speculate_state", "hist_state", "adapter_state")},
+            "adapters": max(p.adapters for p in progs)}
 
 
 def _target_wire(trainer) -> str:
@@ -691,7 +716,8 @@ class PodServer:
                         else:
                             want = bool(want)
                         job = _Job(tenant, payload, want, shp, ctl=_sampling_words(req, tenant),
-                                   stop=_stopping_words(req, tenant), spec=_speculate_words(req, tenant))
+                                   stop=_stopping_words(req, tenant), spec=_speculate_words(req, tenant),
+                                   adapter=_adapter_ids(req, tenant))
                         self._jobs.put(job, hi=tenant.latency)
                         job.done.wait()
                         if job.error:
@@ -716,7 +742,7 @@ class PodServer:
                         _check_wire_dtype(req.get("dtype"), _wire_dtype(tenant.x), "input")
                         job = _Job(tenant, payload, [feed], shp, kind="generate", steps=n, feed=feed,
                                    ctl=_sampling_words(req, tenant), stop=_stopping_words(req, tenant),
-                                   spec=_speculate_words(req, tenant))
+                                   spec=_speculate_words(req, tenant), adapter=_adapter_ids(req, tenant))
                         self._jobs.put(job, hi=tenant.latency)
                         job.done.wait()
                         if job.error:
@@ -1269,6 +1295,8 @@ class PodServer:
                     t.state[t.stopping_state].copy_(torch.from_numpy(job.stop))
                 if job.spec is not None:
                     t.state[t.speculate_state].copy_(torch.from_numpy(job.spec))
+                if job.adapter is not None:
+                    t.state[t.adapter_state].copy_(torch.from_numpy(job.adapter))
                 if x_in is not None:
                     v.x.copy_(torch.from_numpy(x_in.copy()).view(v.x.shape))
                 v.outputs = outs = v.model(v.x)
@@ -1311,6 +1339,11 @@ class PodServer:
                         ctl = t.state[t.speculate_state]
                         hb = _pinned(t.host, "speculate", ctl.shape, ctl.dtype)
                         hb.numpy()[:] = job.spec
+                        ctl.copy_(hb, non_blocking=True)
+                    if job.adapter is not None:   # and its rows' adapters
+                        ctl = t.state[t.adapter_state]
+                        hb = _pinned(t.host, "adapter", ctl.shape, ctl.dtype)
+                        hb.numpy()[:] = job.adapter
                         ctl.copy_(hb, non_blocking=True)
                     if x_in is not None:
                         if str(v.x.dtype)[6:] == str(x_in.dtype):
@@ -1411,7 +1444,7 @@ class PodServer:
     @staticmethod
     def _not_counters(t: Tenant) -> tuple:
         """Small i32 states that are no counters: the control words and (at a tiny vocab) the bitmaps."""
-        return (t.sampling_state, t.stopping_state, t.seen_state, t.speculate_state, t.hist_state)
+        return (t.sampling_state, t.stopping_state, t.seen_state, t.speculate_state, t.hist_state, t.adapter_state)
 
     def _counters_start(self, t: Tenant):
         """``_counters`` behind the lane's one synchronisation: the copies are
