@@ -1724,6 +1724,267 @@ __global__ __launch_bounds__(256) void lora_shrink_kernel(const float* __restric
   }
 }
 
+// ------------------------------------------------------------------ mixture of experts (rows <= 8)
+// y[m] = sum_s w[m][s] W2[e] (silu(W13[e][:I] x') * (W13[e][I:] x')), e = idx[m][s]: the k experts row m's
+// router chose, in three launches -- route (idx, w), glu (act [rows][k][I]) and down (y).  x' is the x
+// the GEMVs multiply: under an RMSNorm prologue the row's statistic is computed here and gamma read
+// through a pointer (no expert weight is ever copied or folded).  Every sum has a fixed order (no
+// atomics), so a step is bit-reproducible.  An index read from idx is checked against [0, E) before
+// it forms an address: a slot outside it reads no weight and contributes zero.
+constexpr int MOE_MAX_E = 64;   // a lane per expert in the softmax and the arg-max rounds
+constexpr int MOE_MAX_K = 8;
+
+// Row xr [H] into LDS as the GEMV prologue leaves it (times gamma under rms_eps > 0); returns the
+// factor the products over xs are scaled by (1 without a prologue).  Every thread of the workgroup
+// calls it; xs is complete on return.
+__device__ __forceinline__ float moe_stage_x(const float* __restrict__ xr, const float* __restrict__ gamma,
+                                             float rms_eps, int H, float* __restrict__ xs, float (&red)[4]) {
+  const int tid = threadIdx.x;
+  float q = 0.f;
+  for (int k = tid * 4; k < H; k += 1024) {
+    float4 xv = *reinterpret_cast<const float4*>(xr + k);
+    if (rms_eps > 0.f) {
+      q = fmaf(xv.x, xv.x, fmaf(xv.y, xv.y, fmaf(xv.z, xv.z, fmaf(xv.w, xv.w, q))));
+      if (gamma != nullptr) {
+        const float4 g = *reinterpret_cast<const float4*>(gamma + k);
+        xv = float4{xv.x * g.x, xv.y * g.y, xv.z * g.z, xv.w * g.w};
+      }
+    }
+    *reinterpret_cast<float4*>(xs + k) = xv;
+  }
+  q = nos::wave_sum(q);
+  if ((tid & 63) == 0) red[tid >> 6] = q;
+  __syncthreads();
+  return rms_eps > 0.f ? rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)H + rms_eps) : 1.f;
+}
+
+__device__ __forceinline__ float dot4(float4 a, float4 b, float acc) {
+  return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, fmaf(a.w, b.w, acc))));
+}
+
+// One workgroup per row: the E router logits (the waves share the experts, 16-byte loads of Wr), the
+// softmax over all E in wave 0 (a lane per expert), k arg-max rounds (a tie goes to the lower index)
+// and the renormalisation: idx [rows][k], w [rows][k] in descending order of p.
+__global__ __launch_bounds__(256) void moe_route_kernel(const float* __restrict__ x, int ldx,
+                                                        const float* __restrict__ Wr, int ldwr,
+                                                        const float* __restrict__ gamma, float rms_eps,
+                                                        int* __restrict__ idx, float* __restrict__ w, int E, int H,
+                                                        int k) {
+  extern __shared__ __attribute__((aligned(16))) float xs[];   // [H]
+  __shared__ float red[4];
+  __shared__ float logit[MOE_MAX_E];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, m = blockIdx.x;
+  // a wave takes the experts e0 and e0 + 4 together, KU K steps of both in flight: at E = 8 and
+  // H = 1024 the whole router is one batch of loads per lane, issued ahead of the x staging
+  constexpr int KU = 4;
+  const float4 zero4 = float4{0.f, 0.f, 0.f, 0.f};
+  auto load_pair = [&](int e0, int k0, float4 (&a)[KU], float4 (&c)[KU]) {
+    const bool two = e0 + 4 < E;
+    const float* r0 = Wr + (long long)e0 * ldwr;
+    const float* r1 = Wr + (long long)(two ? e0 + 4 : e0) * ldwr;
+    const int H1 = two ? H : 0;   // a missing second expert: no lane loads (a bound, not a branch per load)
+#pragma unroll
+    for (int j = 0; j < KU; ++j) {
+      const int kk = k0 + 256 * j;
+      a[j] = kk < H ? *reinterpret_cast<const float4*>(r0 + kk) : zero4;
+      c[j] = kk < H1 ? *reinterpret_cast<const float4*>(r1 + kk) : zero4;
+    }
+  };
+  float4 pa[KU], pc[KU];
+  if (wid < E) load_pair(wid, lane * 4, pa, pc);
+  const float rsc = moe_stage_x(x + (long long)m * ldx, gamma, rms_eps, H, xs, red);
+  for (int e0 = wid; e0 < E; e0 += 8) {
+    float a0 = 0.f, a1 = 0.f;
+    for (int k0 = lane * 4; k0 < H; k0 += 256 * KU) {
+      float4 ra[KU], rc[KU];
+      if (e0 == wid && k0 == lane * 4) {
+#pragma unroll
+        for (int j = 0; j < KU; ++j) {
+          ra[j] = pa[j];
+          rc[j] = pc[j];
+        }
+      } else {
+        load_pair(e0, k0, ra, rc);
+      }
+#pragma unroll
+      for (int j = 0; j < KU; ++j) {
+        const int kk = k0 + 256 * j;
+        if (kk < H) {
+          const float4 xv = *reinterpret_cast<const float4*>(xs + kk);
+          a0 = dot4(ra[j], xv, a0);
+          a1 = dot4(rc[j], xv, a1);
+        }
+      }
+    }
+    a0 = nos::wave_sum(a0);
+    a1 = nos::wave_sum(a1);
+    if (lane == 0) {
+      logit[e0] = a0 * rsc;
+      if (e0 + 4 < E) logit[e0 + 4] = a1 * rsc;
+    }
+  }
+  __syncthreads();
+  if (wid != 0) return;
+  const float l = lane < E ? logit[lane] : -INFINITY;
+  const float mx = nos::wave_max(l);
+  const float ex = lane < E ? expf(l - mx) : 0.f;
+  const float p = ex / nos::wave_sum(ex);
+  float cand = lane < E ? p : -1.f;   // a chosen expert leaves the running (p >= 0 > -1)
+  float tot = 0.f, my_p = 0.f;
+  int my_i = 0;
+  for (int s = 0; s < k; ++s) {
+    float bv = cand;
+    int bi = lane;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > bv || (ov == bv && oi < bi)) {
+        bv = ov;
+        bi = oi;
+      }
+    }
+    if (lane == s) {
+      my_p = bv;
+      my_i = bi;
+    }
+    if (lane == bi) cand = -1.f;
+    tot += bv;
+  }
+  if (lane < k) {
+    idx[(long long)m * k + lane] = my_i;
+    w[(long long)m * k + lane] = my_p / tot;
+  }
+}
+
+// Grid (column tiles of I) x (rows x k): pair (m, s) streams the gate and up rows of its expert's W13
+// against x'[m] (a wave per column: gate row n and up row I + n, as the GEMV's GLU epilogue pairs
+// them) and writes act[m][s][n] = silu(g) * u.  A slot whose index is outside [0, E) writes zeros.
+__global__ __launch_bounds__(256) void moe_glu_kernel(const float* __restrict__ x, int ldx,
+                                                      const int* __restrict__ idx, const float* __restrict__ W13,
+                                                      long long bs13, int ld13, const float* __restrict__ gamma,
+                                                      float rms_eps, float* __restrict__ act, int E, int H, int I,
+                                                      int k) {
+  extern __shared__ __attribute__((aligned(16))) float xs[];   // [H]
+  __shared__ float red[4];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int pair = blockIdx.y, m = pair / k;
+  const int e = __builtin_amdgcn_readfirstlane(idx[pair]);
+  float* out = act + (long long)pair * I;
+  const int ngrp = (I + 3) / 4;
+  if (e < 0 || e >= E) {   // the whole workgroup: no barrier is left behind
+    for (int n = blockIdx.x * 256 + tid; n < I; n += gridDim.x * 256) out[n] = 0.f;
+    return;
+  }
+  const float* We = W13 + (long long)e * bs13;
+  constexpr int KU = 4;
+  auto load_chunk = [&](const float* g, const float* u, int k0, float4 (&a)[KU], float4 (&c)[KU]) {
+#pragma unroll
+    for (int j = 0; j < KU; ++j) {
+      const int kk = k0 + 256 * j;
+      a[j] = kk < H ? *reinterpret_cast<const float4*>(g + kk) : float4{0.f, 0.f, 0.f, 0.f};
+      c[j] = kk < H ? *reinterpret_cast<const float4*>(u + kk) : float4{0.f, 0.f, 0.f, 0.f};
+    }
+  };
+  // the first group's first chunk of weights in flight while x is staged (as the GEMV does)
+  float4 pa[KU], pc[KU];
+  if ((int)blockIdx.x < ngrp) {
+    const int n = min((int)blockIdx.x * 4 + wid, I - 1);
+    load_chunk(We + (long long)n * ld13, We + (long long)(I + n) * ld13, lane * 4, pa, pc);
+  }
+  const float rsc = moe_stage_x(x + (long long)m * ldx, gamma, rms_eps, H, xs, red);
+  for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    const int n0 = grp * 4 + wid, n = min(n0, I - 1);
+    const float* g = We + (long long)n * ld13;
+    const float* u = We + (long long)(I + n) * ld13;
+    float ag = 0.f, au = 0.f;
+    for (int k0 = lane * 4; k0 < H; k0 += 256 * KU) {
+      float4 ra[KU], rc[KU];
+      if (grp == (int)blockIdx.x && k0 == lane * 4) {
+#pragma unroll
+        for (int j = 0; j < KU; ++j) {
+          ra[j] = pa[j];
+          rc[j] = pc[j];
+        }
+      } else {
+        load_chunk(g, u, k0, ra, rc);
+      }
+#pragma unroll
+      for (int j = 0; j < KU; ++j) {
+        const int kk = k0 + 256 * j;
+        if (kk < H) {
+          const float4 xv = *reinterpret_cast<const float4*>(xs + kk);
+          ag = dot4(ra[j], xv, ag);
+          au = dot4(rc[j], xv, au);
+        }
+      }
+    }
+    ag = nos::wave_sum(ag) * rsc;
+    au = nos::wave_sum(au) * rsc;
+    if (lane == 0 && n0 < I) out[n0] = ag / (1.f + __expf(-ag)) * au;
+  }
+}
+
+// Grid (column tiles of H) x rows: out[m][n] = res[m][n] + sum_{s < k} w[m][s] (W2[e_s][n] . act[m][s]),
+// a column per wave; a lane sums its slots' terms in the order 0 .. k - 1 and the wave sum closes
+// the column.  act[m] (k x I floats) sits in LDS.
+__global__ __launch_bounds__(256) void moe_down_kernel(const float* __restrict__ act, const int* __restrict__ idx,
+                                                       const float* __restrict__ w, const float* __restrict__ W2,
+                                                       long long bs2, int ld2, const float* __restrict__ res, int ldr,
+                                                       float* __restrict__ y, int ldy, int E, int H, int I, int k) {
+  extern __shared__ __attribute__((aligned(16))) float as[];   // [k][I]
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, m = blockIdx.y;
+  const float* am = act + (long long)m * k * I;
+  for (int e4 = tid * 4; e4 < k * I; e4 += 1024)
+    *reinterpret_cast<float4*>(as + e4) = *reinterpret_cast<const float4*>(am + e4);
+  __syncthreads();
+  // a column per wave (H = 1024 at one row: 256 workgroups, one per CU), its slots two at a time with
+  // KU K steps of both in flight: I = 1408 at k = 2 is ONE batch of loads per lane, as the dense
+  // down projection's K = 2816 is
+  const int ngrp = (H + 3) / 4;
+  constexpr int KU = 6;
+  const float4 zero4 = float4{0.f, 0.f, 0.f, 0.f};
+  for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    const int n0 = grp * 4 + wid, r = min(n0, H - 1);
+    float acc = 0.f;
+    for (int s = 0; s < k; s += 2) {
+      const bool two = s + 1 < k;
+      const int e0 = __builtin_amdgcn_readfirstlane(idx[(long long)m * k + s]);
+      const int e1 = two ? __builtin_amdgcn_readfirstlane(idx[(long long)m * k + s + 1]) : -1;
+      const bool v0 = e0 >= 0 && e0 < E, v1 = e1 >= 0 && e1 < E;   // wave-uniform; checked before any address
+      if (!v0 && !v1) continue;
+      const float* p0 = v0 ? W2 + (long long)e0 * bs2 + (long long)r * ld2 : W2;
+      const float* p1 = v1 ? W2 + (long long)e1 * bs2 + (long long)r * ld2 : W2;
+      const float* a0 = as + s * I;
+      const float* a1 = as + (v1 ? s + 1 : s) * I;
+      const int I0 = v0 ? I : 0, I1 = v1 ? I : 0;   // an invalid slot: no lane loads or adds (a bound, not a branch per load)
+      float d0 = 0.f, d1 = 0.f;
+      for (int k0 = lane * 4; k0 < I; k0 += 256 * KU) {
+        float4 ra[KU], rc[KU];
+#pragma unroll
+        for (int j = 0; j < KU; ++j) {
+          const int kk = k0 + 256 * j;
+          ra[j] = kk < I0 ? *reinterpret_cast<const float4*>(p0 + kk) : zero4;
+          rc[j] = kk < I1 ? *reinterpret_cast<const float4*>(p1 + kk) : zero4;
+        }
+#pragma unroll
+        for (int j = 0; j < KU; ++j) {
+          const int kk = k0 + 256 * j;
+          if (kk < I0) d0 = dot4(ra[j], *reinterpret_cast<const float4*>(a0 + kk), d0);
+          if (kk < I1) d1 = dot4(rc[j], *reinterpret_cast<const float4*>(a1 + kk), d1);
+        }
+      }
+      if (v0) acc = fmaf(w[(long long)m * k + s], d0, acc);       // slot order: s, then s + 1
+      if (v1) acc = fmaf(w[(long long)m * k + s + 1], d1, acc);
+    }
+    acc = nos::wave_sum(acc);
+    if (lane == 0 && n0 < H) {
+      if (res != nullptr) acc += res[(long long)m * ldr + n0];
+      y[(long long)m * ldy + n0] = acc;
+    }
+  }
+}
+
 // out [N, K] fp32 = (float)q * wscale[n], one rounding: 4 weights per thread (a 4-byte load, a 16-byte store)
 __global__ __launch_bounds__(256) void dequant_q8_kernel(const signed char* __restrict__ w, int ldw,
                                                          const float* __restrict__ wscale, float* __restrict__ out,
@@ -2327,5 +2588,60 @@ NOS_API int nos_dequant_q8(const void* wq, int ldw, const float* wscale, float* 
   const long long blocks = (total + 255) / 256;
   hipLaunchKernelGGL(dequant_q8_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, stream,
                      static_cast<const signed char*>(wq), ldw, wscale, out, ldo, N, K);
+  return (int)hipGetLastError();
+}
+
+// The mixture-of-experts block of a decode step (moe_route_kernel / moe_glu_kernel / moe_down_kernel):
+// M <= 8 rows of x [M, H] fp32, E <= 64 experts, 1 <= k <= min(E, 8), H % 4 == 0 and I % 4 == 0, every
+// base 16-byte aligned and every row stride a multiple of 4 floats; gamma (or null) only with
+// rms_eps > 0.  idx [M, k] i32 and w [M, k] fp32 are contiguous, act [M, k, I] fp32 too.
+static bool moe_dims_ok(int M, int E, int H, int I, int k) {
+  return M >= 1 && M <= 8 && E >= 1 && E <= MOE_MAX_E && k >= 1 && k <= MOE_MAX_K && k <= E && H >= 4 && (H % 4) == 0 &&
+         I >= 4 && (I % 4) == 0 && (long long)H * 4 <= 65536;
+}
+
+static bool moe_x_ok(const float* x, int ldx, const float* gamma, float rms_eps, int H) {
+  return x && ldx >= H && (ldx % 4) == 0 && !((uintptr_t)x & 15) &&
+         (!gamma || (rms_eps > 0.f && !((uintptr_t)gamma & 15)));
+}
+
+NOS_API int nos_moe_route(const float* x, int ldx, const float* Wr, int ldwr, const float* gamma, float rms_eps,
+                          int* idx, float* w, int M, int E, int H, int k, hipStream_t stream) {
+  if (!moe_dims_ok(M, E, H, 4, k) || !moe_x_ok(x, ldx, gamma, rms_eps, H) || !Wr || ldwr < H || (ldwr % 4) ||
+      ((uintptr_t)Wr & 15) || !idx || !w || ((uintptr_t)idx & 3) || ((uintptr_t)w & 3))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(moe_route_kernel, dim3((unsigned)M), dim3(256), (size_t)H * 4, stream, x, ldx, Wr, ldwr, gamma,
+                     rms_eps, idx, w, E, H, k);
+  return (int)hipGetLastError();
+}
+
+NOS_API int nos_moe_glu(const float* x, int ldx, const int* idx, const float* W13, long long bs13, int ld13,
+                        const float* gamma, float rms_eps, float* act, int M, int E, int H, int I, int k,
+                        hipStream_t stream) {
+  if (!moe_dims_ok(M, E, H, I, k) || !moe_x_ok(x, ldx, gamma, rms_eps, H) || !idx || ((uintptr_t)idx & 3) || !W13 ||
+      ld13 < H || (ld13 % 4) || bs13 < (long long)(2 * I - 1) * ld13 + H || (bs13 % 4) || ((uintptr_t)W13 & 15) ||
+      !act || ((uintptr_t)act & 15))
+    return (int)hipErrorInvalidValue;
+  const int ngrp = (I + 3) / 4, pairs = M * k;
+  int gx = 16 * nos_effective_cus() / pairs;   // up to 16 workgroups per CU over all pairs, as the GEMV
+  gx = gx < 1 ? 1 : (gx > ngrp ? ngrp : gx);
+  hipLaunchKernelGGL(moe_glu_kernel, dim3((unsigned)gx, (unsigned)pairs), dim3(256), (size_t)H * 4, stream, x, ldx,
+                     idx, W13, bs13, ld13, gamma, rms_eps, act, E, H, I, k);
+  return (int)hipGetLastError();
+}
+
+NOS_API int nos_moe_down(const float* act, const int* idx, const float* w, const float* W2, long long bs2, int ld2,
+                         const float* res, int ldr, float* y, int ldy, int M, int E, int H, int I, int k,
+                         hipStream_t stream) {
+  if (!moe_dims_ok(M, E, H, I, k) || (long long)k * I * 4 > 65536 || !act || ((uintptr_t)act & 15) || !idx ||
+      ((uintptr_t)idx & 3) || !w || ((uintptr_t)w & 3) || !W2 || ld2 < I || (ld2 % 4) ||
+      bs2 < (long long)(H - 1) * ld2 + I || (bs2 % 4) || ((uintptr_t)W2 & 15) || !y || ((uintptr_t)y & 3) || ldy < H ||
+      (res && (ldr < H || ((uintptr_t)res & 3))))
+    return (int)hipErrorInvalidValue;
+  const int ngrp = (H + 3) / 4;
+  int gx = 16 * nos_effective_cus() / M;
+  gx = gx < 1 ? 1 : (gx > ngrp ? ngrp : gx);
+  hipLaunchKernelGGL(moe_down_kernel, dim3((unsigned)gx, (unsigned)M), dim3(256), (size_t)k * I * 4, stream, act, idx,
+                     w, W2, bs2, ld2, res, ldr, y, ldy, E, H, I, k);
   return (int)hipGetLastError();
 }

@@ -60,6 +60,51 @@ def llama_model(cfg, seed: int = 0):
     return m
 
 
+def mixtral_config(small: bool = True, **kw):
+    """A MixtralConfig: ``small`` -- the tests' tiny variant (4 experts, top-2); else the fleet shape, the
+    fleet Llama tenant with its MLP as E = 8 experts of ``intermediate_size`` 1408 and k = 2, so a token
+    streams the dense fleet decoder's MLP bytes.  Keyword arguments override fields."""
+    from transformers import MixtralConfig
+
+    base = dict(hidden_size=256, num_hidden_layers=2, num_attention_heads=2, num_key_value_heads=1,
+                intermediate_size=96, vocab_size=512, max_position_embeddings=512, rms_norm_eps=1e-5,
+                num_local_experts=4, num_experts_per_tok=2, sliding_window=None, tie_word_embeddings=False) if small else \
+        dict(hidden_size=1024, num_hidden_layers=8, num_attention_heads=8, num_key_value_heads=2,
+             intermediate_size=1408, vocab_size=32000, max_position_embeddings=4096, rms_norm_eps=1e-5,
+             num_local_experts=8, num_experts_per_tok=2, sliding_window=None, tie_word_embeddings=False)
+    base.update(kw)
+    return MixtralConfig(**base)
+
+
+def mixtral_model(cfg, seed: int = 0):
+    """A random-init HF MixtralForCausalLM in fp32, eval mode (eager attention); the router's weights are
+    drawn at three times HF's 0.02, so that the experts' probabilities differ clearly and no expert's is tiny."""
+    import torch
+    from transformers import MixtralForCausalLM
+
+    torch.manual_seed(seed)
+    cfg._attn_implementation = "eager"
+    cfg._experts_implementation = "eager"   # the per-expert loop (any dtype; the grouped GEMM takes no fp64)
+    m = MixtralForCausalLM(cfg).float().eval()
+    with torch.no_grad():
+        g = torch.Generator().manual_seed(seed + 1)
+        for name, p in m.named_parameters():
+            if name.endswith("norm.weight"):
+                p.copy_(1 + 0.1 * torch.randn(p.shape, generator=g))
+            elif name.endswith("mlp.gate.weight"):
+                p.copy_(0.06 * torch.randn(p.shape, generator=g))
+    return m
+
+
+def _rope_theta(cfg) -> float:
+    """The rotary base: ``rope_parameters["rope_theta"]`` where the config keeps it there (transformers 5),
+    else its ``rope_theta`` attribute, else 10000."""
+    rp = getattr(cfg, "rope_parameters", None)
+    if isinstance(rp, dict) and rp.get("rope_theta") is not None:
+        return float(rp["rope_theta"])
+    return float(getattr(cfg, "rope_theta", 10000.0))
+
+
 def rope_tables(seq: int, head_dim: int, theta: float) -> tuple[np.ndarray, np.ndarray]:
     inv = 1.0 / theta ** (np.arange(0, head_dim, 2, dtype=np.float64) / head_dim)
     f = np.outer(np.arange(seq, dtype=np.float64), inv)
@@ -86,7 +131,7 @@ def llama_program(model, seq: int, batch: int = 1, dtype: str = "fp32",
     b = Builder(f"llama-h{d}-l{cfg.num_hidden_layers}-{dtype}")
     ids = b.input("input_ids", [batch, seq], "i32")
     P = lambda k: b.param(k, sd[k], dtype)  # noqa: E731
-    cos, sin = rope_tables(rope_len, hd, float(getattr(cfg, "rope_theta", 10000.0)))
+    cos, sin = rope_tables(rope_len, hd, _rope_theta(cfg))
     rc, rs = b.param("rope.cos", cos, "fp32"), b.param("rope.sin", sin, "fp32")
     if rope_len > seq:
         rc, rs = (b.op("slice", t, dim=0, start=0, end=seq) for t in (rc, rs))
@@ -281,9 +326,22 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     with one stacked A ``[A_q; A_k; A_v]`` and a B block-structured over the
     merged columns (``scale`` folded in, zero blocks stored), the stacked rank
     at most 64 and a multiple of 4.  :func:`adapted_llama` is the model such a
-    tenant computes for one adapter.  Adapters are fixed at registration."""
+    tenant computes for one adapter.  Adapters are fixed at registration.
+
+    A ``MixtralForCausalLM`` (``config.model_type == "mixtral"``) builds the same
+    programs, named ``mixtral-...``, with the MLP half of every layer as ``h =
+    add(moe(rmsnorm(h), mlp.gate.weight, mlp.experts.gate_up_proj,
+    mlp.experts.down_proj, top_k=num_experts_per_tok), h)`` over the fused expert
+    tensors as the state dict holds them.  ``batch``, ``extend``, ``sampling``,
+    ``stopping``, ``kv="int8"``, ``speculate`` and ``adapters`` on q / k / v / o work
+    as above; refused, each with its rule: ``weights="int8"``, ``dtype="bf16"``,
+    adapter targets in the MLP, a ``sliding_window`` smaller than ``max_len`` and a
+    ``speculate`` with ``batch * K * max(H, I) * 4 > GEMV_X_BYTES``."""
     from ..ops.tenant import GEMV_MAX_ROWS, GEMV_X_BYTES
 
+    moe = getattr(model.config, "model_type", None) == "mixtral"
+    if moe:
+        _refuse_mixtral(model.config, max_len, batch, dtype, weights, speculate, adapters, GEMV_X_BYTES)
     if adapters is not None and dtype != "fp32":
         raise ValueError("adapters are an fp32 tenant's (fp32 A and B beside fp32 or int8 weights): dtype must be 'fp32', "
                          "dtype='bf16' is not taken")
@@ -325,7 +383,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     nkv = cfg.num_key_value_heads
     hd = getattr(cfg, "head_dim", None) or d // nh
     eps = float(cfg.rms_norm_eps)
-    cos, sin = rope_tables(max_len, hd, float(getattr(cfg, "rope_theta", 10000.0)))
+    cos, sin = rope_tables(max_len, hd, _rope_theta(cfg))
     head = "lm_head.weight" if "lm_head.weight" in sd else "model.embed_tokens.weight"
     cache_dt = "bf16" if dtype == "bf16" else "fp32"
     progs = []
@@ -334,7 +392,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
         chunks.append((speculate, False, True))
     payload = b""
     for seq, reset, verify in chunks:
-        b = Builder(f"llama-h{d}-l{cfg.num_hidden_layers}-{dtype}{'-q8' if q8 else ''}{'-kvq8' if kvq8 else ''}-"
+        b = Builder(f"{'mixtral' if moe else 'llama'}-h{d}-l{cfg.num_hidden_layers}-{dtype}{'-q8' if q8 else ''}{'-kvq8' if kvq8 else ''}-"
                     f"{'stop-' if stopping else ''}{'spec-' if speculate else ''}{'lora-' if stacked else ''}"
                     f"{'prefill' if reset else 'verify' if verify else 'step'}{seq}")
         ids = b.input("input_ids", [batch, seq], "i32")
@@ -401,6 +459,10 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
             o = b.op("reshape", b.op("sdpa_cache", q, kc, vc, p, *ks, *vs), shape=[batch, seq, nh * hd])
             h = b.op("add", adapted(lin(o, pf + "self_attn.o_proj.weight"), o, pf + "self_attn.o_proj"), h)
             y = b.op("rmsnorm", h, P(pf + "post_attention_layernorm.weight"), eps=eps)
+            if moe:   # the sparse MLP: the router, the fused expert tensors as the state dict holds them
+                h = b.op("add", b.moe(y, P(pf + "mlp.gate.weight"), P(pf + "mlp.experts.gate_up_proj"),
+                                      P(pf + "mlp.experts.down_proj"), cfg.num_experts_per_tok), h)
+                continue
             if q8 or pf + "mlp.gate_up_proj" in stacked:
                 if pf + "mlp.gate_up_proj" in stacked:
                     gu = adapted(merged(y, pf + "mlp.gate_up_proj"), y, pf + "mlp.gate_up_proj")
@@ -452,6 +514,30 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
         progs.append(prog)
         payload = w
     return progs, payload
+
+
+def _refuse_mixtral(cfg, max_len, batch, dtype, weights, speculate, adapters, x_bytes) -> None:
+    """What a Mixtral tenant does not take (``llama_decode_programs``), each with its rule."""
+    if weights == "int8":
+        raise ValueError("a Mixtral tenant's weights are fp32: weights='int8' is not taken (no quantized experts yet)")
+    if dtype != "fp32":
+        raise ValueError(f"a Mixtral tenant is fp32 (the moe op takes an fp32 x and fp32 experts): dtype={dtype!r} "
+                         f"is not taken")
+    if adapters is not None:
+        mlp = sorted(k for a in adapters if isinstance(a, dict) for k in a if ".mlp." in str(k))
+        if mlp:
+            raise ValueError(f"a Mixtral tenant's adapters target q / k / v / o only: {mlp[0]!r} is in the MLP, which "
+                             f"is a mixture of experts")
+    sw = getattr(cfg, "sliding_window", None)
+    if sw is not None and sw < max_len:
+        raise ValueError(f"sliding_window = {sw} is set and smaller than max_len = {max_len}: the caches attend every "
+                         f"earlier position (no sliding-window attention here)")
+    if isinstance(speculate, int) and not isinstance(speculate, bool):
+        widest = max(cfg.hidden_size, cfg.intermediate_size)
+        if batch * speculate * widest * 4 > x_bytes:
+            raise ValueError(f"speculate: batch * K * max(H, I) * 4 = {batch * speculate * widest * 4} > {x_bytes} "
+                             f"(GEMV_X_BYTES): the verify step's rows must fit the staging of the GEMVs and the moe "
+                             f"kernels")
 
 
 def dequantized_llama(model):
@@ -536,5 +622,5 @@ def llama_tenant(dtype: str = "fp32", seed: int = 0, small: bool = True, seq: in
     return llama_program(m, seq if small else 64, batch, dtype)
 
 
-__all__ = ["llama_config", "llama_model", "llama_program", "llama_decode_programs", "llama_tenant", "rope_tables",
+__all__ = ["mixtral_config", "mixtral_model", "llama_config", "llama_model", "llama_program", "llama_decode_programs", "llama_tenant", "rope_tables",
            "dequantized_llama", "kv_q8_roundtrip_cache", "adapted_llama"]

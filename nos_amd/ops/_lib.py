@@ -148,6 +148,13 @@ _SIGS = {
     "nos_gemv_q8_lora": [c_void_p, c_int, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                          c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
                          c_void_p, c_void_p, c_ll, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
+    # decode.hip: the mixture-of-experts block of a decode step (route, expert GLU, expert down)
+    "nos_moe_route": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int, c_int,
+                      c_int, c_void_p],
+    "nos_moe_glu": [c_void_p, c_int, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_float, c_void_p, c_int, c_int, c_int,
+                    c_int, c_int, c_void_p],
+    "nos_moe_down": [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                     c_int, c_int, c_int, c_int, c_void_p],
     "nos_attn_h3g_workspace": [c_int, c_int, c_int, c_int, c_int, c_int],
     # LayerNorm hand-off (gemm_f32h.hip): producer row statistics, LN in the consumer's A load
     "nos_gemm_f32h3_stats": [c_void_p, c_int, c_ll, c_void_p, c_float, c_void_p, c_int, c_ll, c_void_p, c_void_p,

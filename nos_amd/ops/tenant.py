@@ -1807,6 +1807,235 @@ def _glu_halves(y: torch.Tensor) -> torch.Tensor:
     return glu(y[..., :h], y[..., h:], "silu")
 
 
+# ------------------------------------------------------------------ mixture of experts
+MOE_MAX_EXPERTS = 64   # a lane per expert in the route kernel (decode.hip MOE_MAX_E)
+MOE_MAX_TOP_K = 8      # decode.hip MOE_MAX_K
+
+
+def _moe_x(x2, rms_eps, gamma, dtype):
+    """x' of the MoE kernels in ``dtype``: x, RMS-normalised and times ``gamma`` when ``rms_eps`` > 0."""
+    xf = x2.to(dtype)
+    if rms_eps:
+        xf = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + rms_eps)
+        if gamma is not None:
+            xf = xf * gamma.to(dtype)
+    return xf
+
+
+def _moe_slots(idx, E: int):
+    """Per slot of idx [rows, k]: (its expert lies in [0, E)?, the index clamped into it); no host read."""
+    e = idx.to(torch.long)
+    return (e >= 0) & (e < E), e.clamp(0, E - 1)
+
+
+def moe_route_ref(x2, Wr, k: int, rms_eps: float = 0.0, gamma=None, dtype: torch.dtype = torch.float32):
+    """:func:`moe_route` in ``dtype`` arithmetic: p = softmax(Wr x') over all E experts, the k largest
+    by k rounds of arg-max (a tie goes to the lower index) as idx [rows, k] i32 in descending order of
+    p, and w = p[idx] / sum(p[idx])."""
+    p = torch.softmax(_moe_x(x2, rms_eps, gamma, dtype) @ Wr.to(dtype).T, dim=-1)
+    cand, picks = p.clone(), []
+    for _ in range(int(k)):
+        i = cand.argmax(dim=-1, keepdim=True)   # the first maximal value: the lower index
+        picks.append(i)
+        cand.scatter_(1, i, -1.0)
+    idx = torch.cat(picks, dim=1)
+    ps = p.gather(1, idx)
+    tot = ps[:, 0].clone()
+    for s in range(1, int(k)):   # in slot order
+        tot = tot + ps[:, s]
+    return idx.to(torch.int32), ps / tot[:, None]
+
+
+def moe_glu_ref(x2, idx, W13, rms_eps: float = 0.0, gamma=None, dtype: torch.dtype = torch.float32):
+    """:func:`moe_glu` in ``dtype`` arithmetic: act [rows, k, I], ``act[m, s] = silu(W13[e][:I] x'[m]) *
+    (W13[e][I:] x'[m])`` for e = idx[m, s]; zeros for an e outside [0, E)."""
+    rows, k = idx.shape
+    I = W13.shape[1] // 2
+    ok, e = _moe_slots(idx, W13.shape[0])
+    xf = _moe_x(x2, rms_eps, gamma, dtype).repeat_interleave(k, dim=0)
+    gu = torch.bmm(W13.index_select(0, e.reshape(-1)).to(dtype), xf.unsqueeze(-1)).squeeze(-1)
+    act = (F.silu(gu[:, :I]) * gu[:, I:]).view(rows, k, I)
+    return torch.where(ok.unsqueeze(-1), act, torch.zeros_like(act))
+
+
+def moe_down_ref(act, idx, w, W2, res=None, dtype: torch.dtype = torch.float32):
+    """:func:`moe_down` in ``dtype`` arithmetic: ``y[m] = res[m] + sum_s w[m, s] * (W2[idx[m, s]] @ act[m, s])``,
+    the slots summed in the order 0 .. k - 1; a slot whose index is outside [0, E) contributes zero."""
+    rows, k, I = act.shape
+    ok, e = _moe_slots(idx, W2.shape[0])
+    d = torch.bmm(W2.index_select(0, e.reshape(-1)).to(dtype), act.to(dtype).reshape(rows * k, I, 1)).view(rows, k, -1)
+    d = torch.where(ok.unsqueeze(-1), w.to(dtype).unsqueeze(-1) * d, torch.zeros_like(d))
+    y = d[:, 0]
+    for s in range(1, k):
+        y = y + d[:, s]
+    return y if res is None else res.to(dtype).reshape(rows, -1) + y
+
+
+def moe_ref(x, Wr, W13, W2, k: int, dtype: torch.dtype | None = None):
+    """What ``moe(x, Wr, W13, W2; top_k=k)`` means (transformers' ``MixtralSparseMoeBlock``), in ``dtype``
+    arithmetic (default: x's): per row of x [..., H], p = softmax(Wr x) over the E experts, the k
+    largest (a tie: the lower index) renormalised to sum 1, and ``y = sum_s w_s W2[e_s] (silu(W13[e_s][:I]
+    x) * (W13[e_s][I:] x))`` in descending order of p.  Wr [E, H], W13 [E, 2I, H] (gate rows, then up
+    rows), W2 [E, H, I]."""
+    dt = dtype or x.dtype
+    x2 = x.reshape(-1, x.shape[-1])
+    idx, w = moe_route_ref(x2, Wr, k, dtype=dt)
+    y = moe_down_ref(moe_glu_ref(x2, idx, W13, dtype=dt), idx, w, W2, dtype=dt)
+    return y.view(x.shape)
+
+
+def _moe_refuse(what: str, **tensors) -> None:
+    """fp32, unit inner stride, 16-byte base and rows: what the MoE kernels load 16 bytes at a time."""
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} must be fp32, got {t.dtype}")
+        if not t.is_cuda:
+            raise ValueError(f"{what}: {name} must be on the GPU with x, it is on {t.device}")
+        if t.stride(-1) != 1 or any(s % 4 for s in t.stride()[:-1]) or t.data_ptr() % 16:
+            raise ValueError(f"{what}: {name} {tuple(t.shape)} with strides {t.stride()} at offset "
+                             f"{t.data_ptr() % 16} of a 16-byte line: unit inner stride, outer strides that are "
+                             f"multiples of 4 and a 16-byte aligned base required")
+
+
+def _moe_dims(what: str, rows: int, E: int, H: int, I: int, k: int) -> None:
+    if not (isinstance(k, int) and 1 <= k <= min(E, MOE_MAX_TOP_K)):
+        raise ValueError(f"{what}: top_k must be in [1, min(E, {MOE_MAX_TOP_K})] = [1, {min(E, MOE_MAX_TOP_K)}], got {k!r}")
+    if E > MOE_MAX_EXPERTS:
+        raise ValueError(f"{what}: E = {E} experts, at most {MOE_MAX_EXPERTS}")
+    if H % 4 or I % 4:
+        raise ValueError(f"{what}: H = {H} and I = {I} must be multiples of 4 (16-byte loads)")
+    if not 1 <= rows <= GEMV_MAX_ROWS:
+        raise ValueError(f"{what}: {rows} rows; the kernels take 1 .. {GEMV_MAX_ROWS} (GEMV_MAX_ROWS)")
+    if H * 4 > GEMV_X_BYTES or k * I * 4 > GEMV_X_BYTES:
+        raise ValueError(f"{what}: a row of H = {H} or k x I = {k} x {I} floats is over the {GEMV_X_BYTES} bytes "
+                         f"the kernels stage")
+
+
+def _moe_gamma(what: str, gamma, rms_eps: float, H: int) -> None:
+    if gamma is not None and (not rms_eps or gamma.dim() != 1 or gamma.shape[0] != H):
+        raise ValueError(f"{what}: gamma must be [{H}] and comes with rms_eps > 0 only")
+
+
+def _moe_idx(what: str, idx, rows: int, k: int | None = None) -> None:
+    if (idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != rows or not idx.is_contiguous()
+            or (k is not None and idx.shape[1] != k) or not idx.is_cuda):
+        raise ValueError(f"{what}: idx must be a contiguous i32 [{rows}, k] on the GPU, got {idx.dtype} "
+                         f"{tuple(idx.shape)} on {idx.device}")
+
+
+def moe_route(x: torch.Tensor, Wr: torch.Tensor, k: int, rms_eps: float = 0.0, gamma: torch.Tensor | None = None,
+              out: tuple | None = None):
+    """(idx [rows, k] i32, w [rows, k] fp32) of x [rows <= 8, H] fp32 and the router Wr [E <= 64, H]: the
+    k experts of each row in descending order of p = softmax(Wr x') and their renormalised weights
+    (decode.hip ``nos_moe_route``; x' is x under the RMSNorm prologue ``rms_eps`` > 0, ``gamma``).  A
+    tie goes to the lower index.  ``out``: contiguous (idx, w) destinations.  CPU tensors:
+    :func:`moe_route_ref`."""
+    if x.dim() != 2 or Wr.dim() != 2 or Wr.shape[1] != x.shape[1]:
+        raise ValueError(f"moe_route: x [rows, H] and Wr [E, H] required, got {tuple(x.shape)} and {tuple(Wr.shape)}")
+    rows, H = x.shape
+    _moe_gamma("moe_route", gamma, rms_eps, H)
+    if not x.is_cuda:
+        return moe_route_ref(x, Wr, k, rms_eps, gamma)
+    _moe_dims("moe_route", rows, Wr.shape[0], H, 4, k)
+    _moe_refuse("moe_route", x=x, Wr=Wr, gamma=gamma)
+    if out is not None:
+        idx, w = out
+        _moe_idx("moe_route", idx, rows, k)
+        if w.dtype != torch.float32 or tuple(w.shape) != (rows, k) or not w.is_contiguous() or not w.is_cuda:
+            raise ValueError(f"moe_route: out w must be a contiguous fp32 [{rows}, {k}] on the GPU, got {w.dtype} "
+                             f"{tuple(w.shape)} on {w.device}")
+    else:
+        idx = torch.empty((rows, k), dtype=torch.int32, device=x.device)
+        w = torch.empty((rows, k), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().nos_moe_route(x.data_ptr(), x.stride(0), Wr.data_ptr(), Wr.stride(0), _ptr(gamma),
+                                        float(rms_eps), idx.data_ptr(), w.data_ptr(), rows, Wr.shape[0], H, int(k),
+                                        _stream()), "nos_moe_route")
+    return idx, w
+
+
+def moe_glu(x: torch.Tensor, idx: torch.Tensor, W13: torch.Tensor, rms_eps: float = 0.0,
+            gamma: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """act [rows, k, I] fp32: ``silu(W13[e][:I] x'[m]) * (W13[e][I:] x'[m])`` for e = idx[m, s], of x
+    [rows <= 8, H] fp32 and W13 [E, 2I, H] (decode.hip ``nos_moe_glu``; x' as :func:`moe_route`).  The
+    kernel checks every index: a slot outside [0, E) reads no weight and is zeros.  ``out``: a
+    contiguous destination.  CPU tensors: :func:`moe_glu_ref`."""
+    if x.dim() != 2 or W13.dim() != 3 or W13.shape[2] != x.shape[1] or W13.shape[1] % 2 or idx.dim() != 2:
+        raise ValueError(f"moe_glu: x [rows, H], idx [rows, k] and W13 [E, 2I, H] required, got {tuple(x.shape)}, "
+                         f"{tuple(idx.shape)} and {tuple(W13.shape)}")
+    rows, H = x.shape
+    _moe_gamma("moe_glu", gamma, rms_eps, H)
+    if not x.is_cuda:
+        return moe_glu_ref(x, idx, W13, rms_eps, gamma)
+    E, I, k = W13.shape[0], W13.shape[1] // 2, idx.shape[1]
+    _moe_dims("moe_glu", rows, E, H, I, k)
+    _moe_idx("moe_glu", idx, rows)
+    _moe_refuse("moe_glu", x=x, W13=W13, gamma=gamma)
+    act = out if out is not None else torch.empty((rows, k, I), dtype=torch.float32, device=x.device)
+    if (act.dtype != torch.float32 or tuple(act.shape) != (rows, k, I) or not act.is_contiguous() or not act.is_cuda
+            or act.data_ptr() % 16):
+        raise ValueError(f"moe_glu: out must be a contiguous, 16-byte aligned fp32 [{rows}, {k}, {I}] on the GPU, got "
+                         f"{act.dtype} {tuple(act.shape)} on {act.device}")
+    _lib.check(_lib.lib().nos_moe_glu(x.data_ptr(), x.stride(0), idx.data_ptr(), W13.data_ptr(), W13.stride(0),
+                                      W13.stride(1), _ptr(gamma), float(rms_eps), act.data_ptr(), rows, E, H, I, k,
+                                      _stream()), "nos_moe_glu")
+    return act
+
+
+def moe_down(act: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, W2: torch.Tensor,
+             res: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """y [rows, H] fp32 = ``res + sum_s w[m, s] * (W2[idx[m, s]] @ act[m, s])`` of act [rows <= 8, k, I], w
+    [rows, k] and W2 [E, H, I] (decode.hip ``nos_moe_down``), the slots summed in the order 0 .. k - 1
+    without atomics: bit-reproducible.  A slot whose index is outside [0, E) contributes zero.  ``out``:
+    a [rows, H] destination with unit inner stride.  CPU tensors: :func:`moe_down_ref`."""
+    if (act.dim() != 3 or W2.dim() != 3 or W2.shape[2] != act.shape[2] or tuple(w.shape) != tuple(act.shape[:2])
+            or tuple(idx.shape) != tuple(act.shape[:2])):
+        raise ValueError(f"moe_down: act [rows, k, I], idx and w [rows, k] and W2 [E, H, I] required, got "
+                         f"{tuple(act.shape)}, {tuple(idx.shape)}, {tuple(w.shape)} and {tuple(W2.shape)}")
+    rows, k, I = act.shape
+    E, H = W2.shape[:2]
+    if res is not None and tuple(res.shape) != (rows, H):
+        raise ValueError(f"moe_down: res must be [{rows}, {H}], got {tuple(res.shape)}")
+    if not act.is_cuda:
+        y = moe_down_ref(act, idx, w, W2, res)
+        return y if out is None else out.copy_(y)
+    _moe_dims("moe_down", rows, E, H, I, k)
+    _moe_idx("moe_down", idx, rows, k)
+    if not act.is_contiguous() or not w.is_contiguous() or w.dtype != torch.float32 or not w.is_cuda:
+        raise ValueError(f"moe_down: act and w must be contiguous and w fp32 on the GPU, got w {w.dtype} on {w.device}")
+    _moe_refuse("moe_down", act=act, W2=W2)
+    y = out if out is not None else torch.empty((rows, H), dtype=torch.float32, device=act.device)
+    for name, t in (("res", res), ("out", y)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_cuda or t.stride(-1) != 1 or tuple(t.shape) != (rows, H)
+                              or t.stride(0) < H):
+            raise ValueError(f"moe_down: {name} must be an fp32 [{rows}, {H}] on the GPU with unit inner stride, got "
+                             f"{t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
+    _lib.check(_lib.lib().nos_moe_down(act.data_ptr(), idx.data_ptr(), w.data_ptr(), W2.data_ptr(), W2.stride(0),
+                                       W2.stride(1), _ptr(res), res.stride(0) if res is not None else 0, y.data_ptr(),
+                                       y.stride(0), rows, E, H, I, k, _stream()), "nos_moe_down")
+    return y
+
+
+def moe(x: torch.Tensor, Wr: torch.Tensor, W13: torch.Tensor, W2: torch.Tensor, k: int) -> torch.Tensor:
+    """``moe`` (:func:`moe_ref`) of fp32 x [..., H] on the device for steps of more rows than the kernels
+    take (a prefill): PyTorch ops, DENSE over the experts -- every expert's MLP on every row, times a
+    gate that is the renormalised p for the k chosen experts (scattered from the arg-max rounds) and 0
+    elsewhere; E / k times the useful FLOPs, stream-ordered, no host read of a routing value.  CPU
+    tensors: the reference."""
+    if not x.is_cuda:
+        return moe_ref(x, Wr, W13, W2, k)
+    x2 = x.reshape(-1, x.shape[-1])
+    idx, w = moe_route_ref(x2, Wr, k)
+    gates = torch.zeros((x2.shape[0], Wr.shape[0]), dtype=x2.dtype, device=x.device).scatter_(1, idx.long(), w)
+    I = W13.shape[1] // 2
+    y = torch.zeros_like(x2)
+    for e in range(Wr.shape[0]):
+        gu = x2 @ W13[e].T
+        y = y + gates[:, e:e + 1] * ((F.silu(gu[:, :I]) * gu[:, I:]) @ W2[e].T)
+    return y.view(x.shape)
+
+
 def set_attention_h3g_kvsplit(n: int) -> None:
     """Key splits of :func:`sdpa` (0 = auto: fill the CU slots)."""
     _lib.check(_lib.lib().nos_attn_h3g_set_kvsplit(int(n)), "nos_attn_h3g_set_kvsplit")
@@ -1815,7 +2044,8 @@ def set_attention_h3g_kvsplit(n: int) -> None:
 __all__ = ["glu", "kv_write", "rotary_at", "sdpa_cache", "pos_update", "argmax", "sample", "sample_row_ref",
            "sampling_ctl", "philox4x32", "gemv", "gemv_ok", "gemv_partials", "gemv_q8", "gemv_q8_ok", "gemv_q8_partials",
            "dequant_q8", "linear_q8", "linear_q8_ref", "lora", "lora_ref", "lora_shrink", "lora_shrink_ref", "lora_expand_ref", "linear_lora",
-           "LORA_MAX_RANK",
+           "LORA_MAX_RANK", "moe", "moe_ref", "moe_route", "moe_glu", "moe_down", "moe_route_ref", "moe_glu_ref",
+           "moe_down_ref", "MOE_MAX_EXPERTS", "MOE_MAX_TOP_K",
            "DecodePartials", "conv2d", "matmul", "sdpa", "linear_rms", "embedding", "rmsnorm", "softmax", "rotary", "conv2d_ref",
            "sdpa_ref", "rope_ref", "rmsnorm_ref", "linear_rms_ref", "set_attention_h3g_kvsplit", "EPI_BIAS_ROW",
            "sdpa_lse", "sdpa_bwd", "sdpa_lse_ref", "sdpa_bwd_ref", "sdpa_bwd_workspace_bytes"]

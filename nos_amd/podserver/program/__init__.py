@@ -63,7 +63,10 @@ written in place by its GEMM (``cat_buffer``), fp16-plane and LayerNorm
 hand-offs between h3 kernels (``cat_stats``: layer 0's statistics from the
 patch GEMM plus build-time constant rows), conv weight preparation, and for
 adapter tenants ``add(linear | linear_q8, lora)`` at decode rows as the GEMV
-with the adapter epilogue plus one ``lora_shrink`` step (``_fuse_lora``).
+with the adapter epilogue plus one ``lora_shrink`` step (``_fuse_lora``), and
+a ``moe`` at decode rows as ``moe_route`` / ``moe_glu`` / ``moe_down`` with the
+``rmsnorm`` in front as their prologue and the ``add`` behind as the residual
+(``_fuse_moe``).
 
 The compiled program is a callable ``(x) -> tuple(outputs)``, captured into a
 HIP graph by the server exactly like a built-in model.  :meth:`Program.reference`

@@ -119,6 +119,12 @@ class Builder:
         request's ``"adapter"`` field and every ``lora`` node reads as its ``sel``."""
         return self.state(name, [batch], "i32")
 
+    def moe(self, x: str, router: str, gate_up: str, down: str, top_k: int, out: str | None = None) -> str:
+        """A sparse mixture-of-experts MLP over x [..., H]: ``router`` [E, H], ``gate_up`` [E, 2I, H] (gate rows,
+        then up rows) and ``down`` [E, H, I] are fp32 params; each row takes its ``top_k`` experts
+        (``ops.tenant.moe_ref``)."""
+        return self.op("moe", x, router, gate_up, down, out=out, top_k=int(top_k))
+
     def op(self, op: str, *inputs: str, out: str | None = None, **attrs) -> str:
         self._n += 1
         out = out or f"%{self._n}"

@@ -70,6 +70,7 @@ class Lowered:
             if "blockdiag" not in skip:
                 steps = self._merge_blockdiag_linears(steps)
             steps = self._fuse_lora(steps)
+            steps = self._fuse_moe(steps)
             steps = self._fold_layernorm(steps)
             steps = self._fold_rmsnorm(steps)
             steps = self._fuse_epilogues(steps)
@@ -561,7 +562,7 @@ class Lowered:
         output dim ``d``, as (input index, input dim); None: not row-wise in d."""
         if p.kind in UNARY or p.kind == "cast":
             return [(0, d)]
-        if p.kind in ("linear", "linear_q8", "layernorm", "rmsnorm"):
+        if p.kind in ("linear", "linear_q8", "layernorm", "rmsnorm", "moe"):   # moe: each row routes for itself
             return [(0, d)] if len(self._shape(p.inputs[0])) == r else None
         if p.kind in BINARY:
             plan = []
@@ -888,6 +889,75 @@ class Lowered:
             out.append(s)
         self.outputs = [rename.get(o, o) for o in self.outputs]   # an output that was the add
         return self._reorder(out)
+
+    def _fuse_moe(self, steps: list[_Step]) -> list[_Step]:
+        """GPU, decode rows (at most ``GEMV_MAX_ROWS``, within the GEMVs' 64 KiB of x): a ``moe`` becomes the
+        three launches of decode.hip -- ``moe_route`` (its value: the pair (idx, w)), ``moe_glu`` (act) and
+        ``moe_down`` (y).  An ``rmsnorm`` in front whose only reader is the moe becomes the prologue of
+        route and glu (the statistic in the kernels, gamma as a pointer: no expert weight is copied or
+        folded), an ``add(moe, h)`` after it ``moe_down``'s residual.  More rows (a prefill), or the CPU:
+        the ``moe`` step stays and runs as PyTorch ops on the device."""
+        from ...ops.tenant import GEMV_MAX_ROWS, GEMV_X_BYTES
+
+        st = self.stats
+        st["moe_blocks"] = sum(1 for s in steps if s.kind == "moe")
+        st["moe_launches"] = st["moe_rms_prologue"] = st["moe_residual_fused"] = 0
+        if not self.gpu or not st["moe_blocks"]:
+            return steps
+        uses = self._consumers(steps, self.outputs)
+        by_out = {s.output: s for s in steps}
+        by_in: dict[str, list[_Step]] = {}
+        for s in steps:
+            for i in s.inputs:
+                by_in.setdefault(i, []).append(s)
+        drop: set[int] = set()
+        rename: dict[str, str] = {}
+        out: list[_Step] = []
+        for s in steps:
+            if s.kind != "moe":
+                out.append(s)
+                continue
+            x, wr, w13, w2 = s.inputs
+            xs, k = tuple(self._shape(x)), int(s.attrs["top_k"])
+            rows, H, I = math.prod(xs[:-1]), xs[-1], self._shape(w13)[1] // 2
+            if (rows > GEMV_MAX_ROWS or H * 4 > GEMV_X_BYTES or k * I * 4 > GEMV_X_BYTES
+                    or not all(i in self.consts for i in (wr, w13, w2))):
+                out.append(s)
+                continue
+            pro: dict = {}
+            gam: list[str] = []
+            rn = by_out.get(x)
+            if (rn is not None and rn.kind == "rmsnorm" and uses.get(rn.output) == 1 and rn.inputs[1] in self.consts
+                    and self._dtype(rn.inputs[0]) == "fp32"):
+                x, gam, pro = rn.inputs[0], [rn.inputs[1]], {"eps": rn.attrs.get("eps", 1e-5), "gamma": True}
+                drop.add(id(rn))
+                st["moe_rms_prologue"] += 1
+            down = {"top_k": k}
+            res: list[str] = []
+            ad = by_in.get(s.output, [None])[0]
+            if (uses.get(s.output) == 1 and ad is not None and ad.kind == "add" and self._dtype(ad.output) == "fp32"
+                    and ad.inputs[0] != ad.inputs[1]):
+                other = ad.inputs[1] if ad.inputs[0] == s.output else ad.inputs[0]
+                if tuple(self._shape(other)) == xs == tuple(self._shape(ad.output)) and self._dtype(other) == "fp32":
+                    res, down = [other], {**down, "residual": True}
+                    rename[ad.output] = s.output
+                    drop.add(id(ad))
+                    st["moe_residual_fused"] += 1
+            rt, act = s.output + "::route", s.output + "::act"
+            self._new_shapes[rt], self._new_dtypes[rt] = (rows, 2 * k), "i32"
+            self._new_shapes[act], self._new_dtypes[act] = (rows, k, I), "fp32"
+            out.append(_Step("moe_route", [x, wr] + gam, rt, {"top_k": k, **pro}))
+            out.append(_Step("moe_glu", [x, rt, w13] + gam, act, dict(pro)))
+            out.append(_Step("moe_down", [act, rt, w2] + res, s.output, down))
+            st["moe_launches"] += 3
+        kept = []
+        for s in out:
+            if id(s) in drop:
+                continue
+            s.inputs = [rename.get(i, i) for i in s.inputs]
+            kept.append(s)
+        self.outputs = [rename.get(o, o) for o in self.outputs]
+        return self._reorder(kept)
 
     def _shrink_of(self, lin: _Step, by_out: dict) -> _Step | None:
         """The ``lora_shrink`` step of a linear with the adapter epilogue (None: a plain linear)."""

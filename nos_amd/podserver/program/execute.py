@@ -33,6 +33,18 @@ class CompiledProgram(Lowered):
                                   rms_eps=float(s.attrs.get("eps", 0.0)), gamma=a[3] if s.attrs.get("gamma") else None)
             elif k == "lora":   # more rows than the GEMVs take (a prefill): PyTorch ops, sel read on the device
                 y = T.lora(a[0], a[1], a[2], a[3])
+            elif k == "moe_route":   # inputs: x, Wr, [gamma]; its value is the pair (idx, w)
+                y = T.moe_route(_rows(a[0]).view(-1, a[0].shape[-1]), a[1], int(s.attrs["top_k"]),
+                                rms_eps=float(s.attrs.get("eps", 0.0)), gamma=a[2] if s.attrs.get("gamma") else None)
+            elif k == "moe_glu":   # inputs: x, (idx, w), W13, [gamma]
+                y = T.moe_glu(_rows(a[0]).view(-1, a[0].shape[-1]), a[1][0], a[2], rms_eps=float(s.attrs.get("eps", 0.0)),
+                              gamma=a[3] if s.attrs.get("gamma") else None)
+            elif k == "moe_down":   # inputs: act, (idx, w), W2, [residual]
+                shp = self._shape(s.output)
+                res = _rows(a[3]).view(-1, shp[-1]) if s.attrs.get("residual") else None
+                y = T.moe_down(a[0], a[1][0], a[1][1], a[2], res=res).view(shp)
+            elif k == "moe":   # more rows than the kernels take (a prefill): PyTorch ops, no host read of the routing
+                y = T.moe(a[0], a[1], a[2], a[3], int(s.attrs["top_k"]))
             elif k == "linear" and s.attrs.get("x_partials"):   # x = the decode attention's split partials
                 res = a.pop() if s.attrs.get("residual") else None
                 y = T.gemv_partials(a[0], a[1], a[2] if len(a) > 2 else None, act=s.attrs.get("act"),

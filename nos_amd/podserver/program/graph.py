@@ -52,6 +52,16 @@ def _workspace(node: Node, ins: list[Value], out: Value, f32_math: str) -> int:
         if b * s <= 8:
             return b * s * r * 4
         return b * (r * k + n * r) * 4 + b * s * r * 4 + 2 * out.numel * 4
+    if op == "moe":
+        # decode rows: idx and w [rows, k] and act [rows, k, I] between the three launches; more rows (a
+        # prefill) run dense over the experts: the gates [rows, E] and, per expert, the merged product
+        # [rows, 2I], its activation [rows, I] and the down product and running sum [rows, H] (the expert
+        # weights themselves are params: charged once, never copied)
+        h = ins[0].shape[-1]
+        rows, (e, i2, _), k = ins[0].numel // h, ins[2].shape, node.attrs["top_k"]
+        if rows <= 8:
+            return rows * k * (8 + i2 // 2 * 4)
+        return rows * (3 * e + 2 * k) * 4 + rows * (i2 + i2 // 2 + 3 * h) * 4
     if op == "matmul":
         k = ins[0].shape[-1]
         kp = -(-k // 32) * 32

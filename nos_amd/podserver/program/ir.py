@@ -145,13 +145,18 @@ LORA_MAX_RANK = 64           # the stacked rank R of one lora node (the GEMV epi
 STATE_OPS = STATE_OPS + ("lora",)
 STATE_DTYPES = ("fp32", "bf16", "i32", "i8")
 MAX_STATE = 1024
-OPS = OPS + STATE_OPS
+# mixture of experts (a Mixtral-class tenant): moe(x, Wr, W13, W2; top_k) is a sparse MoE MLP whose expert
+# weights are chosen per row by a value computed on the device (ops.tenant.moe_ref)
+MOE_MAX_EXPERTS = 64         # a lane per expert in the route kernel
+MOE_MAX_TOP_K = 8
+OPS = OPS + STATE_OPS + ("moe",)
 # linear_q8: folding it would materialise the fp32 weight the format exists to avoid
-NEVER_FOLD = ("attention", "sdpa", "linear_q8", *STATE_OPS)
+NEVER_FOLD = ("attention", "sdpa", "linear_q8", "moe", *STATE_OPS)
 # step kinds that run a gfx950 kernel of libnos_hip.so (CompiledProgram.stats["kernels"])
 NATIVE_KINDS = ("linear", "linear_ln", "linear_rms", "ln_qkv_attention", "attention", "layernorm", "conv2d", "matmul",
                 "softmax", "embedding", "rmsnorm", "rotary", "sdpa", "patches", "unary", "kv_write", "sdpa_cache",
-                "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu", "linear_q8", *STOP_OPS, "stop_step", *SPEC_OPS, "spec_step", "lora_shrink")
+                "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu", "linear_q8", *STOP_OPS, "stop_step", *SPEC_OPS, "spec_step", "lora_shrink",
+                "moe_route", "moe_glu", "moe_down")
 # the steps a speculating tenant's verify program closes with (CompiledProgram.stats["spec_launches"]);
 # spec_step: spec_accept / hist_write / pos_advance / spec_draft fused into one launch
 SPEC_KINDS = (*SPEC_OPS, "spec_step")

@@ -6,7 +6,7 @@ from __future__ import annotations
 import math
 
 from .graph import Program
-from .ir import (FLOAT_DTYPES, FORMAT, LORA_MAX_RANK, MAX_NUMEL, MAX_PARAMS, MAX_NODES, MAX_RANK, MAX_STATE,
+from .ir import (FLOAT_DTYPES, FORMAT, LORA_MAX_RANK, MOE_MAX_EXPERTS, MOE_MAX_TOP_K, MAX_NUMEL, MAX_PARAMS, MAX_NODES, MAX_RANK, MAX_STATE,
                  MAX_VARIANTS, OPS, PARAM_DTYPES, SPEC_CTL_WORDS, SPEC_MAX_K, SPEC_MIN_K, STATE_DTYPES, STATE_WRITERS, STOP_CTL_WORDS, ACTS,
                  BINARY, INTERP_MODES, UNARY, WIRE_DTYPES, Node, ProgramError, Value, _broadcast, _eps, _int, _name,
                  _pair, _req, _shape)
@@ -490,6 +490,31 @@ def _infer(node: Node, ins: list[Value], gpu: bool) -> tuple[tuple[int, ...], st
                  f"{what}: the adapter kernels take a rank R <= {LORA_MAX_RANK} with R % 4 == 0 and K % 4 == 0, got "
                  f"R = {A.shape[1]}, K = {x.shape[2]}")
         return (x.shape[0], x.shape[1], B.shape[1]), "fp32"
+    if op == "moe":
+        # a sparse mixture-of-experts MLP (transformers' MixtralSparseMoeBlock; ops.tenant.moe_ref): per row the
+        # router's softmax over E experts, the top_k largest renormalised, and their SwiGLU MLPs weighted
+        only("top_k")
+        arity(4, 4)
+        x, Wr, W13, W2 = ins
+        _req(x.dtype == "fp32" and len(x.shape) >= 2,
+             f"{what}: x must be fp32 [..., H] (a bf16 x is not taken), got {x.dtype} {list(x.shape)}")
+        _req(all(w.kind == "param" and w.dtype == "fp32" for w in (Wr, W13, W2)),
+             f"{what}: Wr, W13 and W2 must be fp32 params (the weights are chosen on the device, never computed), got "
+             + ", ".join(f"{w.kind} {w.dtype} {w.name!r}" for w in (Wr, W13, W2)))
+        H = x.shape[-1]
+        _req(len(Wr.shape) == 2 and len(W13.shape) == 3 and len(W2.shape) == 3 and W13.shape[1] % 2 == 0
+             and Wr.shape == (W13.shape[0], H) and W13.shape[2] == H
+             and W2.shape == (W13.shape[0], H, W13.shape[1] // 2),
+             f"{what}: the weights' shapes must match: Wr [E, H], W13 [E, 2I, H] and W2 [E, H, I] with H = {H}, got "
+             f"{list(Wr.shape)}, {list(W13.shape)} and {list(W2.shape)}")
+        E, I = Wr.shape[0], W13.shape[1] // 2
+        _req(E <= MOE_MAX_EXPERTS, f"{what}: E = {E} experts; E <= {MOE_MAX_EXPERTS} required")
+        k = _int(a.get("top_k"), f"{what}: top_k", 1)
+        _req(k <= min(E, MOE_MAX_TOP_K), f"{what}: 1 <= top_k <= min(E, {MOE_MAX_TOP_K}) = {min(E, MOE_MAX_TOP_K)} "
+             f"required, got {k}")
+        _req(H % 4 == 0 and I % 4 == 0, f"{what}: H % 4 == 0 and I % 4 == 0 required (16-byte loads), got H = {H}, "
+             f"I = {I}")
+        return x.shape, "fp32"
     raise ProgramError(f"{what}: op {op!r} is not one the pod server runs (whitelist: {' '.join(OPS)})")
 
 

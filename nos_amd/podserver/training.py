@@ -54,6 +54,9 @@ def parse_train_spec(spec, prog: Program) -> dict:
     """Validate a register request's ``train`` spec against the program;
     returns it normalised, with the target's shape and dtype."""
     _req(isinstance(spec, dict), "train must be an object")
+    _req(not any(n.op == "moe" for n in prog.nodes),
+         "a program holding a moe node cannot be a training tenant: its routing (top-k, arg-max) has no trained "
+         "form here (no auxiliary load-balancing loss, no gradient through the selection); serve it for inference")
     extra = set(spec) - SPEC_KEYS
     _req(not extra, f"unknown train keys {sorted(extra)}")
     loss = spec.get("loss", "mse")
