@@ -22,6 +22,8 @@
 //  * nos_kv_write_q8 / nos_attn_decode_q8 -- the two over int8 caches (D int8 values
 //    and one fp32 scale per row): the write quantizes the rows, the attention
 //    dequantizes them as it stages a split and is the fp32 cache's code after that;
+//  * nos_kv_write_ring(_q8) / nos_attn_decode_ring(_q8) -- the same over ring caches of C slots for a
+//    sliding window W (kv_ring.h): position p in slot p % C, query p attends max(0, p - W + 1) .. p;
 //  * nos_pos_update -- pos += n / pos = n;
 //  * nos_argmax -- greedy next tokens, one wave per row;
 //  * nos_sample -- sampled next tokens (temperature, top-k, top-p, seed read
@@ -41,6 +43,7 @@
 
 #include "common.h"
 #include "epilogue.h"
+#include "kv_ring.h"
 
 namespace {
 
@@ -133,10 +136,13 @@ struct KvPair {
   void* cache2;
 };
 
-__global__ __launch_bounds__(256) void kv_write_kernel(const void* __restrict__ x, int xbf, int ldx, long long bsx,
-                                                       void* __restrict__ cache, int cbf, const int* __restrict__ pos,
-                                                       const float* __restrict__ cs, const float* __restrict__ sn,
-                                                       int R, int B, int S, int H, int D, int L, KvPair v2) {
+// RING: the cache is a ring of L slots (kv_ring.h): position p goes to slot p % L, positions outside
+// [0, limit) are dropped; the rotary tables are read at the position, not the slot
+template <bool RING>
+__device__ __forceinline__ void kv_write_rows(const void* __restrict__ x, int xbf, int ldx, long long bsx,
+                                              void* __restrict__ cache, int cbf, const int* __restrict__ pos,
+                                              const float* __restrict__ cs, const float* __restrict__ sn, int R,
+                                              int B, int S, int H, int D, int L, KvPair v2, int limit) {
   if (blockIdx.y == 1) {  // the V half: its own rows, no rotation
     x = v2.x2;
     ldx = v2.ldx2;
@@ -153,7 +159,13 @@ __global__ __launch_bounds__(256) void kv_write_kernel(const void* __restrict__ 
   r /= H;
   const int s = (int)(r % S), b = (int)(r / S);
   const int p = pos[b] + s;
-  if (p < 0 || p >= L) return;  // past the cache: dropped (the server reports the overflow)
+  int row = p;  // the cache row of position p
+  if constexpr (RING) {
+    row = nos::ring_slot(p, L, limit);
+    if (row < 0) return;  // outside [0, limit): dropped before any address is formed from it
+  } else {
+    if (p < 0 || p >= L) return;  // past the cache: dropped (the server reports the overflow)
+  }
   const long long xo = b * bsx + (long long)s * ldx + (long long)h * D;
   float x0 = ldf(x, xo + d, xbf), x1 = ldf(x, xo + d + hd, xbf);
   if (cs != nullptr) {
@@ -163,9 +175,24 @@ __global__ __launch_bounds__(256) void kv_write_kernel(const void* __restrict__ 
     x0 = y0;
     x1 = y1;
   }
-  const long long co = (((long long)b * L + p) * H + h) * D;
+  const long long co = (((long long)b * L + row) * H + h) * D;
   stf(cache, co + d, x0, cbf);
   stf(cache, co + d + hd, x1, cbf);
+}
+
+__global__ __launch_bounds__(256) void kv_write_kernel(const void* __restrict__ x, int xbf, int ldx, long long bsx,
+                                                       void* __restrict__ cache, int cbf, const int* __restrict__ pos,
+                                                       const float* __restrict__ cs, const float* __restrict__ sn,
+                                                       int R, int B, int S, int H, int D, int L, KvPair v2) {
+  kv_write_rows<false>(x, xbf, ldx, bsx, cache, cbf, pos, cs, sn, R, B, S, H, D, L, v2, 0);
+}
+
+__global__ __launch_bounds__(256) void kv_write_ring_kernel(const void* __restrict__ x, int xbf, int ldx,
+                                                            long long bsx, void* __restrict__ cache, int cbf,
+                                                            const int* __restrict__ pos, const float* __restrict__ cs,
+                                                            const float* __restrict__ sn, int R, int B, int S, int H,
+                                                            int D, int C, KvPair v2, int limit) {
+  kv_write_rows<true>(x, xbf, ldx, bsx, cache, cbf, pos, cs, sn, R, B, S, H, D, C, v2, limit);
 }
 
 // kv_write into an int8 cache: one wave per (b, s, h) row -- rotate (K), the row's scale across the
@@ -180,12 +207,12 @@ struct KvPairQ8 {
   float* deq2;
 };
 
-template <int D>
-__global__ __launch_bounds__(256) void kv_write_q8_kernel(const float* __restrict__ x, int ldx, long long bsx,
-                                                          signed char* __restrict__ cache, float* __restrict__ scales,
-                                                          float* __restrict__ deq, const int* __restrict__ pos,
-                                                          const float* __restrict__ cs, const float* __restrict__ sn,
-                                                          int R, int B, int S, int H, int L, KvPairQ8 v2) {
+template <int D, bool RING>
+__device__ __forceinline__ void kv_write_q8_rows(const float* __restrict__ x, int ldx, long long bsx,
+                                                 signed char* __restrict__ cache, float* __restrict__ scales,
+                                                 float* __restrict__ deq, const int* __restrict__ pos,
+                                                 const float* __restrict__ cs, const float* __restrict__ sn, int R,
+                                                 int B, int S, int H, int L, KvPairQ8 v2, int limit) {
   if (blockIdx.y == 1) {  // the V half: its own rows, no rotation
     x = v2.x2;
     ldx = v2.ldx2;
@@ -203,7 +230,13 @@ __global__ __launch_bounds__(256) void kv_write_q8_kernel(const float* __restric
   r /= H;
   const int s = (int)(r % S), b = (int)(r / S);
   const int p = pos[b] + s;
-  if (p < 0 || p >= L) return;  // past the cache: dropped (the whole wave)
+  int crow = p;  // the cache row of position p
+  if constexpr (RING) {
+    crow = nos::ring_slot(p, L, limit);
+    if (crow < 0) return;  // outside [0, limit): dropped (the whole wave)
+  } else {
+    if (p < 0 || p >= L) return;  // past the cache: dropped (the whole wave)
+  }
   float x0 = 0.f, x1 = 0.f;
   if (lane < hd) {
     const long long xo = b * bsx + (long long)s * ldx + (long long)h * D;
@@ -219,13 +252,30 @@ __global__ __launch_bounds__(256) void kv_write_q8_kernel(const float* __restric
   }
   int q0, q1;
   const float sc = q8_row(x0, x1, q0, q1);
-  const long long row = ((long long)b * L + p) * H + h;
+  const long long row = ((long long)b * L + crow) * H + h;
   q8_row_store<D>(cache + row * D, scales + row, sc, q0, q1, lane);
   if (deq != nullptr && lane < hd) {
     const long long yo = (((long long)b * S + s) * H + h) * D;
     deq[yo + lane] = (float)q0 * sc;
     deq[yo + lane + hd] = (float)q1 * sc;
   }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void kv_write_q8_kernel(const float* __restrict__ x, int ldx, long long bsx,
+                                                          signed char* __restrict__ cache, float* __restrict__ scales,
+                                                          float* __restrict__ deq, const int* __restrict__ pos,
+                                                          const float* __restrict__ cs, const float* __restrict__ sn,
+                                                          int R, int B, int S, int H, int L, KvPairQ8 v2) {
+  kv_write_q8_rows<D, false>(x, ldx, bsx, cache, scales, deq, pos, cs, sn, R, B, S, H, L, v2, 0);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void kv_write_q8_ring_kernel(
+    const float* __restrict__ x, int ldx, long long bsx, signed char* __restrict__ cache, float* __restrict__ scales,
+    float* __restrict__ deq, const int* __restrict__ pos, const float* __restrict__ cs, const float* __restrict__ sn,
+    int R, int B, int S, int H, int C, KvPairQ8 v2, int limit) {
+  kv_write_q8_rows<D, true>(x, ldx, bsx, cache, scales, deq, pos, cs, sn, R, B, S, H, C, v2, limit);
 }
 
 __global__ __launch_bounds__(256) void rotary_pos_kernel(const void* __restrict__ x, int ldx, long long bsx,
@@ -325,15 +375,30 @@ struct CacheScales<2> {
   float* v;
 };
 
+// a sliding window over ring caches (RING): a kernel argument only of those instantiations
+template <bool RING>
+struct RingArgs {};
+template <>
+struct RingArgs<true> {
+  int W;      // the window: the query at p attends the positions max(0, p - W + 1) .. p
+  int limit;  // positions >= limit are not stored (the rows of the rotary tables)
+};
+
 // CBF: the cache kind -- 0 fp32, 1 bf16, 2 int8 rows with a scale each (dequantized as they are staged
 // into the fp32 LDS tile: a quarter of the fp32 cache's bytes from HBM, the same arithmetic after it)
-template <int D, int CBF>
+// RING: the caches are rings of L = C slots (kv_ring.h) and the queries attend a window.  A split is a
+// range of slots; the position a slot holds follows from the step's last position pmax = pos[b] +
+// Sq_total - 1, the same in every launch of the step.  nk counts the split's slots up to the last one
+// some row of the launch sees; the slots below it that no row sees are staged as zeros without a load
+// (stale or never written: they must not reach P V as 0 x garbage).  With nothing hidden and nothing
+// wrapped the split's arithmetic is the plain kernel's, in its order.
+template <int D, int CBF, bool RING = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(
     const void* __restrict__ q, int qbf, int ldq, long long bsq, const void* __restrict__ kc,
     const void* __restrict__ vc, int /*cbf = CBF*/, const int* __restrict__ pos, const float* __restrict__ cs,
     const float* __restrict__ sn, int Rtab, float* __restrict__ ws, int B, int H, int Hkv, int Sq, int q0, int L,
     int NS, float scale, Fresh fr, int* __restrict__ sync, void* __restrict__ o, int obf, int Sq_total,
-    CacheScales<CBF> csc) {
+    CacheScales<CBF> csc, RingArgs<RING> rg) {
   constexpr int cbf = CBF;   // the cache dtype fixed at compile time: no per-load dtype branch
   constexpr int DP = D + 4;  // padded LDS row (16-byte reads of consecutive rows hit distinct banks)
   __shared__ __attribute__((aligned(16))) float qs[MAXR * D];
@@ -350,14 +415,45 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   const int kvh = bk % Hkv, b = bk / Hkv;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int p0 = pos[b] + q0;                              // position of query row qi = 0 of this launch
-  const int kend = min(p0 + Sq, L);                        // keys 0 .. kend - 1 are visible to some row
-  const int k0 = split * KC, nk = min(KC, kend - k0);
+  const int k0 = split * KC;
+  // RING: a counter outside [0, limit) is bad (nothing written, every split dead); the positions the
+  // rows of this launch see are vlo .. vhi, and slot s holds one of them iff seen(s)
+  bool good = true;
+  int pmax = 0, vlo = 0, vhi = -1, nk;
+  if constexpr (RING) {
+    good = pos[b] >= 0 && pos[b] < rg.limit;
+    pmax = pos[b] + Sq_total - 1;
+    vhi = p0 + Sq - 1;
+    vlo = nos::ring_oldest(p0, pmax, L, rg.W);
+    nk = good ? nos::ring_split_rows(k0, min(KC, L - k0), vlo, vhi, L) : 0;
+  } else {
+    const int kend = min(p0 + Sq, L);                      // keys 0 .. kend - 1 are visible to some row
+    nk = min(KC, kend - k0);
+  }
+  auto seen = [&](int s) {
+    const int a = nos::ring_position(s, pmax, L);
+    return a >= vlo && a <= vhi;
+  };
+  // row j of the split is loaded (else staged as zeros)
+  auto has = [&](int j) {
+    if constexpr (RING)
+      return j < nk && seen(k0 + j);
+    else
+      return j < nk;
+  };
+  // the cache row of the step's fresh row t (RING: -1 for a dropped row; else the caller drops rows >= L)
+  auto fresh_slot = [&](int t) {
+    if constexpr (RING)
+      return nos::ring_slot(pos[b] + t, L, rg.limit);
+    else
+      return pos[b] + t;
+  };
   float* const out = ws + (long long)blockIdx.x * R * (D + 2);
   const long long cstride = (long long)Hkv * D;  // cache row (token) stride
   // the first launch of a step writes the step's fresh K (rotated) / V rows that fall in
   // this split's key range into the caches -- every split, empty or not, so a later
   // launch (query rows q0 > 0) and the next step read them from the cache
-  const bool fresh = fr.n > 0 && q0 == 0 && pos[b] >= 0;
+  const bool fresh = fr.n > 0 && q0 == 0 && pos[b] >= 0 && good;
   auto fresh_row = [&](int t, int d, bool isk, float& x0, float& x1) {
     const void* src = isk ? fr.k : fr.v;
     const long long o = (long long)b * (isk ? fr.bsk : fr.bsv) + (long long)t * (isk ? fr.ldk : fr.ldv) +
@@ -397,31 +493,31 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   if (live) {
     if constexpr (CBF == 2) {
       const int j = tid & (KC - 1);
-      if (j < nk) rs = (tid < KC ? csc.k : csc.v)[((long long)b * L + k0 + j) * Hkv + kvh];
+      if (has(j)) rs = (tid < KC ? csc.k : csc.v)[((long long)b * L + k0 + j) * Hkv + kvh];
     }
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
       const int e = tid + 256 * u, j = e / (D / EPP), d4 = (e % (D / EPP)) * EPP;
       if constexpr (CBF == 2)
-        kr[u] = j < nk ? *reinterpret_cast<const uint4*>(static_cast<const signed char*>(kc) + cbase + j * cstride + d4)
+        kr[u] = has(j) ? *reinterpret_cast<const uint4*>(static_cast<const signed char*>(kc) + cbase + j * cstride + d4)
                        : uint4{0u, 0u, 0u, 0u};
       else
-        kr[u] = j < nk ? ld4raw(kc, cbase + j * cstride + d4, cbf) : uint4{0u, 0u, 0u, 0u};
+        kr[u] = has(j) ? ld4raw(kc, cbase + j * cstride + d4, cbf) : uint4{0u, 0u, 0u, 0u};
     }
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
       const int e = tid + 256 * u, j = e / (D / EPP), d4 = (e % (D / EPP)) * EPP;
       if constexpr (CBF == 2)
-        vr[u] = j < nk ? *reinterpret_cast<const uint4*>(static_cast<const signed char*>(vc) + cbase + j * cstride + d4)
+        vr[u] = has(j) ? *reinterpret_cast<const uint4*>(static_cast<const signed char*>(vc) + cbase + j * cstride + d4)
                        : uint4{0u, 0u, 0u, 0u};
       else
-        vr[u] = j < nk ? ld4raw(vc, cbase + j * cstride + d4, cbf) : uint4{0u, 0u, 0u, 0u};
+        vr[u] = has(j) ? ld4raw(vc, cbase + j * cstride + d4, cbf) : uint4{0u, 0u, 0u, 0u};
     }
   }
   if constexpr (CBF == 2) {
     if (fresh) {
       for (int r = wid; r < 2 * fr.n; r += 4) {  // wave-uniform: the whole wave takes or skips a row
-        const int isv = r >= fr.n, t = isv ? r - fr.n : r, jabs = pos[b] + t;
+        const int isv = r >= fr.n, t = isv ? r - fr.n : r, jabs = fresh_slot(t);
         if (jabs < k0 || jabs >= k0 + KC || jabs >= L) continue;
         int q0_, q1_;
         const float s = fresh_row_q8(t, !isv, q0_, q1_);
@@ -433,7 +529,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   } else if (fresh) {
     for (int e = tid; e < 2 * fr.n * (D / 2); e += 256) {
       const int isv = e >= fr.n * (D / 2), ee = isv ? e - fr.n * (D / 2) : e;
-      const int t = ee / (D / 2), d = ee % (D / 2), jabs = pos[b] + t;
+      const int t = ee / (D / 2), d = ee % (D / 2), jabs = fresh_slot(t);
       if (jabs < k0 || jabs >= k0 + KC || jabs >= L) continue;
       float x0, x1;
       fresh_row(t, d, !isv, x0, x1);
@@ -446,12 +542,21 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   // the fresh rows this split attends come from the registers' source, not the cache
   // (its stores above may still be in flight): staged over the cache's rows, at the cache's
   // precision (fresh_row)
+  // the split row that fresh row t is staged over (outside 0 .. nk - 1: none)
+  auto fresh_at = [&](int t) {
+    if constexpr (RING) {
+      const int s = fresh_slot(t);
+      return s < 0 ? -1 : s - k0;
+    } else {
+      return pos[b] + t - k0;
+    }
+  };
   auto overlay = [&](bool isk) {
     if (!fresh) return;
     __syncthreads();
     if constexpr (CBF == 2) {  // what the stores above put into the cache, dequantized
       for (int t = wid; t < fr.n; t += 4) {
-        const int j = pos[b] + t - k0;
+        const int j = fresh_at(t);
         if (j < 0 || j >= nk) continue;
         int q0_, q1_;
         const float s = fresh_row_q8(t, isk, q0_, q1_);
@@ -463,7 +568,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
       return;
     }
     for (int e = tid; e < fr.n * (D / 2); e += 256) {
-      const int t = e / (D / 2), d = e % (D / 2), j = pos[b] + t - k0;
+      const int t = e / (D / 2), d = e % (D / 2), j = fresh_at(t);
       if (j < 0 || j >= nk) continue;
       float x0, x1;
       fresh_row(t, d, isk, x0, x1);
@@ -551,7 +656,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
       const int r = rh + 2 * i;
       if (r < R) {
         const int qpos = p0 + r / G;  // causal: this row sees keys <= its position
-        sc[r * KC + j] = (j < nk && jabs <= qpos) ? acc[i] : -INFINITY;
+        if constexpr (RING)
+          sc[r * KC + j] = (j < nk && nos::ring_visible(jabs, qpos, pmax, L, rg.W)) ? acc[i] : -INFINITY;
+        else
+          sc[r * KC + j] = (j < nk && jabs <= qpos) ? acc[i] : -INFINITY;
       }
     }
   }
@@ -2016,6 +2124,67 @@ NOS_API int nos_kv_write(const void* x, int xbf, int ldx, long long bsx, void* c
   return (int)hipGetLastError();
 }
 
+// the arguments of a ring cache of C slots at a step of S rows: window W >= 1, min(limit, W + S - 1) <= C
+// <= limit (the step's rows and the first row's window fit), and the rotary tables cover every stored position
+static bool ring_ok(int C, int S, int W, int limit, bool rope, int R) {
+  if (W < 1 || limit < 1 || limit > (1 << 30) || C > limit || S > C) return false;
+  const long long need = (long long)W + S - 1;
+  if (C < (need < limit ? need : limit)) return false;
+  return !rope || limit <= R;
+}
+
+// nos_kv_write into ring caches [B, C, H, D] (kv_ring.h): the row of position p = pos[b] + s goes to slot
+// p % C, rows at p < 0 or p >= limit are dropped; window: the attention's, for the size check only
+NOS_API int nos_kv_write_ring(const void* x, int xbf, int ldx, long long bsx, void* cache, int cbf, const int* pos,
+                              const float* cos_t, const float* sin_t, int R, int B, int S, int H, int D, int C,
+                              const void* x2, int ldx2, long long bsx2, void* cache2, int window, int limit,
+                              hipStream_t stream) {
+  if (B <= 0 || S <= 0 || H <= 0 || D <= 0 || (D % 2) || C <= 0 || S > C || ldx < H * D || !x || !cache || !pos ||
+      (B > 1 && bsx < (long long)(S - 1) * ldx + H * D) || (xbf != 0 && xbf != 1) || (cbf != 0 && cbf != 1) ||
+      ((cos_t == nullptr) != (sin_t == nullptr)) || (cos_t && R <= 0) || ((x2 == nullptr) != (cache2 == nullptr)) ||
+      (x2 && (ldx2 < H * D || (B > 1 && bsx2 < (long long)(S - 1) * ldx2 + H * D))) ||
+      !ring_ok(C, S, window, limit, cos_t != nullptr, R))
+    return (int)hipErrorInvalidValue;
+  const long long n = (long long)B * S * H * (D / 2);
+  hipLaunchKernelGGL(kv_write_ring_kernel, dim3((unsigned)((n + 255) / 256), x2 ? 2u : 1u), dim3(256), 0, stream, x,
+                     xbf, ldx, bsx, cache, cbf, pos, cos_t, sin_t, R, B, S, H, D, C, KvPair{x2, ldx2, bsx2, cache2},
+                     limit);
+  return (int)hipGetLastError();
+}
+
+// nos_kv_write_q8 into int8 ring caches [B, C, H, D] with their row scales [B, C, H]
+NOS_API int nos_kv_write_ring_q8(const float* x, int ldx, long long bsx, void* cache, float* scales, float* deq,
+                                 const int* pos, const float* cos_t, const float* sin_t, int R, int B, int S, int H,
+                                 int D, int C, const float* x2, int ldx2, long long bsx2, void* cache2,
+                                 float* scales2, float* deq2, int window, int limit, hipStream_t stream) {
+  if (B <= 0 || S <= 0 || H <= 0 || (D != 64 && D != 128) || C <= 0 || S > C || ldx < H * D || !x || !cache ||
+      !scales || !pos || (B > 1 && bsx < (long long)(S - 1) * ldx + H * D) || ((uintptr_t)cache & 15) ||
+      ((uintptr_t)scales & 3) || ((uintptr_t)x & 3) || ((uintptr_t)deq & 3) ||
+      ((cos_t == nullptr) != (sin_t == nullptr)) || (cos_t && R <= 0) || ((x2 == nullptr) != (cache2 == nullptr)) ||
+      ((x2 == nullptr) != (scales2 == nullptr)) || (!x2 && deq2) ||
+      (x2 && (ldx2 < H * D || (B > 1 && bsx2 < (long long)(S - 1) * ldx2 + H * D) || ((uintptr_t)cache2 & 15) ||
+              ((uintptr_t)scales2 & 3) || ((uintptr_t)x2 & 3) || ((uintptr_t)deq2 & 3))) ||
+      !ring_ok(C, S, window, limit, cos_t != nullptr, R))
+    return (int)hipErrorInvalidValue;
+  const long long rows = (long long)B * S * H;
+  const dim3 grid((unsigned)((rows + 3) / 4), x2 ? 2u : 1u);
+  const KvPairQ8 v2{x2, ldx2, bsx2, static_cast<signed char*>(cache2), scales2, deq2};
+  if (D == 64)
+    hipLaunchKernelGGL(kv_write_q8_ring_kernel<64>, grid, dim3(256), 0, stream, x, ldx, bsx,
+                       static_cast<signed char*>(cache), scales, deq, pos, cos_t, sin_t, R, B, S, H, C, v2, limit);
+  else
+    hipLaunchKernelGGL(kv_write_q8_ring_kernel<128>, grid, dim3(256), 0, stream, x, ldx, bsx,
+                       static_cast<signed char*>(cache), scales, deq, pos, cos_t, sin_t, R, B, S, H, C, v2, limit);
+  return (int)hipGetLastError();
+}
+
+// the slot and visibility arithmetic the ring kernels use (kv_ring.h), for tests on the host
+NOS_API int nos_ring_slot(int p, int C, int limit) { return nos::ring_slot(p, C, limit); }
+NOS_API int nos_ring_position(int s, int pmax, int C) { return nos::ring_position(s, pmax, C); }
+NOS_API int nos_ring_visible(int s, int qpos, int pmax, int C, int W) { return nos::ring_visible(s, qpos, pmax, C, W); }
+NOS_API int nos_ring_oldest(int qlo, int pmax, int C, int W) { return nos::ring_oldest(qlo, pmax, C, W); }
+NOS_API int nos_ring_split_rows(int k0, int n, int lo, int hi, int C) { return nos::ring_split_rows(k0, n, lo, hi, C); }
+
 // nos_kv_write into int8 caches: x fp32, cache [B, L, H, D] int8 (16-byte aligned) with its row scales
 // [B, L, H] fp32, D = 64 / 128; deq (or null): [B, S, H, D] fp32 contiguous, the rows as the cache holds
 // them.  x2 / cache2 / scales2 / deq2: the unrotated second write of the launch (V).
@@ -2080,7 +2249,10 @@ static int attn_decode_launch(const void* q, int qbf, int ldq, long long bsq, co
                               void* out, int obf, int B, int H, int Hkv, int Sq, int L, int D, float scale, void* ws,
                               long long ws_bytes, const void* kn, const void* vn, int nbf, int ldk, long long bsk,
                               int ldv, long long bsv, int nfresh, int* sync, long long sync_n, int partials_only,
-                              hipStream_t stream) {
+                              bool ring, int window, int limit, hipStream_t stream) {
+  // ring caches (L = C slots): the window and the limit checked before anything else
+  if (ring && (L <= 0 || Sq <= 0 || !ring_ok(L, Sq, window, limit, cos_t != nullptr, R)))
+    return (int)hipErrorInvalidValue;
   if (B <= 0 || H <= 0 || Hkv <= 0 || H % Hkv || H / Hkv > MAXR || Sq <= 0 || L <= 0 || (D != 64 && D != 128) ||
       ldq < H * D || (B > 1 && bsq < (long long)(Sq - 1) * ldq + H * D) || !q || !kc || !vc || !pos || !out ||
       !ws || ((cos_t == nullptr) != (sin_t == nullptr)) || (cos_t && R <= 0) || (qbf != 0 && qbf != 1) ||
@@ -2116,10 +2288,18 @@ static int attn_decode_launch(const void* q, int qbf, int ldq, long long bsq, co
     const int sq = Sq - q0 < chunk ? Sq - q0 : chunk;
     const unsigned grid = (unsigned)(B * Hkv * NS);
     const unsigned rows = (unsigned)(B * Hkv * G * sq);
-#define NOS_ATTN_DECODE(d, c, ...)                                                                              \
-  hipLaunchKernelGGL((attn_decode_kernel<d, c>), dim3(grid), dim3(256), 0, stream, q, qbf, ldq, bsq, kc, vc, cbf, pos, \
-                     cos_t, sin_t, R, static_cast<float*>(ws), B, H, Hkv, sq, q0, L, NS, scale, fr, sync, out, obf, Sq, \
-                     CacheScales<c>{__VA_ARGS__})
+#define NOS_ATTN_DECODE_R(d, c, r, rg, ...)                                                                        \
+  hipLaunchKernelGGL((attn_decode_kernel<d, c, r>), dim3(grid), dim3(256), 0, stream, q, qbf, ldq, bsq, kc, vc, cbf,    \
+                     pos, cos_t, sin_t, R, static_cast<float*>(ws), B, H, Hkv, sq, q0, L, NS, scale, fr, sync, out, obf, \
+                     Sq, CacheScales<c>{__VA_ARGS__}, rg)
+#define NOS_ATTN_DECODE(d, c, ...)                                              \
+  do {                                                                          \
+    if (ring) {                                                                 \
+      NOS_ATTN_DECODE_R(d, c, true, (RingArgs<true>{window, limit}), __VA_ARGS__); \
+    } else {                                                                    \
+      NOS_ATTN_DECODE_R(d, c, false, RingArgs<false>{}, __VA_ARGS__);           \
+    }                                                                           \
+  } while (0)
     if (D == 64) {
       if (cbf == 2)
         NOS_ATTN_DECODE(64, 2, ks, vs);
@@ -2142,7 +2322,8 @@ static int attn_decode_launch(const void* q, int qbf, int ldq, long long bsq, co
                            static_cast<const float*>(ws), out, obf, B, H, Hkv, sq, q0, Sq, NS);
     }
   }
-  #undef NOS_ATTN_DECODE
+#undef NOS_ATTN_DECODE
+#undef NOS_ATTN_DECODE_R
   return (int)hipGetLastError();
 }
 
@@ -2154,7 +2335,24 @@ NOS_API int nos_attn_decode(const void* q, int qbf, int ldq, long long bsq, cons
   if (cbf != 0 && cbf != 1) return (int)hipErrorInvalidValue;
   return attn_decode_launch(q, qbf, ldq, bsq, kc, vc, cbf, nullptr, nullptr, pos, cos_t, sin_t, R, out, obf, B, H, Hkv,
                             Sq, L, D, scale, ws, ws_bytes, kn, vn, nbf, ldk, bsk, ldv, bsv, nfresh, sync, sync_n,
-                            partials_only, stream);
+                            partials_only, false, 0, 0, stream);
+}
+
+// nos_attn_decode over ring caches [B, C, Hkv, D] (kv_ring.h) with a sliding window: query i at position
+// p = pos[b] + i attends the positions max(0, p - window + 1) .. p, position j in slot j % C; fresh rows go
+// to their slots (rows at positions >= limit dropped); a counter outside [0, limit) gives zero rows.
+// C >= min(limit, window + Sq - 1), C <= limit, limit <= R with tables.  Workspace, sync and partials as
+// nos_attn_decode with L = C.
+NOS_API int nos_attn_decode_ring(const void* q, int qbf, int ldq, long long bsq, const void* kc, const void* vc,
+                                 int cbf, const int* pos, const float* cos_t, const float* sin_t, int R, void* out,
+                                 int obf, int B, int H, int Hkv, int Sq, int C, int D, float scale, void* ws,
+                                 long long ws_bytes, const void* kn, const void* vn, int nbf, int ldk, long long bsk,
+                                 int ldv, long long bsv, int nfresh, int* sync, long long sync_n, int partials_only,
+                                 int window, int limit, hipStream_t stream) {
+  if (cbf != 0 && cbf != 1) return (int)hipErrorInvalidValue;
+  return attn_decode_launch(q, qbf, ldq, bsq, kc, vc, cbf, nullptr, nullptr, pos, cos_t, sin_t, R, out, obf, B, H, Hkv,
+                            Sq, C, D, scale, ws, ws_bytes, kn, vn, nbf, ldk, bsk, ldv, bsv, nfresh, sync, sync_n,
+                            partials_only, true, window, limit, stream);
 }
 
 // nos_attn_decode over int8 caches [B, L, Hkv, D] (16-byte aligned) with one fp32 scale per row in
@@ -2169,7 +2367,19 @@ NOS_API int nos_attn_decode_q8(const float* q, int ldq, long long bsq, void* kc,
                                hipStream_t stream) {
   return attn_decode_launch(q, 0, ldq, bsq, kc, vc, 2, kscales, vscales, pos, cos_t, sin_t, R, out, 0, B, H, Hkv, Sq, L,
                             D, scale, ws, ws_bytes, kn, vn, 0, ldk, bsk, ldv, bsv, nfresh, sync, sync_n,
-                            partials_only, stream);
+                            partials_only, false, 0, 0, stream);
+}
+
+// nos_attn_decode_ring over int8 ring caches with their row scales [B, C, Hkv]
+NOS_API int nos_attn_decode_ring_q8(const float* q, int ldq, long long bsq, void* kc, void* vc, float* kscales,
+                                    float* vscales, const int* pos, const float* cos_t, const float* sin_t, int R,
+                                    float* out, int B, int H, int Hkv, int Sq, int C, int D, float scale, void* ws,
+                                    long long ws_bytes, const float* kn, const float* vn, int ldk, long long bsk,
+                                    int ldv, long long bsv, int nfresh, int* sync, long long sync_n,
+                                    int partials_only, int window, int limit, hipStream_t stream) {
+  return attn_decode_launch(q, 0, ldq, bsq, kc, vc, 2, kscales, vscales, pos, cos_t, sin_t, R, out, 0, B, H, Hkv, Sq, C,
+                            D, scale, ws, ws_bytes, kn, vn, 0, ldk, bsk, ldv, bsv, nfresh, sync, sync_n,
+                            partials_only, true, window, limit, stream);
 }
 
 NOS_API int nos_pos_update(int* pos, int B, int add, int n, hipStream_t stream) {

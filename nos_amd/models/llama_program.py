@@ -96,6 +96,37 @@ def mixtral_model(cfg, seed: int = 0):
     return m
 
 
+def mistral_config(small: bool = True, **kw):
+    """A MistralConfig: ``small`` -- the tests' tiny variant (sliding window 8); else the fleet decoder's shape
+    with a window of 1024.  Keyword arguments override fields."""
+    from transformers import MistralConfig
+
+    base = dict(hidden_size=256, num_hidden_layers=2, num_attention_heads=2, num_key_value_heads=1,
+                intermediate_size=512, vocab_size=512, max_position_embeddings=512, rms_norm_eps=1e-5,
+                sliding_window=8, tie_word_embeddings=False) if small else \
+        dict(hidden_size=1024, num_hidden_layers=8, num_attention_heads=8, num_key_value_heads=2,
+             intermediate_size=2816, vocab_size=32000, max_position_embeddings=8192, rms_norm_eps=1e-5,
+             sliding_window=1024, tie_word_embeddings=False)
+    base.update(kw)
+    return MistralConfig(**base)
+
+
+def mistral_model(cfg, seed: int = 0):
+    """A random-init HF MistralForCausalLM in fp32, eval mode (eager attention)."""
+    import torch
+    from transformers import MistralForCausalLM
+
+    torch.manual_seed(seed)
+    cfg._attn_implementation = "eager"
+    m = MistralForCausalLM(cfg).float().eval()
+    with torch.no_grad():  # non-trivial norm weights (HF initialises them to ones)
+        g = torch.Generator().manual_seed(seed + 1)
+        for name, p in m.named_parameters():
+            if name.endswith("norm.weight"):
+                p.copy_(1 + 0.1 * torch.randn(p.shape, generator=g))
+    return m
+
+
 def _rope_theta(cfg) -> float:
     """The rotary base: ``rope_parameters["rope_theta"]`` where the config keeps it there (transformers 5),
     else its ``rope_theta`` attribute, else 10000."""
@@ -224,7 +255,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
                           extend: tuple[int, ...] = (), sampling: bool = False,
                           weights: str = "fp32", kv: str | None = None,
                           stopping: bool = False, speculate: int | None = None,
-                          adapters: list | None = None) -> tuple[list[dict], bytes]:
+                          adapters: list | None = None, window: int | None = None) -> tuple[list[dict], bytes]:
     """A STATEFUL generation tenant: ``[prefill, decode, *extends]`` programs
     over one weight payload and one state -- per layer a K and a V cache
     ``[batch, max_len, kv_heads, head_dim]`` plus the position counter
@@ -336,12 +367,30 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     ``stopping``, ``kv="int8"``, ``speculate`` and ``adapters`` on q / k / v / o work
     as above; refused, each with its rule: ``weights="int8"``, ``dtype="bf16"``,
     adapter targets in the MLP, a ``sliding_window`` smaller than ``max_len`` and a
-    ``speculate`` with ``batch * K * max(H, I) * 4 > GEMV_X_BYTES``."""
+    ``speculate`` with ``batch * K * max(H, I) * 4 > GEMV_X_BYTES``.
+
+    ``window`` (default: ``config.sliding_window`` of a ``MistralForCausalLM``, else none; with every
+    option above): sliding-window attention, the query at position p attending the W positions
+    max(0, p - W + 1) .. p.  It takes effect only for W < ``max_len`` (else the programs are the plain
+    ones, byte for byte).  The caches are then RINGS of ``C = min(max_len, W + S - 1)`` slots, S the
+    longest step of the tenant (``prompt_len``, the ``extend`` lengths, ``speculate``): position p
+    lives in slot p % C, a step writes its rows and then attends, and the row a fresh row replaces
+    lies outside every window of the step and of every later one -- a verify step's rejected rows
+    included.  ``kv_write`` and ``sdpa_cache`` carry ``window=W, limit=max_len``; ``hist``, the rotary
+    tables and the server's context limit stay at ``max_len``, so the caches cost C rows whatever
+    ``max_len`` is.  A prompt longer than W keeps the decode kernel for its prefill (correct, slow:
+    docs/tenant_programs.md).  A Mixtral takes no window."""
     from ..ops.tenant import GEMV_MAX_ROWS, GEMV_X_BYTES
 
     moe = getattr(model.config, "model_type", None) == "mixtral"
     if moe:
         _refuse_mixtral(model.config, max_len, batch, dtype, weights, speculate, adapters, GEMV_X_BYTES)
+        if window is not None:
+            raise ValueError("a Mixtral tenant takes no window (no sliding-window attention beside the moe op yet)")
+    if window is None and getattr(model.config, "model_type", None) == "mistral":
+        window = getattr(model.config, "sliding_window", None)
+    if window is not None and (not isinstance(window, int) or isinstance(window, bool) or window < 1):
+        raise ValueError(f"window must be an int >= 1 (the positions a query attends, itself included), got {window!r}")
     if adapters is not None and dtype != "fp32":
         raise ValueError("adapters are an fp32 tenant's (fp32 A and B beside fp32 or int8 weights): dtype must be 'fp32', "
                          "dtype='bf16' is not taken")
@@ -390,6 +439,10 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     chunks = [(prompt_len, True, False), (1, False, False)] + [(n, False, False) for n in extend]
     if speculate:
         chunks.append((speculate, False, True))
+    # a window below max_len: every variant's caches are one ring, sized for the longest step
+    ring_slots = min(max_len, window + max(n for n, _, _ in chunks) - 1) if window is not None and window < max_len \
+        else None
+    ring = {"window": window, "limit": max_len} if ring_slots else {}
     payload = b""
     for seq, reset, verify in chunks:
         b = Builder(f"{'mixtral' if moe else 'llama'}-h{d}-l{cfg.num_hidden_layers}-{dtype}{'-q8' if q8 else ''}{'-kvq8' if kvq8 else ''}-"
@@ -428,7 +481,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
         ctl = b.state("sampling", [4], "i32") if sampling else None
         done, seen, sctl = b.stopping_states(batch, cfg.vocab_size) if stopping else (None, None, None)
         hist, spec_ctl = b.speculate_states(batch, max_len) if speculate else (None, None)
-        cshape = [batch, max_len, nkv, hd]
+        cshape = [batch, ring_slots or max_len, nkv, hd]
         if kvq8:   # ((K cache, its scales), (V cache, its scales)) per layer
             caches = [(b.cache_q8(f"kc{i}", f"ks{i}", cshape), b.cache_q8(f"vc{i}", f"vs{i}", cshape))
                       for i in range(cfg.num_hidden_layers)]
@@ -454,9 +507,9 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
             v = b.op("reshape", proj(2), shape=[batch, seq, nkv, hd])
             q, k = b.op("rotary_at", q, rc, rs, p), b.op("rotary_at", k, rc, rs, p)
             (kc0, *ks), (vc0, *vs) = caches[i]   # ks / vs: the scales states of i8 caches, else empty
-            kc = b.op("kv_write", kc0, k, p, *ks)
-            vc = b.op("kv_write", vc0, v, p, *vs)
-            o = b.op("reshape", b.op("sdpa_cache", q, kc, vc, p, *ks, *vs), shape=[batch, seq, nh * hd])
+            kc = b.op("kv_write", kc0, k, p, *ks, **ring)
+            vc = b.op("kv_write", vc0, v, p, *vs, **ring)
+            o = b.op("reshape", b.op("sdpa_cache", q, kc, vc, p, *ks, *vs, **ring), shape=[batch, seq, nh * hd])
             h = b.op("add", adapted(lin(o, pf + "self_attn.o_proj.weight"), o, pf + "self_attn.o_proj"), h)
             y = b.op("rmsnorm", h, P(pf + "post_attention_layernorm.weight"), eps=eps)
             if moe:   # the sparse MLP: the router, the fused expert tensors as the state dict holds them
@@ -622,5 +675,5 @@ def llama_tenant(dtype: str = "fp32", seed: int = 0, small: bool = True, seq: in
     return llama_program(m, seq if small else 64, batch, dtype)
 
 
-__all__ = ["mixtral_config", "mixtral_model", "llama_config", "llama_model", "llama_program", "llama_decode_programs", "llama_tenant", "rope_tables",
+__all__ = ["mistral_config", "mistral_model", "mixtral_config", "mixtral_model", "llama_config", "llama_model", "llama_program", "llama_decode_programs", "llama_tenant", "rope_tables",
            "dequantized_llama", "kv_q8_roundtrip_cache", "adapted_llama"]

@@ -116,6 +116,26 @@ _SIGS = {
     "nos_attn_decode_q8": [c_void_p, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_ll,
                            c_void_p, c_void_p, c_int, c_ll, c_int, c_ll, c_int, c_void_p, c_ll, c_int, c_void_p],
+    # sliding-window decoders: ring K / V caches (decode.hip, kv_ring.h) -- the plain entry points'
+    # arguments with C for L, then window and limit before the stream; the index helpers for host tests
+    "nos_kv_write_ring": [c_void_p, c_int, c_int, c_ll, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                          c_int, c_int, c_int, c_int, c_void_p, c_int, c_ll, c_void_p, c_int, c_int, c_void_p],
+    "nos_kv_write_ring_q8": [c_void_p, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                             c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_ll, c_void_p, c_void_p, c_void_p,
+                             c_int, c_int, c_void_p],
+    "nos_attn_decode_ring": [c_void_p, c_int, c_int, c_ll, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                             c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_ll,
+                             c_void_p, c_void_p, c_int, c_int, c_ll, c_int, c_ll, c_int, c_void_p, c_ll, c_int, c_int,
+                             c_int, c_void_p],
+    "nos_attn_decode_ring_q8": [c_void_p, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                c_ll, c_void_p, c_void_p, c_int, c_ll, c_int, c_ll, c_int, c_void_p, c_ll, c_int, c_int,
+                                c_int, c_void_p],
+    "nos_ring_slot": [c_int, c_int, c_int],
+    "nos_ring_position": [c_int, c_int, c_int],
+    "nos_ring_visible": [c_int, c_int, c_int, c_int, c_int],
+    "nos_ring_oldest": [c_int, c_int, c_int, c_int],
+    "nos_ring_split_rows": [c_int, c_int, c_int, c_int, c_int],
     "nos_pos_update": [c_void_p, c_int, c_int, c_int, c_void_p],
     "nos_argmax": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     "nos_sample_row_in_lds": [c_int],

@@ -713,8 +713,19 @@ def _i32_pos(pos: torch.Tensor, B: int) -> torch.Tensor:
     return pos
 
 
+def _ring(what: str, window, limit, C: int, S: int, rope) -> bool:
+    """``window`` / ``limit`` of a ring cache of C slots at a step of S rows: whether the cache is a ring."""
+    from ..podserver.program.reference import _ring_args
+
+    ring = _ring_args(what, window, limit, C, S)
+    if ring and rope is not None and limit > rope[0].shape[0]:
+        raise ValueError(f"{what}: limit {limit} exceeds the rotary tables' {rope[0].shape[0]} rows")
+    return ring
+
+
 def kv_write(cache: torch.Tensor, x: torch.Tensor, pos: torch.Tensor, rope: tuple | None = None,
-             second: tuple | None = None, scales: torch.Tensor | None = None, deq: bool = False):
+             second: tuple | None = None, scales: torch.Tensor | None = None, deq: bool = False,
+             window: int | None = None, limit: int | None = None):
     """cache[b, pos[b] + s] = x[b, s] in place (rows past the cache dropped);
     ``rope`` = (cos, sin) fp32 tables: x rotated at those positions first.
     ``second`` = (cache2, x2): a second, unrotated write of the same shape in
@@ -724,18 +735,24 @@ def kv_write(cache: torch.Tensor, x: torch.Tensor, pos: torch.Tensor, rope: tupl
     (cache2, x2, scales2)): the fp32 rows are quantized as they are written
     (after the rotation; ``quantize_rows_q8``'s rule per row).  ``deq``:
     also return the written rows as the cache now holds them, fp32
-    [B, S, H, D] -- ``(cache, deq)``, with ``second`` ``(cache, deq, deq2)``."""
+    [B, S, H, D] -- ``(cache, deq)``, with ``second`` ``(cache, deq, deq2)``.
+
+    ``window`` and ``limit`` (together): the cache is a ring of C = L slots
+    for a sliding window -- the row of position p goes to slot p % C, rows at
+    p < 0 or p >= limit are dropped; min(limit, window + S - 1) <= C <= limit."""
     from ..podserver.program.reference import kv_write_ref, rotary_at_ref
 
     q8 = cache.dtype == torch.int8
     if q8 != (scales is not None) or (deq and not q8):
         raise ValueError("kv_write: an int8 cache, and only an int8 cache, takes scales (and gives deq)")
+    ring = _ring("kv_write", window, limit, cache.shape[1], x.shape[1], rope)
     if q8:
-        return _kv_write_q8(cache, x, pos, rope, second, scales, deq)
+        return _kv_write_q8(cache, x, pos, rope, second, scales, deq, window, limit)
     if not cache.is_cuda:
         if second is not None:
-            kv_write_ref(second[0], second[1], pos)
-        return kv_write_ref(cache, rotary_at_ref(x, rope[0], rope[1], pos) if rope else x, pos)
+            kv_write_ref(second[0], second[1], pos, window=window, limit=limit)
+        return kv_write_ref(cache, rotary_at_ref(x, rope[0], rope[1], pos) if rope else x, pos, window=window,
+                            limit=limit)
     B, L, H, D = cache.shape
     S = x.shape[1]
     if x.shape[0] != B or x.shape[2:] != cache.shape[2:] or not cache.is_contiguous():
@@ -754,6 +771,12 @@ def kv_write(cache: torch.Tensor, x: torch.Tensor, pos: torch.Tensor, rope: tupl
             raise ValueError("kv_write: the second write must match the first's shapes and dtypes")
         x2, ld2, bs2 = _rows(x2)
         x2p, c2p = x2.data_ptr(), c2.data_ptr()
+    if ring:
+        _lib.check(_lib.lib().nos_kv_write_ring(x.data_ptr(), _bf(x), ldx, bsx, cache.data_ptr(), _bf(cache),
+                                                _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R, B, S, H, D, L, x2p,
+                                                ld2, bs2, c2p, int(window), int(limit), _stream()),
+                   "nos_kv_write_ring")
+        return cache
     _lib.check(_lib.lib().nos_kv_write(x.data_ptr(), _bf(x), ldx, bsx, cache.data_ptr(), _bf(cache),
                                        _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R, B, S, H, D, L, x2p, ld2, bs2,
                                        c2p, _stream()), "nos_kv_write")
@@ -767,7 +790,7 @@ def _q8_cache_ok(what: str, cache: torch.Tensor, scales: torch.Tensor) -> None:
                          f"got {cache.dtype} {tuple(cache.shape)} and {scales.dtype} {tuple(scales.shape)}")
 
 
-def _kv_write_q8(cache, x, pos, rope, second, scales, deq):
+def _kv_write_q8(cache, x, pos, rope, second, scales, deq, window=None, limit=None):
     """:func:`kv_write` into int8 caches (decode.hip ``nos_kv_write_q8``; the eager reference on the CPU)."""
     from ..podserver.program.reference import dequantize_kv_rows, kv_write_ref, quantize_kv_rows, rotary_at_ref
 
@@ -780,9 +803,9 @@ def _kv_write_q8(cache, x, pos, rope, second, scales, deq):
         raise ValueError("kv_write: int8 caches take fp32 rows")
     if not cache.is_cuda:
         xs = [rotary_at_ref(x, rope[0], rope[1], pos) if rope else x] + ([second[1]] if second is not None else [])
-        kv_write_ref(cache, xs[0], pos, scales)
+        kv_write_ref(cache, xs[0], pos, scales, window=window, limit=limit)
         if second is not None:
-            kv_write_ref(second[0], xs[1], pos, second[2])
+            kv_write_ref(second[0], xs[1], pos, second[2], window=window, limit=limit)
         return (cache, *(dequantize_kv_rows(*quantize_kv_rows(t)) for t in xs)) if deq else cache
     B, L, H, D = cache.shape
     S = x.shape[1]
@@ -803,9 +826,15 @@ def _kv_write_q8(cache, x, pos, rope, second, scales, deq):
         x2, ld2, bs2 = _rows(x2)
         x2p, c2p, s2p = x2.data_ptr(), c2.data_ptr(), s2.data_ptr()
         dq2 = torch.empty_like(dq) if deq else None
-    _lib.check(_lib.lib().nos_kv_write_q8(x.data_ptr(), ldx, bsx, cache.data_ptr(), scales.data_ptr(), _ptr(dq),
-                                          _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R, B, S, H, D, L, x2p, ld2,
-                                          bs2, c2p, s2p, _ptr(dq2), _stream()), "nos_kv_write_q8")
+    if window is not None:
+        _lib.check(_lib.lib().nos_kv_write_ring_q8(x.data_ptr(), ldx, bsx, cache.data_ptr(), scales.data_ptr(),
+                                                   _ptr(dq), _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R, B, S,
+                                                   H, D, L, x2p, ld2, bs2, c2p, s2p, _ptr(dq2), int(window),
+                                                   int(limit), _stream()), "nos_kv_write_ring_q8")
+    else:
+        _lib.check(_lib.lib().nos_kv_write_q8(x.data_ptr(), ldx, bsx, cache.data_ptr(), scales.data_ptr(), _ptr(dq),
+                                              _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R, B, S, H, D, L, x2p,
+                                              ld2, bs2, c2p, s2p, _ptr(dq2), _stream()), "nos_kv_write_q8")
     if not deq:
         return cache
     return (cache, dq) if second is None else (cache, dq, dq2)
@@ -841,7 +870,8 @@ class DecodePartials:
 
 def sdpa_cache(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: torch.Tensor, scale: float | None = None,
                rope: tuple | None = None, fresh: tuple | None = None, sync: torch.Tensor | None = None,
-               partials: bool = False, scales: tuple | None = None):
+               partials: bool = False, scales: tuple | None = None, window: int | None = None,
+               limit: int | None = None):
     """Query i of sequence b, at position pos[b] + i, attends the cached keys
     0 .. pos[b] + i: q [B, Sq, H, D], caches [B, L, Hkv, D] (fp32 / bf16).
     ``rope`` = (cos, sin): q rotated at its positions inside the kernel.
@@ -858,7 +888,15 @@ def sdpa_cache(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: torch.T
     int8 caches with ``scales`` = (kscales, vscales) [B, L, Hkv] fp32 (q and
     ``fresh`` fp32): the attention of the values ``float(q) * scale`` the
     caches hold; fresh rows are quantized into the caches and the scales (as
-    :func:`kv_write` does) and attended as stored."""
+    :func:`kv_write` does) and attended as stored.
+
+    ``window`` and ``limit`` (together): sliding-window attention over ring
+    caches of C = L slots -- the query at position p attends the positions
+    max(0, p - window + 1) .. p, position j living in slot j % C (written
+    there by :func:`kv_write` with the same pair, or as ``fresh`` rows; rows
+    at positions >= limit dropped).  min(limit, window + Sq - 1) <= C <=
+    limit; a counter outside [0, limit) gives zero rows.  The partials carry
+    the ring's split count."""
     from ..podserver.program.reference import kv_write_ref, rotary_at_ref, sdpa_cache_ref
 
     q8 = kc.dtype == torch.int8
@@ -870,11 +908,14 @@ def sdpa_cache(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: torch.T
         if q.dtype != torch.float32 or (fresh is not None and fresh[0].dtype != torch.float32):
             raise ValueError("sdpa_cache: int8 caches take an fp32 q and fp32 fresh rows")
     ks, vs = scales if q8 else (None, None)
+    ring = _ring("sdpa_cache", window, limit, kc.shape[1], q.shape[1], rope)
     if not q.is_cuda:
         if fresh is not None:
-            kv_write_ref(kc, rotary_at_ref(fresh[0], rope[0], rope[1], pos) if rope else fresh[0], pos, ks)
-            kv_write_ref(vc, fresh[1], pos, vs)
-        return sdpa_cache_ref(rotary_at_ref(q, rope[0], rope[1], pos) if rope else q, kc, vc, pos, scale, ks, vs)
+            kv_write_ref(kc, rotary_at_ref(fresh[0], rope[0], rope[1], pos) if rope else fresh[0], pos, ks,
+                         window=window, limit=limit)
+            kv_write_ref(vc, fresh[1], pos, vs, window=window, limit=limit)
+        return sdpa_cache_ref(rotary_at_ref(q, rope[0], rope[1], pos) if rope else q, kc, vc, pos, scale, ks, vs,
+                              window=window, limit=limit)
     B, Sq, H, D = q.shape
     L, Hkv = kc.shape[1], kc.shape[2]
     if (kc.shape != vc.shape or kc.dtype != vc.dtype or kc.shape[0] != B or kc.shape[3] != D or H % Hkv
@@ -904,7 +945,21 @@ def sdpa_cache(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: torch.T
         raise ValueError(f"sdpa_cache: sync needs >= {B * Hkv} contiguous int32 device counters")
     if partials and (Sq != 1 or sync is not None or q.dtype != torch.float32):
         raise ValueError("sdpa_cache: partials need one fp32 query token and no sync")
-    if q8:
+    if ring:   # the plain entry points' arguments (L the ring's slots), then the window and the limit
+        tail = (_ptr(kn), _ptr(vn), *(() if q8 else (nbf,)), ldk, bsk, ldv, bsv, Sq if fresh is not None else 0,
+                _ptr(sync), sync.numel() if sync is not None else 0, int(bool(partials)), int(window), int(limit),
+                _stream())
+        if q8:
+            _lib.check(L_.nos_attn_decode_ring_q8(q.data_ptr(), ldq, bsq, kc.data_ptr(), vc.data_ptr(), ks.data_ptr(),
+                                                  vs.data_ptr(), _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R,
+                                                  out.data_ptr(), B, H, Hkv, Sq, L, D, float(sc), ws.data_ptr(),
+                                                  ws.numel() * 4, *tail), "nos_attn_decode_ring_q8")
+        else:
+            _lib.check(L_.nos_attn_decode_ring(q.data_ptr(), _bf(q), ldq, bsq, kc.data_ptr(), vc.data_ptr(), _bf(kc),
+                                               _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R, out.data_ptr(),
+                                               _bf(out), B, H, Hkv, Sq, L, D, float(sc), ws.data_ptr(),
+                                               ws.numel() * 4, *tail), "nos_attn_decode_ring")
+    elif q8:
         _lib.check(L_.nos_attn_decode_q8(q.data_ptr(), ldq, bsq, kc.data_ptr(), vc.data_ptr(), ks.data_ptr(),
                                          vs.data_ptr(), _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R,
                                          out.data_ptr(), B, H, Hkv, Sq, L, D, float(sc), ws.data_ptr(), ws.numel() * 4,

@@ -28,6 +28,12 @@ def _reads(s: _Step) -> list[str]:
     return s.inputs + s.attrs.get("lora", [])
 
 
+def _ring_of(s: _Step) -> dict:
+    """The ring attributes (``window``, ``limit``) of a ``kv_write`` / ``sdpa_cache`` step: they ride
+    through every fusion unchanged."""
+    return {k: s.attrs[k] for k in ("window", "limit") if k in s.attrs}
+
+
 class Lowered:
     """A parsed program lowered onto the nos-amd ops for one device: the
     passes below turn its nodes into ``self.steps`` (the package docstring
@@ -175,6 +181,10 @@ class Lowered:
                 s.inputs = s.inputs[:n]
                 roots.update(s.attrs["scales"])
         self.stats["kv_q8_caches"] = len(roots)
+        # the caches kept as rings (a sliding window: kv_write / sdpa_cache with window and limit)
+        root = self.program.state_root
+        self.stats["ring_caches"] = len({root.get(s.inputs[k], s.inputs[k]) for s in steps if "window" in s.attrs
+                                         for k in ((0,) if s.kind == "kv_write" else (1, 2))})
         return steps
 
     def _lower_static_positions(self, steps: list[_Step]) -> list[_Step]:
@@ -217,6 +227,8 @@ class Lowered:
                         or wk.inputs[2] != s.inputs[3] or wv.inputs[2] != s.inputs[3]
                         or self._shape(wk.inputs[1])[1] != sq or self._shape(wv.inputs[1])[1] != sq):
                     continue
+                if sq > s.attrs.get("window", sq):   # a window shorter than the step hides keys from its late
+                    continue                         # rows: the ring decode kernel keeps it (correct, slow)
                 kv = [wk.inputs[1], wv.inputs[1]]
                 if s.attrs.get("scales"):
                     for w in (wk, wv):
@@ -1197,7 +1209,7 @@ class Lowered:
             wk, wv = by_out.get(s.inputs[1]), by_out.get(s.inputs[2])
             if (wk is None or wv is None or wk.kind != "kv_write" or wv.kind != "kv_write" or id(wk) in drop
                     or wv.attrs.get("rope") or wv.attrs.get("pair") or wk.inputs[2] != wv.inputs[2]
-                    or wk.attrs.get("deq_out") or wv.attrs.get("deq_out")
+                    or wk.attrs.get("deq_out") or wv.attrs.get("deq_out") or _ring_of(wk) != _ring_of(wv)
                     or tuple(self._shape(wk.inputs[1])) != tuple(self._shape(wv.inputs[1]))
                     or tuple(self._shape(wk.inputs[0])) != tuple(self._shape(wv.inputs[0]))
                     or self._dtype(wk.inputs[0]) != self._dtype(wv.inputs[0])
@@ -1205,7 +1217,8 @@ class Lowered:
                 continue
             wv.inputs = wk.inputs + [wv.inputs[0], wv.inputs[1]]   # K cache, K x, pos, [cos, sin], V cache, V x
             wv.attrs = {"pair": True, "rope": bool(wk.attrs.get("rope")), "k_out": wk.output,
-                        **({"scales": wk.attrs["scales"] + wv.attrs["scales"]} if wk.attrs.get("scales") else {})}
+                        **({"scales": wk.attrs["scales"] + wv.attrs["scales"]} if wk.attrs.get("scales") else {}),
+                        **_ring_of(wk)}
             drop.add(id(wk))
             n += 1
         self.stats["kv_writes_paired"] = n
@@ -1234,7 +1247,7 @@ class Lowered:
             r = 5 if rope else 3                      # w: K cache, K x, pos, [cos, sin], V cache, V x
             if (rope != bool(s.attrs.get("rope")) or s.inputs[3] != w.inputs[2]
                     or (rope and list(w.inputs[3:5]) != list(s.inputs[4:6]))
-                    or uses.get(w.output) != 1 or uses.get(w.attrs["k_out"]) != 1
+                    or uses.get(w.output) != 1 or uses.get(w.attrs["k_out"]) != 1 or _ring_of(w) != _ring_of(s)
                     or uses.get(w.inputs[0]) != 1 or uses.get(w.inputs[r]) != 1
                     or tuple(self._shape(w.inputs[1]))[1] != tuple(self._shape(s.inputs[0]))[1]):
                 continue

@@ -160,12 +160,14 @@ class CompiledProgram(Lowered):
                 r = 5 if s.attrs.get("rope") else 3
                 sc = [self.state[n] for n in s.attrs.get("scales", ())]   # i8 caches: K's and V's row scales
                 env[s.attrs["k_out"]] = T.kv_write(a[0], a[1], a[2], rope=(a[3], a[4]) if s.attrs.get("rope") else None,
-                                                   second=(a[r], a[r + 1], *sc[1:]), scales=sc[0] if sc else None)
+                                                   second=(a[r], a[r + 1], *sc[1:]), scales=sc[0] if sc else None,
+                                                   window=s.attrs.get("window"), limit=s.attrs.get("limit"))
                 y = a[r]
             elif k == "kv_write":
                 sc = [self.state[n] for n in s.attrs.get("scales", ())]
                 y = T.kv_write(a[0], a[1], a[2], rope=(a[3], a[4]) if s.attrs.get("rope") else None,
-                               scales=sc[0] if sc else None, deq=bool(s.attrs.get("deq_out")))
+                               scales=sc[0] if sc else None, deq=bool(s.attrs.get("deq_out")),
+                               window=s.attrs.get("window"), limit=s.attrs.get("limit"))
                 if s.attrs.get("deq_out"):   # the rows as the i8 cache holds them, for the prefill's flash attention
                     y, env[s.attrs["deq_out"]] = y
             elif k == "sdpa_cache":
@@ -174,7 +176,7 @@ class CompiledProgram(Lowered):
                                  rope=(a[4], a[5]) if s.attrs.get("rope") else None,
                                  fresh=(a[-2], a[-1]) if s.attrs.get("fresh") else None,
                                  sync=self.aux.get(s.attrs.get("sync")), partials=bool(s.attrs.get("partials")),
-                                 scales=sc or None)
+                                 scales=sc or None, window=s.attrs.get("window"), limit=s.attrs.get("limit"))
             elif k == "rotary_at":
                 y = T.rotary_at(a[0], a[1], a[2], a[3])
             elif k == "stop_step":   # pos_add(pos, done) / stop_ids / done_mark: next ids, pos, done, ctl

@@ -114,9 +114,11 @@ def _eager(op: str, args: list, attrs: dict, ref: bool = False):
     if op == "sdpa":
         return T.sdpa_ref(args[0], args[1], args[2], attrs.get("causal", False), attrs.get("scale"))
     if op == "kv_write":
-        return kv_write_ref(args[0], args[1], args[2], args[3] if len(args) > 3 else None)
+        return kv_write_ref(args[0], args[1], args[2], args[3] if len(args) > 3 else None,
+                            window=attrs.get("window"), limit=attrs.get("limit"))
     if op == "sdpa_cache":
-        return sdpa_cache_ref(args[0], args[1], args[2], args[3], attrs.get("scale"), *args[4:6])
+        return sdpa_cache_ref(args[0], args[1], args[2], args[3], attrs.get("scale"), *args[4:6],
+                              window=attrs.get("window"), limit=attrs.get("limit"))
     if op == "rotary_at":
         return rotary_at_ref(args[0], args[1], args[2], args[3])
     if op == "pos_add" and len(args) == 2:   # a stopping tenant's: finished rows keep their counter
@@ -173,15 +175,41 @@ def dequantize_kv_rows(q, scale):
     return q.to(torch.float32) * scale.to(torch.float32)[..., None]
 
 
-def kv_write_ref(cache, x, pos, scales=None):
+def _ring_args(what: str, window, limit, C: int, S: int) -> bool:
+    """``window`` / ``limit`` of a ring cache of C slots at a step of S rows (both or neither; the
+    validator's rule): whether the cache is a ring."""
+    if (window is None) != (limit is None):
+        raise ValueError(f"{what}: window and limit are given together (a ring cache), or neither")
+    if window is None:
+        return False
+    if window < 1 or limit < 1 or C > limit or C < min(limit, window + S - 1):
+        raise ValueError(f"{what}: a ring cache of {C} slots does not fit window {window}, limit {limit} and "
+                         f"{S} rows a step (min(limit, window + S - 1) <= slots <= limit)")
+    return True
+
+
+def kv_write_ref(cache, x, pos, scales=None, window=None, limit=None):
     """cache[b, pos[b] + i] = x[b, i] for the rows that fit (in place).  An int8 cache with its
-    ``scales`` [B, L, Hkv] (fp32): the rows quantized (:func:`quantize_kv_rows`) into both."""
+    ``scales`` [B, L, Hkv] (fp32): the rows quantized (:func:`quantize_kv_rows`) into both.
+
+    ``window`` and ``limit``: the cache is a ring of C = L slots -- the row of position p goes to slot
+    p % C, rows at p < 0 or p >= limit are dropped."""
     import torch
 
     q8 = cache.dtype == torch.int8
     if q8 != (scales is not None):
         raise ValueError("kv_write: an int8 cache, and only an int8 cache, takes scales")
     L, S = cache.shape[1], x.shape[1]
+    if _ring_args("kv_write", window, limit, L, S):
+        for b in range(cache.shape[0]):
+            for i in range(S):
+                p = int(pos[b]) + i
+                if 0 <= p < limit:
+                    if q8:
+                        cache[b, p % L], scales[b, p % L] = quantize_kv_rows(x[b, i])
+                    else:
+                        cache[b, p % L] = x[b, i].to(cache.dtype)
+        return cache
     for b in range(cache.shape[0]):
         p0 = int(pos[b])
         n = max(0, min(S, L - p0))
@@ -193,10 +221,42 @@ def kv_write_ref(cache, x, pos, scales=None):
     return cache
 
 
-def sdpa_cache_ref(q, kc, vc, pos, scale=None, kscales=None, vscales=None):
+def _sdpa_ring_ref(q, kc, vc, pos, sc, window: int, limit: int, ct):
+    """:func:`sdpa_cache_ref` over ring caches (dequantized already), a sequence at a time."""
+    import torch
+
+    B, Sq, H, D = q.shape
+    C, G = kc.shape[1], H // kc.shape[2]
+    out = torch.zeros(q.shape, dtype=ct)
+    slots = torch.arange(C)
+    for b in range(B):
+        pb = int(pos[b])
+        if pb < 0 or pb >= limit:   # a bad counter: no row sees anything
+            continue
+        pmax = pb + Sq - 1
+        held = pmax - torch.remainder(pmax - slots, C)     # the position every slot holds after the step's writes
+        qpos = pb + torch.arange(Sq).view(Sq, 1)
+        keep = (held >= 0) & (held <= qpos) & (held > qpos - window)      # [Sq, C]
+        seen = keep.any(dim=0)    # slots no row sees may hold anything (stale, never written): they are not read
+        z = torch.zeros((), dtype=ct)
+        kf = torch.where(seen.view(C, 1, 1), kc[b].to(ct), z).repeat_interleave(G, dim=1)
+        vf = torch.where(seen.view(C, 1, 1), vc[b].to(ct), z).repeat_interleave(G, dim=1)
+        s = torch.einsum("qhd,khd->hqk", q[b].to(ct), kf) * sc
+        s = s.masked_fill(~keep[None], float("-inf"))
+        p = torch.softmax(s, dim=-1)     # every row sees its own position (Sq <= C)
+        out[b] = torch.einsum("hqk,khd->qhd", p, vf)
+    return out.to(q.dtype)
+
+
+def sdpa_cache_ref(q, kc, vc, pos, scale=None, kscales=None, vscales=None, window=None, limit=None):
     """Query i of sequence b at position pos[b] + i attends the cached keys
     0 .. min(pos[b] + i, L - 1) (fp32 math, fp64 for an fp64 q; grouped-query K / V heads).
-    int8 caches with their scales: the attention of the values they hold (:func:`dequantize_kv_rows`)."""
+    int8 caches with their scales: the attention of the values they hold (:func:`dequantize_kv_rows`).
+
+    ``window`` and ``limit``: the caches are rings of C = L slots.  After the step's rows are written
+    (:func:`kv_write_ref`) slot s holds position a(s) = pmax - ((pmax - s) mod C) for the step's last
+    position pmax = pos[b] + Sq - 1; the query at qpos sees slot s iff 0 <= a(s) <= qpos and
+    a(s) > qpos - window.  A counter outside [0, limit) gives zero rows."""
     import math
 
     import torch
@@ -209,6 +269,8 @@ def sdpa_cache_ref(q, kc, vc, pos, scale=None, kscales=None, vscales=None):
     B, Sq, H, D = q.shape
     L, Hkv = kc.shape[1], kc.shape[2]
     ct = torch.float64 if q.dtype == torch.float64 else torch.float32   # an fp64 reference stays fp64
+    if _ring_args("sdpa_cache", window, limit, L, Sq):
+        return _sdpa_ring_ref(q, kc, vc, pos, scale if scale is not None else 1.0 / math.sqrt(D), window, limit, ct)
     kf = kc.to(ct).repeat_interleave(H // Hkv, dim=2)
     vf = vc.to(ct).repeat_interleave(H // Hkv, dim=2)
     sc = scale if scale is not None else 1.0 / math.sqrt(D)

@@ -288,11 +288,14 @@ def _infer(node: Node, ins: list[Value], gpu: bool) -> tuple[tuple[int, ...], st
     if op == "kv_write":
         # cache [B, L, Hkv, D] <- x [B, S, Hkv, D] at rows pos[b] .. pos[b] + S - 1 (rows past L are dropped)
         # an i8 cache (rows quantized as they are written) takes its fp32 scales state [B, L, Hkv] as input 3
-        only()
+        # window + limit: the cache is a ring of C = L slots (position p in slot p % C, rows at p >= limit dropped)
+        only("window", "limit")
         arity(3, 4)
         c, x, p = ins[:3]
         _req(len(c.shape) == 4 and c.dtype in FLOAT_DTYPES + ("i8",),
              f"{what}: the cache must be a float or i8 [B, L, Hkv, D] state")
+        if len(x.shape) == 4:
+            _ring_attrs(a, c.shape[1], x.shape[1], what)
         q8 = c.dtype == "i8"
         _req(q8 or len(ins) == 3, f"{what}: a {c.dtype} cache takes no scales (input 3 belongs to an i8 cache)")
         _req(not q8 or len(ins) == 4, f"{what}: an i8 cache needs its scales state as input 3")
@@ -307,9 +310,12 @@ def _infer(node: Node, ins: list[Value], gpu: bool) -> tuple[tuple[int, ...], st
     if op == "sdpa_cache":
         # q [B, Sq, H, D] at positions pos[b] + i over the cached keys 0 .. pos[b] + i (causal)
         # i8 caches take their fp32 scales states [B, L, Hkv] as inputs 4 (K) and 5 (V)
-        only("scale")
+        # window + limit: ring caches; the query at p attends the positions max(0, p - window + 1) .. p
+        only("scale", "window", "limit")
         _req(len(ins) in (4, 6), f"{what}: takes 4 inputs (6 with the scales of i8 caches), got {len(ins)}")
         q, kc, vc, p = ins[:4]
+        if len(q.shape) == 4 and len(kc.shape) == 4:
+            _ring_attrs(a, kc.shape[1], q.shape[1], what)
         _req(len(q.shape) == 4 and len(kc.shape) == 4 and kc.shape == vc.shape and kc.dtype == vc.dtype
              and q.shape[0] == kc.shape[0] and q.shape[3] == kc.shape[3] and q.shape[2] % kc.shape[2] == 0
              and q.shape[1] <= kc.shape[1] and q.dtype in FLOAT_DTYPES and kc.dtype in FLOAT_DTYPES + ("i8",),
@@ -539,11 +545,30 @@ def _stop_ctl(ctl: Value, what: str) -> None:
          f"{ctl.dtype} {list(ctl.shape)}")
 
 
+def _ring_name(ring: tuple | None) -> str:
+    return "a plain cache" if ring is None else f"a ring of window {ring[0]} and limit {ring[1]}"
+
+
 def _scales_state(s: Value, cache: Value, what: str) -> None:
     """The row scales of an i8 cache [B, L, Hkv, D]: an fp32 [B, L, Hkv] state."""
     _req(s.kind == "state" and s.dtype == "fp32" and s.shape == cache.shape[:3],
          f"{what}: the scales of an i8 cache must be an fp32 {list(cache.shape[:3])} state, got {s.kind} "
          f"{s.name!r} {s.dtype} {list(s.shape)}")
+
+
+def _ring_attrs(a: dict, C: int, S: int, what: str) -> None:
+    """``window`` / ``limit`` of a ``kv_write`` / ``sdpa_cache`` over a ring cache of C slots, at a step of S rows:
+    the step writes its rows and then attends, so the ring holds the first row's window and the whole step."""
+    _req(("window" in a) == ("limit" in a), f"{what}: window and limit are given together (a ring cache), or neither")
+    if "window" not in a:
+        return
+    for k in ("window", "limit"):
+        _req(isinstance(a[k], int) and not isinstance(a[k], bool) and 1 <= a[k] <= 1 << 30,
+             f"{what}: {k} must be an int >= 1, got {a[k]!r}")
+    W, limit = a["window"], a["limit"]
+    _req(C <= limit, f"{what}: a ring cache of {C} slots is longer than its limit {limit}")
+    _req(C >= min(limit, W + S - 1), f"{what}: a ring cache needs min(limit, window + S - 1) = "
+         f"{min(limit, W + S - 1)} slots for window {W} and {S} rows a step, the cache has {C}")
 
 
 # the slots an i8 state (a quantized cache) and its scales state may fill
@@ -657,6 +682,7 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     scales_of: dict[str, str] = {}      # a scales state -> the i8 cache (root) whose row scales it holds
     cache_scales: dict[str, str] = {}   # and back
     other_use: dict[str, str] = {}      # a state -> the first node naming it as anything but a cache's scales
+    rings: dict[str, tuple] = {}        # a cache (root) -> the (window, limit) every node naming it carries, or None
     ns = obj.get("nodes")
     _req(isinstance(ns, list) and 0 < len(ns) <= MAX_NODES, f"nodes must be a list of 1..{MAX_NODES}")
     nodes = []
@@ -728,8 +754,16 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
             _req(adapter in (None, refs[3]), f"node {n.output!r} (lora): a program has one adapter state; "
                  f"{adapter!r} and {refs[3]!r} are two")
             adapter = refs[3]
-        if op == "kv_write":
-            cache_rows.setdefault(values[refs[0]].shape[1], f"node {n.output!r} ({op})")
+        for ck in {"kv_write": (0,), "sdpa_cache": (1, 2)}.get(op, ()):
+            root = root_of.get(refs[ck])
+            _req(root is not None or "window" not in attrs, f"node {n.output!r} ({op}): a ring cache must be a state "
+                 f"(or a version of one); {refs[ck]!r} is not")
+            ring = (attrs["window"], attrs["limit"]) if "window" in attrs else None
+            if root is not None:
+                _req(rings.setdefault(root, ring) == ring, f"node {n.output!r} ({op}): the cache {root!r} is "
+                     f"{_ring_name(rings[root])} in an earlier node and {_ring_name(ring)} here")
+        if op == "kv_write":   # the positions the write keeps: a ring's limit, else the cache's rows
+            cache_rows.setdefault(attrs.get("limit", values[refs[0]].shape[1]), f"node {n.output!r} ({op})")
         if op == "spec_accept":
             spec_limits.setdefault(attrs["limit"], f"node {n.output!r} ({op})")
         define(Value(n.output, shape, dt, "node"))

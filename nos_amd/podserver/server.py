@@ -277,7 +277,7 @@ def _pos_limits(progs) -> dict:
         for n in p.nodes:
             if n.op == "kv_write":
                 root = p.state_root.get(n.inputs[2], n.inputs[2])
-                rows = p.values[n.inputs[0]].shape[1]
+                rows = n.attrs.get("limit", p.values[n.inputs[0]].shape[1])   # a ring cache keeps positions < limit
                 lim[root] = min(lim.get(root, rows), rows)
     return lim
 
