@@ -37,7 +37,10 @@
 //  * nos_gemv -- y = act(r x W^T + b) + R for M <= 8 rows (a decode step's
 //    every GEMM): weight-streaming, each wave two output columns, lanes over
 //    K with 16-byte weight loads, x rows in LDS (optionally RMS-normalised in
-//    the prologue: RMSNorm folded into the GEMM, gamma in W), exact fp32 math.
+//    the prologue: RMSNorm folded into the GEMM, gamma in W), exact fp32 math;
+//  * nos_gemv_q8 / nos_gemv_mx4 -- the same over int8 rows with a scale per row and over
+//    MXFP4 blocks (4-bit E2M1 codes, an E8M0 scale byte per 32 k): weight-only storage
+//    formats, fp32 math on the dequantized values.
 #include <float.h>
 #include <math.h>
 
@@ -1771,6 +1774,249 @@ __global__ __launch_bounds__(256) void gemv_q8_kernel(const float* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------ MXFP4 weight-only GEMV (M <= 8)
+// W = codes [N, K / 2] u8 (two E2M1 elements per byte, element 2 i in the low nibble) with one E8M0
+// scale byte e per 32 consecutive k of a row (scales [N, K / 32] u8, 2 <= e <= 252): a storage
+// format, the product is that of the dequantized fp32 weight elem x 2^(e - 127), every such value a
+// normal fp32.  gfx950 converts a byte of two codes to two fp32 with the block scale as an operand
+// (v_cvt_scalef32_pk_f32_fp4; the scale is the float with bits e << 23), so the FMAs run on the
+// dequantized values and nothing is left for the epilogue.  NOS_MX4_CVT_PLAIN builds the same decode
+// from integer operations instead (sign, 3-bit magnitude, one exact multiply by the scale).
+__device__ __forceinline__ float mx4_scale(unsigned e) { return __uint_as_float(e << 23); }
+
+#ifdef NOS_MX4_CVT_PLAIN
+__device__ __forceinline__ float mx4_cvt1(unsigned c, float s) {
+  const unsigned mag = c & 7u;   // 0, 0.5, then 1, 1.5, 2, 3, 4, 6 = the fp32 with bits (mag << 22) + (126 << 23)
+  const float el = mag < 2u ? 0.5f * (float)mag : __uint_as_float((mag << 22) + (126u << 23));
+  return __uint_as_float(__float_as_uint(el * s) | ((c & 8u) << 28));
+}
+#endif
+
+// elements 2 B, 2 B + 1 of the eight in word v (byte B: low nibble first), times the scale s
+template <int B>
+__device__ __forceinline__ float2 mx4_cvt2(unsigned v, float s) {
+#ifdef NOS_MX4_CVT_PLAIN
+  return float2{mx4_cvt1(v >> (8 * B), s), mx4_cvt1(v >> (8 * B + 4), s)};
+#else
+  const auto r = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(v, s, B);
+  return float2{r[0], r[1]};
+#endif
+}
+
+// elements 4 H .. 4 H + 3 of word v
+template <int H>
+__device__ __forceinline__ float4 mx4_cvt4(unsigned v, float s) {
+  const float2 a = mx4_cvt2<2 * H>(v, s), b = mx4_cvt2<2 * H + 1>(v, s);
+  return float4{a.x, a.y, b.x, b.y};
+}
+
+// A lane's load is LB bytes of one row: KL = 2 LB consecutive k.  LB = 16 is exactly one MX block
+// (one scale byte per lane, row and load; a wave's are 64 consecutive bytes) and a wave load covers
+// 2048 k; LB = 8 is half a block (two lanes share a scale byte), 1024 k per wave load, so that a
+// 1024-wide row still has work for all 64 lanes.  x sits in LDS as fp32, permuted as for the int8
+// GEMV with the lane's run of KL k in place of 16:
+//   k = 64 KL b + KL l + 4 j + e  ->  64 KL b + 4 nl j + 4 l + e,  j < KL / 4,  nl = min(64, (K - 64 KL b) / KL)
+// so that the wave's read of the j-th float4 of every lane is one contiguous run (16-byte lane
+// stride: ds_read_b128 conflict-free, by the argument above gemv_q8_kernel).  K % 32 == 0.
+constexpr int MX4_R = 4;   // weight rows per wave, as Q8_R
+
+template <int LB>
+struct Mx4Words;
+template <>
+struct Mx4Words<16> {
+  using T = uint4;
+  static __device__ __forceinline__ void get(const uint4& v, unsigned (&w)[4]) {
+    w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+  }
+};
+template <>
+struct Mx4Words<8> {
+  using T = uint2;
+  static __device__ __forceinline__ void get(const uint2& v, unsigned (&w)[2]) { w[0] = v.x, w[1] = v.y; }
+};
+
+template <int M, int KU, int LB>
+__global__ __launch_bounds__(256) void gemv_mx4_kernel(const float* __restrict__ x, int ldx,
+                                                       const unsigned char* __restrict__ w, int ldw,
+                                                       const unsigned char* __restrict__ wsc, int ldsc,
+                                                       const float* __restrict__ gamma, const float* __restrict__ bias,
+                                                       const float* __restrict__ res, int ldr, float* __restrict__ y,
+                                                       int ldy, int N, int K, int epi, float rms_eps, Parts pt) {
+  static_assert(MX4_R == 4, "the GLU pairing is written for four rows");
+  static_assert(LB == 16 || LB == 8, "a lane loads one MX block or half of one");
+  constexpr int KL = 2 * LB, BLK = 64 * KL, NW = LB / 4;   // k per lane and per wave load; words per lane load
+  using Ld = typename Mx4Words<LB>::T;
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // [M][K] fp32, each row permuted as above
+  __shared__ float rsc[M];
+  __shared__ float sqp[4][M];   // the waves' sums of squares of each x row
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const bool glu = (epi & EPI_GLU) != 0;
+  const int Nh = N / 2;
+  const int ngrp = glu ? (Nh + 7) / 8 : (N + 15) / 16;
+  // the wave's MX4_R weight rows of column group grp; GLU: gates n0, n0 + 1, then their ups
+  auto rows_of = [&](int grp, int& n0, int (&nr)[MX4_R]) {
+    n0 = glu ? grp * 8 + wid * 2 : grp * 16 + wid * MX4_R;
+#pragma unroll
+    for (int c = 0; c < MX4_R; ++c) nr[c] = glu ? min(n0 + (c & 1), Nh - 1) + (c >> 1) * Nh : min(n0 + c, N - 1);
+  };
+  // codes and the block's scale byte; past K: zeros under the scale 1
+  auto load_chunk = [&](const int (&nr)[MX4_R], int kb, Ld (&a)[MX4_R][KU], unsigned (&e)[MX4_R][KU]) {
+#pragma unroll
+    for (int u = 0; u < KU; ++u) {
+      const int k = kb + BLK * u + lane * KL;
+#pragma unroll
+      for (int c = 0; c < MX4_R; ++c) {
+        a[c][u] = k < K ? *reinterpret_cast<const Ld*>(w + (long long)nr[c] * ldw + (k >> 1)) : Ld{};
+        e[c][u] = k < K ? (unsigned)wsc[(long long)nr[c] * ldsc + (k >> 5)] : 127u;
+      }
+    }
+  };
+  // the first group's first K chunk of weights in flight while x is staged (as gemv_kernel); later
+  // groups' while the one before is computed
+  Ld pa[MX4_R][KU];
+  unsigned pe[MX4_R][KU];
+  if ((int)blockIdx.x < ngrp) {
+    int n0, nr[MX4_R];
+    rows_of(blockIdx.x, n0, nr);
+    load_chunk(nr, 0, pa, pe);
+  }
+  float sq[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) sq[m] = 0.f;
+  // p: the LDS position, its k from the permutation; a thread's loads go out four at a time
+  constexpr int SU = 4;
+  for (int p0 = tid * 4; p0 < M * K; p0 += 1024 * SU) {
+    float4 v[SU], g[SU];
+    int ms[SU];
+#pragma unroll
+    for (int s = 0; s < SU; ++s) {
+      const int p = p0 + 1024 * s;
+      if (p < M * K) {
+        const int m = p / K, pk = p % K;
+        const int b = pk / BLK, o = pk % BLK;
+        const int nl = min(64, (K - b * BLK) / KL);
+        const int k = b * BLK + KL * ((o % (4 * nl)) >> 2) + 4 * (o / (4 * nl));
+        ms[s] = m;
+        v[s] = gemv_x4(pt, x, 0, ldx, m, k);
+        g[s] = gamma != nullptr ? *reinterpret_cast<const float4*>(gamma + k) : float4{1.f, 1.f, 1.f, 1.f};
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < SU; ++s) {
+      const int p = p0 + 1024 * s;
+      if (p < M * K) {
+        float4 t = v[s];
+        if (rms_eps > 0.f) {
+          const float q = fmaf(t.x, t.x, fmaf(t.y, t.y, fmaf(t.z, t.z, t.w * t.w)));
+#pragma unroll
+          for (int mm = 0; mm < M; ++mm) sq[mm] += mm == ms[s] ? q : 0.f;
+          t = float4{t.x * g[s].x, t.y * g[s].y, t.z * g[s].z, t.w * g[s].w};
+        }
+        *reinterpret_cast<float4*>(&xs[p]) = t;
+      }
+    }
+  }
+  if (rms_eps > 0.f) {
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      const float t = nos::wave_sum(sq[m]);
+      if (lane == 0) sqp[wid][m] = t;
+    }
+  }
+  __syncthreads();
+  if (tid < M)
+    rsc[tid] = rms_eps > 0.f
+                   ? rsqrtf(((sqp[0][tid] + sqp[1][tid]) + (sqp[2][tid] + sqp[3][tid])) / (float)K + rms_eps)
+                   : 1.f;
+  __syncthreads();
+  for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    int n0, nr[MX4_R];
+    rows_of(grp, n0, nr);
+    float acc[MX4_R][M];
+#pragma unroll
+    for (int c = 0; c < MX4_R; ++c)
+#pragma unroll
+      for (int m = 0; m < M; ++m) acc[c][m] = 0.f;
+    for (int kb = 0; kb < K; kb += BLK * KU) {
+      Ld ra[MX4_R][KU];
+      unsigned re[MX4_R][KU];
+      if (kb == 0) {   // prefetched; the workgroup's next group's first chunk goes out before this one's math
+#pragma unroll
+        for (int c = 0; c < MX4_R; ++c)
+#pragma unroll
+          for (int u = 0; u < KU; ++u) {
+            ra[c][u] = pa[c][u];
+            re[c][u] = pe[c][u];
+          }
+        if (grp + (int)gridDim.x < ngrp) {
+          int nn, nrn[MX4_R];
+          rows_of(grp + gridDim.x, nn, nrn);
+          load_chunk(nrn, 0, pa, pe);
+        }
+      } else {
+        load_chunk(nr, kb, ra, re);
+      }
+#pragma unroll
+      for (int u = 0; u < KU; ++u) {
+        const int k0 = kb + BLK * u;               // block k0 / BLK of the row
+        if (k0 + lane * KL < K) {
+          const int nl = min(64, (K - k0) / KL);
+          unsigned wd[MX4_R][NW];
+          float sc[MX4_R];
+#pragma unroll
+          for (int c = 0; c < MX4_R; ++c) {
+            Mx4Words<LB>::get(ra[c][u], wd[c]);
+            sc[c] = mx4_scale(re[c][u]);
+          }
+#pragma unroll
+          for (int j2 = 0; j2 < NW; ++j2) {        // a word: 8 k, two float4 of x
+            float4 wlo[MX4_R], whi[MX4_R];
+#pragma unroll
+            for (int c = 0; c < MX4_R; ++c) {
+              wlo[c] = mx4_cvt4<0>(wd[c][j2], sc[c]);
+              whi[c] = mx4_cvt4<1>(wd[c][j2], sc[c]);
+            }
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+              const float* xr = &xs[m * K + k0 + 4 * lane];
+              const float4 x0 = *reinterpret_cast<const float4*>(xr + 4 * nl * (2 * j2));
+              const float4 x1 = *reinterpret_cast<const float4*>(xr + 4 * nl * (2 * j2 + 1));
+#pragma unroll
+              for (int c = 0; c < MX4_R; ++c) {
+                acc[c][m] = fmaf(wlo[c].x, x0.x, fmaf(wlo[c].y, x0.y, fmaf(wlo[c].z, x0.z, fmaf(wlo[c].w, x0.w, acc[c][m]))));
+                acc[c][m] = fmaf(whi[c].x, x1.x, fmaf(whi[c].y, x1.y, fmaf(whi[c].z, x1.z, fmaf(whi[c].w, x1.w, acc[c][m]))));
+              }
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < MX4_R; ++c)
+#pragma unroll
+      for (int m = 0; m < M; ++m) acc[c][m] = nos::wave_sum(acc[c][m]);
+    if (glu) {  // lane (c * M + m), c < 2, finishes output (m, n0 + c) from gate row c and up row c + 2
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+          const int n = n0 + c;
+          if (lane == c * M + m && n < Nh)
+            gemv_finish_glu(acc[c][m] * rsc[m], acc[c + 2][m] * rsc[m], m, n, Nh, epi, bias, 0, y, ldy, 0);
+        }
+      continue;
+    }
+    // lane (c * M + m) finishes output (m, n0 + c)
+#pragma unroll
+    for (int c = 0; c < MX4_R; ++c)
+#pragma unroll
+      for (int m = 0; m < M; ++m) {
+        const int n = n0 + c;
+        if (lane == c * M + m && n < N) gemv_finish(acc[c][m] * rsc[m], m, n, epi, bias, 0, res, ldr, y, ldy, 0);
+      }
+  }
+}
+
 // ------------------------------------------------------------------ LoRA shrink (M <= 8)
 // t[m][j] = sum_k A[a_m - 1][j][k] xn[m][k], a_m = sel[m / rps]: the low-rank activations the GEMV after
 // it expands (Lora).  xn is the x that GEMV multiplies: read with its staging helper (gemv_x4: an
@@ -2103,6 +2349,22 @@ __global__ __launch_bounds__(256) void dequant_q8_kernel(const signed char* __re
     const float4 q = q8_cvt4(*reinterpret_cast<const unsigned*>(w + (long long)n * ldw + k));
     const float s = wscale[n];
     *reinterpret_cast<float4*>(out + (long long)n * ldo + k) = float4{q.x * s, q.y * s, q.z * s, q.w * s};
+  }
+}
+
+// out [N, K] fp32 = elem x 2^(e - 127) of the MXFP4 weight, the GEMV's own conversion: 8 weights per
+// thread (a 4-byte load of codes and the block's scale byte, two 16-byte stores)
+__global__ __launch_bounds__(256) void dequant_mx4_kernel(const unsigned char* __restrict__ w, int ldw,
+                                                          const unsigned char* __restrict__ wsc, int ldsc,
+                                                          float* __restrict__ out, int ldo, int N, int K) {
+  const long long total = (long long)N * (K / 8);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int n = (int)(i / (K / 8)), k = (int)(i % (K / 8)) * 8;
+    const unsigned v = *reinterpret_cast<const unsigned*>(w + (long long)n * ldw + (k >> 1));
+    const float s = mx4_scale(wsc[(long long)n * ldsc + (k >> 5)]);
+    float* o = out + (long long)n * ldo + k;
+    *reinterpret_cast<float4*>(o) = mx4_cvt4<0>(v, s);
+    *reinterpret_cast<float4*>(o + 4) = mx4_cvt4<1>(v, s);
   }
 }
 
@@ -2798,6 +3060,102 @@ NOS_API int nos_dequant_q8(const void* wq, int ldw, const float* wscale, float* 
   const long long blocks = (total + 255) / 256;
   hipLaunchKernelGGL(dequant_q8_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, stream,
                      static_cast<const signed char*>(wq), ldw, wscale, out, ldo, N, K);
+  return (int)hipGetLastError();
+}
+
+// y [M, N] fp32 = act(rms(x) gamma x [M, K] . dequant(codes [N, K / 2], scales [N, K / 32])^T + bias) + res,
+// M <= 8: the decode step of an MXFP4 weight-only tenant (gemv_mx4_kernel).  K % 32 == 0, ldw (bytes
+// per row of codes) % 16 == 0, codes 16-byte aligned, ldsc >= K / 32, M x K x 4 <= 64 KiB; gamma (or
+// null: ones) only with rms_eps > 0.  Every scale byte must lie in [2, 252] (the registration checks
+// it).  grid: as the int8 GEMV's.
+#ifndef NOS_MX4_NARROW_K
+#define NOS_MX4_NARROW_K 1024   // rows up to this long take the 8-byte-load form (docs/kernels.md)
+#endif
+static int gemv_mx4_launch(const float* x, int ldx, const void* wq, int ldw, const void* wscale, int ldsc,
+                           const float* gamma, const float* bias, const float* res, int ldr, float* y, int ldy, int M,
+                           int N, int K, int epi, float rms_eps, Parts pt, hipStream_t stream) {
+  if (!wq || !wscale || !y || M <= 0 || M > 8 || N <= 0 || K <= 0 || (K % 32) || ldw < K / 2 || (ldw % 16) ||
+      ((uintptr_t)wq & 15) || ldsc < K / 32 || (long long)M * K * 4 > 65536 || ((epi & EPI_BIAS) && !bias) ||
+      ((epi & EPI_RESID) && (!res || ldr < N)) || ldy < ((epi & EPI_GLU) ? N / 2 : N) ||
+      (gamma && (!(rms_eps > 0.f) || ((uintptr_t)gamma & 15))))
+    return (int)hipErrorInvalidValue;
+  if ((epi & EPI_GLU) && ((N % 2) || (epi & (EPI_RESID | EPI_GELU | EPI_RELU | EPI_SILU))))
+    return (int)hipErrorInvalidValue;
+  const int ngrp = (epi & EPI_GLU) ? (N / 2 + 7) / 8 : (N + 15) / 16;
+  const int cap = 3 * nos_effective_cus();
+  const unsigned grid = (unsigned)(ngrp < cap ? ngrp : cap);
+  const size_t lds = (size_t)M * K * 4;
+#define NOS_GEMV_MX4_F(m, ku, lb)                                                                                  \
+  hipLaunchKernelGGL((gemv_mx4_kernel<m, ku, lb>), dim3(grid), dim3(256), lds, stream, x, ldx,                     \
+                     static_cast<const unsigned char*>(wq), ldw, static_cast<const unsigned char*>(wscale), ldsc, \
+                     gamma, bias, res, ldr, y, ldy, N, K, epi, rms_eps, pt)
+  // K <= 1024: 8-byte loads, the whole row in one batch with every lane at work (148 against 194
+  // VGPRs at M = 1, and measured alone against the 16-byte form: 3.60 / 3.86 us at 1024 x 1024,
+  // 8.95 / 12.80 us at the 32000 x 1024 head); K <= 2048: one block per lane; longer rows (a down
+  // projection's 2816) in batches of 2 x MX4_R loads
+#define NOS_GEMV_MX4(m)                \
+  if (K <= NOS_MX4_NARROW_K) {         \
+    NOS_GEMV_MX4_F(m, 1, 8);           \
+  } else if (K <= 2048) {              \
+    NOS_GEMV_MX4_F(m, 1, 16);          \
+  } else {                             \
+    NOS_GEMV_MX4_F(m, 2, 16);          \
+  }
+  switch (M) {
+    case 1: NOS_GEMV_MX4(1); break;
+    case 2: NOS_GEMV_MX4(2); break;
+    case 3: NOS_GEMV_MX4(3); break;
+    case 4: NOS_GEMV_MX4(4); break;
+    case 5: NOS_GEMV_MX4(5); break;
+    case 6: NOS_GEMV_MX4(6); break;
+    case 7: NOS_GEMV_MX4(7); break;
+    default: NOS_GEMV_MX4(8); break;
+  }
+#undef NOS_GEMV_MX4
+#undef NOS_GEMV_MX4_F
+  return (int)hipGetLastError();
+}
+
+NOS_API int nos_gemv_mx4(const float* x, int ldx, const void* wq, int ldw, const void* wscale, int ldsc,
+                         const float* gamma, const float* bias, const float* res, int ldr, float* y, int ldy, int M,
+                         int N, int K, int epi, float rms_eps, hipStream_t stream) {
+  if (!x || ldx < K || (ldx % 4) || ((uintptr_t)x & 15)) return (int)hipErrorInvalidValue;
+  return gemv_mx4_launch(x, ldx, wq, ldw, wscale, ldsc, gamma, bias, res, ldr, y, ldy, M, N, K, epi, rms_eps, Parts{},
+                         stream);
+}
+
+// nos_gemv_mx4 with x = the decode attention's split partials (as nos_gemv_partials): the combine
+// launch folded into an MXFP4 O-projection
+NOS_API int nos_gemv_mx4_partials(const float* ws, long long ws_n, int NS, int R, int G, int Hkv, int D,
+                                  const void* wq, int ldw, const void* wscale, int ldsc, const float* bias,
+                                  const float* res, int ldr, float* y, int ldy, int M, int N, int K, int epi,
+                                  hipStream_t stream) {
+  if (!parts_ok(ws, ws_n, NS, R, G, Hkv, D, M, K) || (epi & EPI_GLU)) return (int)hipErrorInvalidValue;
+  Parts pt;
+  pt.ws = ws;
+  pt.NS = NS;
+  pt.R = R;
+  pt.G = G;
+  pt.Hkv = Hkv;
+  pt.D = D;
+  return gemv_mx4_launch(nullptr, K, wq, ldw, wscale, ldsc, nullptr, bias, res, ldr, y, ldy, M, N, K, epi, 0.f, pt,
+                         stream);
+}
+
+// out [N, K] fp32 (row stride ldo) = the MXFP4 weight dequantized, bit-exact: the weight of an MXFP4
+// linear at more than 8 rows, for the h3 product.  K % 32 == 0, ldw % 4 == 0, ldo % 4 == 0, codes
+// 4-byte and out 16-byte aligned.
+NOS_API int nos_dequant_mx4(const void* wq, int ldw, const void* wscale, int ldsc, float* out, int ldo, int N, int K,
+                            hipStream_t stream) {
+  if (!wq || !wscale || !out || N <= 0 || K <= 0 || (K % 32) || ldw < K / 2 || (ldw % 4) || ldsc < K / 32 || ldo < K ||
+      (ldo % 4) || ((uintptr_t)wq & 3) || ((uintptr_t)out & 15))
+    return (int)hipErrorInvalidValue;
+  const long long total = (long long)N * (K / 8);
+  const long long cap = 32LL * nos_effective_cus();
+  const long long blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(dequant_mx4_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, stream,
+                     static_cast<const unsigned char*>(wq), ldw, static_cast<const unsigned char*>(wscale), ldsc, out,
+                     ldo, N, K);
   return (int)hipGetLastError();
 }
 

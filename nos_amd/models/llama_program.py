@@ -22,7 +22,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..podserver.program import Builder, dequantize_rows_q8, quantize_rows_q8
+from ..podserver.program import (Builder, dequantize_rows_mx4, dequantize_rows_q8, quantize_rows_mx4,
+                                 quantize_rows_q8)
 
 # the HF Llama linears an int8 tenant stores quantized (every weight but the embedding table and the norms)
 _Q8_LINEARS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
@@ -293,6 +294,16 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     the server computes, in fp32, exactly the model
     :func:`dequantized_llama` returns.
 
+    ``weights="mxfp4"`` (fp32 tenants): the same linears stored as OCP Microscaling MXFP4
+    (``Builder.param_mx4``: 4-bit E2M1 codes, one E8M0 scale byte per 32 consecutive inputs of a row,
+    4.25 bits a weight) and read by ``linear_mx4`` nodes, merged as for int8 (blocks run along the
+    inputs, so merging rows and quantizing commute).  A storage format again:
+    ``dequantized_llama(model, weights="mxfp4")`` is the model the server computes.  It combines with
+    ``batch``, ``extend``, ``sampling``, ``stopping``, ``kv="int8"``, ``window`` and ``speculate`` (under the
+    int8 staging rule below); refused, each with its rule: ``dtype="bf16"``, ``adapters`` (no adapter
+    epilogue on the MXFP4 GEMV yet), a Mixtral (no quantized experts yet) and a hidden or
+    intermediate size that is no multiple of 32.
+
     ``kv="int8"`` (fp32 tenants; default: the tenant's dtype): the caches are
     i8 states ``kc{i}`` / ``vc{i}`` with one fp32 scale per (sequence,
     position, KV head) row in ``ks{i}`` / ``vs{i}`` ``[batch, max_len,
@@ -403,8 +414,9 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
             raise ValueError(f"speculate: batch * K = {batch * speculate} > {GEMV_MAX_ROWS} (GEMV_MAX_ROWS): every "
                              f"linear of the verify step must stay one GEMV launch")
         widest = max(model.config.hidden_size, model.config.intermediate_size)
-        if weights == "int8" and batch * speculate * widest * 4 > GEMV_X_BYTES:
-            raise ValueError(f"speculate: batch * K = {batch * speculate} rows of {widest} inputs are more than the int8 "
+        if weights in ("int8", "mxfp4") and batch * speculate * widest * 4 > GEMV_X_BYTES:
+            raise ValueError(f"speculate: batch * K = {batch * speculate} rows of {widest} inputs are more than the "
+                             f"{'int8' if weights == 'int8' else 'MXFP4'} "
                              f"GEMV stages ({GEMV_X_BYTES} bytes of x rows): that linear of the verify step would "
                              f"dequantize a transient fp32 weight")
         if dtype != "fp32":
@@ -417,15 +429,28 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
                              f"the server routes variants by input shape")
     if not 0 < prompt_len <= max_len:
         raise ValueError(f"prompt_len must be in [1, {max_len}]")
-    if weights not in ("fp32", "int8"):
-        raise ValueError(f"weights must be 'fp32' or 'int8', got {weights!r}")
+    if weights not in ("fp32", "int8", "mxfp4"):
+        raise ValueError(f"weights must be 'fp32', 'int8' or 'mxfp4', got {weights!r}")
     if weights == "int8" and dtype != "fp32":
         raise ValueError("int8 weights are an fp32 tenant's storage format: dtype must be 'fp32'")
+    if weights == "mxfp4":
+        if dtype != "fp32":
+            raise ValueError("MXFP4 weights are an fp32 tenant's storage format: dtype must be 'fp32', dtype='bf16' is "
+                             "not taken")
+        if adapters is not None:
+            raise ValueError("adapters do not combine with weights='mxfp4': the MXFP4 GEMV has no adapter epilogue yet "
+                             "(fp32 and int8 weights take adapters)")
+        for what, size in (("hidden_size", model.config.hidden_size),
+                           ("intermediate_size", model.config.intermediate_size)):
+            if size % 32:
+                raise ValueError(f"weights='mxfp4': {what} = {size} is not a multiple of 32 (an MXFP4 block is 32 "
+                                 f"consecutive inputs of a linear under one scale byte)")
     if kv not in (None, "fp32", "int8") or (kv == "fp32" and dtype != "fp32"):
         raise ValueError(f"kv must be None (the tenant's dtype), 'fp32' (fp32 tenants) or 'int8', got {kv!r}")
     if kv == "int8" and dtype != "fp32":
         raise ValueError("int8 K / V caches are an fp32 tenant's storage format: dtype must be 'fp32'")
-    q8, kvq8 = weights == "int8", kv == "int8"
+    q8, mx4, kvq8 = weights == "int8", weights == "mxfp4", kv == "int8"
+    quant = q8 or mx4   # a quantized tenant: q / k / v and gate / up merged by the builder, the head a copy of its own
     cfg = model.config
     sd = {k: v.detach().float().cpu().numpy() for k, v in model.state_dict().items()}
     d, nh = cfg.hidden_size, cfg.num_attention_heads
@@ -445,20 +470,22 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     ring = {"window": window, "limit": max_len} if ring_slots else {}
     payload = b""
     for seq, reset, verify in chunks:
-        b = Builder(f"{'mixtral' if moe else 'llama'}-h{d}-l{cfg.num_hidden_layers}-{dtype}{'-q8' if q8 else ''}{'-kvq8' if kvq8 else ''}-"
+        b = Builder(f"{'mixtral' if moe else 'llama'}-h{d}-l{cfg.num_hidden_layers}-{dtype}{'-q8' if q8 else '-mx4' if mx4 else ''}{'-kvq8' if kvq8 else ''}-"
                     f"{'stop-' if stopping else ''}{'spec-' if speculate else ''}{'lora-' if stacked else ''}"
                     f"{'prefill' if reset else 'verify' if verify else 'step'}{seq}")
         ids = b.input("input_ids", [batch, seq], "i32")
         P = lambda k: b.param(k, sd[k], dtype)  # noqa: E731
 
         def lin(x, name, *keys, out=None):
-            """x @ W^T: a ``linear`` over the weight ``name``; for int8 weights a ``linear_q8`` over
-            the rows of ``keys``' weights (default: ``name``'s), merged and then quantized -- with a
-            scale per row that equals quantizing each and merging, so no compiler pass has to merge."""
-            if not q8:
+            """x @ W^T: a ``linear`` over the weight ``name``; for int8 weights a ``linear_q8`` (MXFP4: a
+            ``linear_mx4``) over the rows of ``keys``' weights (default: ``name``'s), merged and then
+            quantized -- with a scale per row (per block of a row) that equals quantizing each and
+            merging, so no compiler pass has to merge."""
+            if not quant:
                 return b.op("linear", x, P(name), out=out)
-            wq, sc = b.param_q8(name, np.concatenate([sd[k] for k in keys or (name,)], axis=0))
-            return b.op("linear_q8", x, wq, sc, out=out)
+            w = np.concatenate([sd[k] for k in keys or (name,)], axis=0)
+            wq, sc = b.param_mx4(name, w) if mx4 else b.param_q8(name, w)
+            return b.op("linear_mx4" if mx4 else "linear_q8", x, wq, sc, out=out)
 
         def adapted(y, x, group):
             """y (the group's merged linear of x) plus its adapters' delta, where the group has any."""
@@ -471,7 +498,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
             """An adapted group's projections as ONE linear over the members' rows (the arrangement int8
             weights use): merging and adapters commute, so the delta is added to the merged output."""
             keys = [group.rsplit(".", 2)[0] + "." + m + ".weight" for m in stacked[group][2]]
-            if q8 or len(keys) == 1:
+            if quant or len(keys) == 1:
                 return lin(x, group + ".weight" if len(keys) > 1 else keys[0], *(keys if len(keys) > 1 else ()))
             return b.op("linear", x, b.param(group + ".weight", np.concatenate([sd[k] for k in keys], axis=0), dtype))
 
@@ -493,7 +520,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
         for i in range(cfg.num_hidden_layers):
             pf = f"model.layers.{i}."
             y = b.op("rmsnorm", h, P(pf + "input_layernorm.weight"), eps=eps)
-            if q8 or pf + "self_attn.qkv_proj" in stacked:
+            if quant or pf + "self_attn.qkv_proj" in stacked:
                 if pf + "self_attn.qkv_proj" in stacked:
                     qkv = adapted(merged(y, pf + "self_attn.qkv_proj"), y, pf + "self_attn.qkv_proj")
                 else:
@@ -516,7 +543,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
                 h = b.op("add", b.moe(y, P(pf + "mlp.gate.weight"), P(pf + "mlp.experts.gate_up_proj"),
                                       P(pf + "mlp.experts.down_proj"), cfg.num_experts_per_tok), h)
                 continue
-            if q8 or pf + "mlp.gate_up_proj" in stacked:
+            if quant or pf + "mlp.gate_up_proj" in stacked:
                 if pf + "mlp.gate_up_proj" in stacked:
                     gu = adapted(merged(y, pf + "mlp.gate_up_proj"), y, pf + "mlp.gate_up_proj")
                 else:
@@ -533,7 +560,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
             h = b.op("slice", h, dim=1, start=seq - 1, end=seq)
         h = b.op("rmsnorm", h, P("model.norm.weight"), eps=eps)
         # a tied head reads the embedding table: quantized, it is a copy of its own (the table stays fp32)
-        logits = lin(h, "lm_head.weight", head, out="logits") if q8 else lin(h, head, out="logits")
+        logits = lin(h, "lm_head.weight", head, out="logits") if quant else lin(h, head, out="logits")
         if verify:
             # the draw after every row, the drafts it confirms (+ 1), the history and the counter
             # advanced by that many, and the next step's input: the new pending token and its drafts
@@ -571,8 +598,9 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
 
 def _refuse_mixtral(cfg, max_len, batch, dtype, weights, speculate, adapters, x_bytes) -> None:
     """What a Mixtral tenant does not take (``llama_decode_programs``), each with its rule."""
-    if weights == "int8":
-        raise ValueError("a Mixtral tenant's weights are fp32: weights='int8' is not taken (no quantized experts yet)")
+    if weights in ("int8", "mxfp4"):
+        raise ValueError(f"a Mixtral tenant's weights are fp32: weights={weights!r} is not taken (no quantized experts "
+                         f"yet)")
     if dtype != "fp32":
         raise ValueError(f"a Mixtral tenant is fp32 (the moe op takes an fp32 x and fp32 experts): dtype={dtype!r} "
                          f"is not taken")
@@ -593,12 +621,17 @@ def _refuse_mixtral(cfg, max_len, batch, dtype, weights, speculate, adapters, x_
                              f"kernels")
 
 
-def dequantized_llama(model):
+def dequantized_llama(model, weights: str = "int8"):
     """A deep copy of the HF model whose linear weights (attention and MLP
     projections, the LM head -- untied from the embedding table, which stays
-    fp32) are ``dequantize(quantize(w))`` row by row: the model an int8
-    tenant of ``model`` computes (``llama_decode_programs(weights="int8")``),
-    for tests and users to compare against."""
+    fp32) are ``dequantize(quantize(w))`` row by row (``weights="mxfp4"``: block
+    by block, ``quantize_rows_mx4``): the model an int8 (MXFP4) tenant of
+    ``model`` computes (``llama_decode_programs(weights=...)``), for tests and
+    users to compare against."""
+    if weights not in ("int8", "mxfp4"):
+        raise ValueError(f"dequantized_llama: weights must be 'int8' or 'mxfp4', got {weights!r}")
+    roundtrip = ((lambda w: dequantize_rows_mx4(*quantize_rows_mx4(w))) if weights == "mxfp4"
+                 else (lambda w: dequantize_rows_q8(*quantize_rows_q8(w))))
     import copy
 
     import torch
@@ -612,7 +645,7 @@ def dequantized_llama(model):
         for name, p in m.named_parameters():
             if name == "lm_head.weight" or (name.endswith("_proj.weight") and name.split(".")[-2] in _Q8_LINEARS):
                 w = head if name == "lm_head.weight" else p.detach().float().cpu().numpy()
-                p.copy_(torch.from_numpy(dequantize_rows_q8(*quantize_rows_q8(w))).to(p.dtype))
+                p.copy_(torch.from_numpy(roundtrip(w)).to(p.dtype))
     return m
 
 

@@ -159,6 +159,12 @@ _SIGS = {
     "nos_gemv_q8_partials": [c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                              c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "nos_dequant_q8": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    # decode.hip: MXFP4 weight-only linears (E2M1 codes, an E8M0 scale byte per 32 k)
+    "nos_gemv_mx4": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                     c_int, c_int, c_int, c_int, c_int, c_float, c_void_p],
+    "nos_gemv_mx4_partials": [c_void_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                              c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "nos_dequant_mx4": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
     # decode.hip: multi-adapter LoRA (the shrink launch, the GEMVs with the adapter epilogue)
     "nos_lora_shrink": [c_void_p, c_int, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_void_p, c_ll, c_int, c_void_p,
                         c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p],

@@ -1856,6 +1856,160 @@ def linear_q8(x: torch.Tensor, wq: torch.Tensor, wscale: torch.Tensor, bias: tor
     return y.view(shape)
 
 
+# ------------------------------------------------------------------ MXFP4 weight-only linears
+MX4_BLOCK = 32   # consecutive k of a row under one E8M0 scale byte (podserver.program.builder.quantize_rows_mx4)
+_MX4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0)
+
+
+def _mx4_weight_ok(wq: torch.Tensor, wscale: torch.Tensor) -> bool:
+    return (wq.dtype == torch.uint8 and wscale.dtype == torch.uint8 and wq.dim() == 2 and wscale.dim() == 2
+            and wq.shape[0] == wscale.shape[0] and wq.shape[1] * 2 == wscale.shape[1] * MX4_BLOCK)
+
+
+def _dequant_mx4_ref(wq: torch.Tensor, wscale: torch.Tensor) -> torch.Tensor:
+    """``builder.dequantize_rows_mx4`` in torch: fp32 [N, K] = elem x 2^(e - 127), exact."""
+    if not _mx4_weight_ok(wq, wscale):
+        raise ValueError(f"an MXFP4 weight is codes u8 [N, K / 2] and scales u8 [N, K / {MX4_BLOCK}], got "
+                         f"{tuple(wq.shape)} {wq.dtype} and {tuple(wscale.shape)} {wscale.dtype}")
+    table = torch.tensor(_MX4_VALUES, dtype=torch.float32, device=wq.device)
+    idx = torch.stack(((wq & 15).long(), (wq >> 4).long()), dim=-1).reshape(wq.shape[0], -1)
+    e = wscale.to(torch.int32).repeat_interleave(MX4_BLOCK, dim=1) - 127
+    return torch.ldexp(table[idx], e)
+
+
+def linear_mx4_ref(x, wq, wscale, bias=None, act=None, residual=None, rms_eps: float = 0.0, gamma=None,
+                   glu: bool = False, dtype: torch.dtype = torch.float32):
+    """What an MXFP4 weight-only linear means, in ``dtype`` arithmetic:
+    ``act(x' @ W.T + bias) + residual`` with W = ``dequantize_rows_mx4(wq, wscale)`` formed in fp32
+    (exact: the storage format's definition), ``x' = rmsnorm(x) * gamma`` when ``rms_eps`` > 0 and
+    ``silu(gate) * up`` of the two halves of the columns for ``glu``."""
+    wf = _dequant_mx4_ref(wq, wscale).to(dtype)
+    xf = x.to(dtype)
+    if rms_eps:
+        xf = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + rms_eps)
+        if gamma is not None:
+            xf = xf * gamma.to(dtype)
+    y = F.linear(xf, wf, None if bias is None else bias.to(dtype))
+    if glu:
+        h = y.shape[-1] // 2
+        y = F.silu(y[..., :h]) * y[..., h:]
+    y = F.silu(y) if act == "silu" else _act(y, act)
+    return y if residual is None else y + residual.to(dtype).reshape(y.shape)
+
+
+def gemv_mx4_ok(x2: torch.Tensor, wq: torch.Tensor) -> bool:
+    """Whether the MXFP4 GEMV takes this [M, K] fp32 x [N, K / 2] u8 product."""
+    M, K = x2.shape
+    return (x2.is_cuda and 0 < M <= GEMV_MAX_ROWS and K % MX4_BLOCK == 0 and M * K * 4 <= GEMV_X_BYTES
+            and x2.stride(-1) == 1 and x2.stride(0) % 4 == 0 and x2.dtype == torch.float32 and x2.data_ptr() % 16 == 0
+            and wq.dtype == torch.uint8 and wq.dim() == 2 and wq.shape[1] * 2 == K and wq.stride(-1) == 1
+            and wq.stride(0) % 16 == 0 and wq.data_ptr() % 16 == 0)
+
+
+def _mx4_operands(wq, wscale, gamma, bias, residual, M, N, K):
+    if (not _mx4_weight_ok(wq, wscale) or wq.shape[1] * 2 != K or (bias is not None and bias.numel() != N)
+            or (gamma is not None and gamma.numel() != K) or (residual is not None and residual.numel() != M * N)):
+        raise ValueError(f"linear_mx4: codes u8 [{N}, {K // 2}], wscale u8 [{N}, {K // MX4_BLOCK}], bias [{N}], gamma "
+                         f"[{K}] and residual [{M}, {N}] required")
+    sc = wscale if wscale.stride(-1) == 1 else wscale.contiguous()
+    g = None if gamma is None else gamma.float().contiguous()
+    b = None if bias is None else bias.float().contiguous()
+    r = None if residual is None else residual.reshape(M, N).float()
+    if r is not None and r.stride(-1) != 1:
+        r = r.contiguous()
+    return sc, g, b, r
+
+
+def gemv_mx4(x2: torch.Tensor, wq: torch.Tensor, wscale: torch.Tensor, bias: torch.Tensor | None = None,
+             act: str | None = None, residual: torch.Tensor | None = None, rms_eps: float = 0.0,
+             gamma: torch.Tensor | None = None, glu: bool = False) -> torch.Tensor:
+    """y [M, N] = act(x' [M, K] W^T + b) + R for M <= 8 (:func:`gemv_mx4_ok`;
+    :func:`linear_mx4_ref` defines W, x' and ``glu``): the weight-streaming kernel of an MXFP4 tenant's
+    decode step, 4.25 bits of HBM per weight, fp32 FMAs on the dequantized values.  Every scale byte
+    must lie in [2, 252] (a registration checks it; this call does not read them)."""
+    M, K = x2.shape
+    N = wq.shape[0]
+    if not gemv_mx4_ok(x2, wq) or (glu and N % 2):
+        raise ValueError(f"gemv_mx4: x {tuple(x2.shape)} {x2.dtype} and codes {tuple(wq.shape)} {wq.dtype} are not a "
+                         f"product the MXFP4 GEMV takes (gemv_mx4_ok)")
+    sc, g, b, r = _mx4_operands(wq, wscale, gamma, bias, residual, M, N, K)
+    y = torch.empty((M, N // 2 if glu else N), dtype=torch.float32, device=x2.device)
+    _lib.check(_lib.lib().nos_gemv_mx4(x2.data_ptr(), x2.stride(0), wq.data_ptr(), wq.stride(0), sc.data_ptr(),
+                                       sc.stride(0), _ptr(g), _ptr(b), _ptr(r), r.stride(0) if r is not None else 0,
+                                       y.data_ptr(), y.stride(0), M, N, K, _q8_epi(b, act, r, glu), float(rms_eps),
+                                       _stream()), "nos_gemv_mx4")
+    return y
+
+
+def gemv_mx4_partials(p: DecodePartials, wq: torch.Tensor, wscale: torch.Tensor, bias: torch.Tensor | None = None,
+                      act: str | None = None, residual: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`gemv_mx4` whose x [B, H x D] is the decode attention's output, combined from its split
+    partials in the kernel's x staging (as :func:`gemv_partials`): y [B, N] fp32."""
+    B, _, H, D = p.shape
+    K = H * D
+    N = wq.shape[0]
+    if (wq.dtype != torch.uint8 or wq.dim() != 2 or wq.shape[1] * 2 != K or wq.stride(-1) != 1 or wq.stride(0) % 16
+            or wq.data_ptr() % 16 or B > GEMV_MAX_ROWS):
+        raise ValueError(f"gemv_mx4_partials: codes {tuple(wq.shape)} {wq.dtype} for x [{B}, {K}]")
+    sc, _, b, r = _mx4_operands(wq, wscale, None, bias, residual, B, N, K)
+    y = torch.empty((B, N), dtype=torch.float32, device=wq.device)
+    _lib.check(_lib.lib().nos_gemv_mx4_partials(p.ws.data_ptr(), p.ws.numel(), p.NS, p.G, p.G, p.Hkv, D, wq.data_ptr(),
+                                                wq.stride(0), sc.data_ptr(), sc.stride(0), _ptr(b), _ptr(r),
+                                                r.stride(0) if r is not None else 0, y.data_ptr(), y.stride(0), B, N, K,
+                                                _q8_epi(b, act, r, False), _stream()), "nos_gemv_mx4_partials")
+    return y
+
+
+def dequant_mx4(wq: torch.Tensor, wscale: torch.Tensor) -> torch.Tensor:
+    """``dequantize_rows_mx4(wq, wscale)`` as a fresh fp32 [N, K] tensor, bit for bit (scale bytes in
+    [2, 252]); on the GPU by the GEMV's own conversion (decode.hip ``nos_dequant_mx4``)."""
+    if not wq.is_cuda:
+        return _dequant_mx4_ref(wq, wscale)
+    if not _mx4_weight_ok(wq, wscale) or wq.stride(-1) != 1 or wq.stride(0) % 4 or wq.data_ptr() % 4:
+        raise ValueError(f"dequant_mx4: codes u8 [N, K / 2] with 4-byte aligned rows and scales u8 [N, K / {MX4_BLOCK}], "
+                         f"got {tuple(wq.shape)} {wq.dtype} and {tuple(wscale.shape)} {wscale.dtype}")
+    N, K = wq.shape[0], wq.shape[1] * 2
+    out = torch.empty((N, K), dtype=torch.float32, device=wq.device)
+    sc = wscale if wscale.stride(-1) == 1 else wscale.contiguous()
+    _lib.check(_lib.lib().nos_dequant_mx4(wq.data_ptr(), wq.stride(0), sc.data_ptr(), sc.stride(0), out.data_ptr(), K,
+                                          N, K, _stream()), "nos_dequant_mx4")
+    return out
+
+
+def linear_mx4(x: torch.Tensor, wq: torch.Tensor, wscale: torch.Tensor, bias: torch.Tensor | None = None,
+               act: str | None = None, residual: torch.Tensor | None = None, rms_eps: float = 0.0,
+               gamma: torch.Tensor | None = None, glu: bool = False) -> torch.Tensor:
+    """The MXFP4 weight-only linear (:func:`linear_mx4_ref`) of fp32 x [..., K]: at most
+    :data:`GEMV_MAX_ROWS` rows that fit :data:`GEMV_X_BYTES` on :func:`gemv_mx4`; otherwise the weight
+    is dequantized into a transient fp32 buffer (freed with the call's other intermediates, never
+    cached) for the run-time-split h3 product, after the ``rmsnorm`` kernel when there is a prologue.
+    CPU tensors: the reference."""
+    if not x.is_cuda:
+        return linear_mx4_ref(x, wq, wscale, bias, act, residual, rms_eps, gamma, glu)
+    if x.dtype != torch.float32:
+        raise ValueError(f"linear_mx4 takes an fp32 x, got {x.dtype}")
+    K, N = x.shape[-1], wq.shape[0]
+    x2 = x.reshape(-1, K)
+    if x2.stride(-1) != 1 or x2.stride(0) % 4 or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.shape[0]
+    shape = (*x.shape[:-1], N // 2 if glu else N)
+    if M <= GEMV_MAX_ROWS and gemv_mx4_ok(x2, wq):
+        return gemv_mx4(x2, wq, wscale, bias, act, residual, rms_eps, gamma, glu).view(shape)
+    if rms_eps:
+        x2 = rmsnorm(x2, gamma if gamma is not None else torch.ones(K, dtype=torch.float32, device=x.device), rms_eps)
+    r = None if residual is None else residual.reshape(M, N).float().contiguous()
+    gemm_act = act if act in ("gelu", "relu") else None   # the GEMM's epilogue; silu: a pass of its own
+    y = mm(x2, dequant_mx4(wq, wscale), b_t=True, bias=bias, act=gemm_act, residual=r if act == gemm_act else None)
+    if glu:
+        return _glu_halves(y).view(shape)
+    if act != gemm_act:
+        y = unary(y, act, torch.float32)
+        if r is not None:
+            y = y + r
+    return y.view(shape)
+
+
 def _glu_halves(y: torch.Tensor) -> torch.Tensor:
     """silu(gate) * up of the two column halves of a merged [gate; up] product."""
     h = y.shape[-1] // 2
@@ -2098,7 +2252,8 @@ def set_attention_h3g_kvsplit(n: int) -> None:
 
 __all__ = ["glu", "kv_write", "rotary_at", "sdpa_cache", "pos_update", "argmax", "sample", "sample_row_ref",
            "sampling_ctl", "philox4x32", "gemv", "gemv_ok", "gemv_partials", "gemv_q8", "gemv_q8_ok", "gemv_q8_partials",
-           "dequant_q8", "linear_q8", "linear_q8_ref", "lora", "lora_ref", "lora_shrink", "lora_shrink_ref", "lora_expand_ref", "linear_lora",
+           "dequant_q8", "linear_q8", "linear_q8_ref", "gemv_mx4", "gemv_mx4_ok", "gemv_mx4_partials", "dequant_mx4",
+           "linear_mx4", "linear_mx4_ref","lora", "lora_ref", "lora_shrink", "lora_shrink_ref", "lora_expand_ref", "linear_lora",
            "LORA_MAX_RANK", "moe", "moe_ref", "moe_route", "moe_glu", "moe_down", "moe_route_ref", "moe_glu_ref",
            "moe_down_ref", "MOE_MAX_EXPERTS", "MOE_MAX_TOP_K",
            "DecodePartials", "conv2d", "matmul", "sdpa", "linear_rms", "embedding", "rmsnorm", "softmax", "rotary", "conv2d_ref",

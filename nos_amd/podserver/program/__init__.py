@@ -21,7 +21,10 @@ Values are SSA names; nodes are listed in execution order.  Wire dtypes are
 ``fp32`` (IEEE float32, little endian), ``bf16`` (the upper 16 bits of a
 float32, little-endian uint16) and, for the weight of a ``linear_q8`` node
 only, ``i8`` (two's-complement int8 rows with one fp32 scale per row:
-weight-only quantization, a storage format -- the math stays fp32).
+weight-only quantization, a storage format -- the math stays fp32) and,
+for inputs 1 and 2 of a ``linear_mx4`` node only, ``u8`` (OCP MXFP4: two
+4-bit E2M1 codes a byte, and one E8M0 scale byte per 32 consecutive inputs
+of a row, each in [2, 252]).
 
 :func:`parse` validates a program completely before anything is allocated:
 the op whitelist, every attribute, the topological order and the exact shape
@@ -84,8 +87,8 @@ Modules (each new op touches them in this order):
 """
 from __future__ import annotations
 
-from .builder import (Builder, bf16_bits, bf16_to_f32, dequantize_rows_q8, load_program, mlp_program,
-                      quantize_rows_q8, save_program)
+from .builder import (Builder, bf16_bits, bf16_to_f32, dequantize_rows_mx4, dequantize_rows_q8, load_program,
+                      mlp_program, quantize_rows_mx4, quantize_rows_q8, save_program)
 from .compile import Lowered, _Step
 from .execute import CompiledProgram, _relayout, _rows
 from .graph import Program, _attn_ws, _workspace
@@ -97,4 +100,4 @@ from .validate import _infer, parse, parse_variants
 
 __all__ = ["FORMAT", "Program", "CompiledProgram", "ProgramError", "Builder", "parse", "parse_variants", "mlp_program",
            "bf16_bits", "save_program", "load_program", "bf16_to_f32", "OPS", "torch_dtype", "Value", "Node",
-           "Lowered", "quantize_rows_q8", "dequantize_rows_q8"]
+           "Lowered", "quantize_rows_q8", "dequantize_rows_q8", "quantize_rows_mx4", "dequantize_rows_mx4"]

@@ -40,6 +40,55 @@ def dequantize_rows_q8(q: np.ndarray, scale: np.ndarray) -> np.ndarray:
     return np.asarray(q).astype(np.float32) * np.asarray(scale, dtype=np.float32)[:, None]
 
 
+MX4_BLOCK = 32                   # consecutive k of a row that share one E8M0 scale byte
+MX4_SCALE_MIN, MX4_SCALE_MAX = 2, 252   # the scale bytes in use: every dequantized value is a normal, finite fp32
+# the E2M1 element of each 4-bit code: bit 3 the sign, bits 2..0 the magnitude
+MX4_VALUES = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0], np.float32)
+
+
+def quantize_rows_mx4(w: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """OCP Microscaling MXFP4 of a weight [N, K], K % 32 == 0: 4-bit E2M1 elements, each block of 32
+    consecutive k of a row under one E8M0 power-of-two scale.  The scale byte of a block is ``e =
+    clamp(floor(log2(max|v|)) - 2 + 127, 2, 252)`` (the exponent taken exactly, from ``frexp``; 127 for
+    an all-zero block; 255, the format's NaN, never).  ``v / 2^(e - 127)`` is rounded to the nearest of
+    +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, ties to the even code, saturating at +-6; the sign is the code's
+    bit 3.  Element 2 i sits in the low nibble of byte i, element 2 i + 1 in the high one.  Returns
+    (codes u8 [N, K / 2], scales u8 [N, K / 32]); :func:`dequantize_rows_mx4` gives the weight the
+    server computes with."""
+    a = np.ascontiguousarray(w, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] % MX4_BLOCK:
+        raise ValueError(f"quantize_rows_mx4 takes a [N, K] weight with K % {MX4_BLOCK} == 0 (a scale byte per "
+                         f"{MX4_BLOCK} consecutive k), got {a.shape}")
+    if not np.isfinite(a).all():
+        raise ValueError("quantize_rows_mx4 takes finite weights")
+    N, K = a.shape
+    blk = a.reshape(N, K // MX4_BLOCK, MX4_BLOCK)
+    amax = np.abs(blk).max(axis=2) if K else np.zeros((N, 0), np.float32)
+    _, ex = np.frexp(amax)                       # amax = m 2^ex with 0.5 <= m < 1: floor(log2) = ex - 1
+    e = np.where(amax > 0, np.clip(ex.astype(np.int64) - 3 + 127, MX4_SCALE_MIN, MX4_SCALE_MAX), 127)
+    mag = np.abs(np.ldexp(blk.astype(np.float64), (127 - e)[:, :, None]))   # exact in fp64
+    # the midpoints between neighbouring magnitudes; a tie goes to the even code of the two
+    code = ((mag > 0.25).astype(np.uint8) + (mag >= 0.75) + (mag > 1.25) + (mag >= 1.75) + (mag > 2.5)
+            + (mag >= 3.5) + (mag > 5.0)).astype(np.uint8)
+    code |= (np.signbit(blk).astype(np.uint8) << 3)
+    code = code.reshape(N, K)
+    return (code[:, 0::2] | (code[:, 1::2] << 4)).astype(np.uint8), e.astype(np.uint8)
+
+
+def dequantize_rows_mx4(codes: np.ndarray, scales: np.ndarray) -> np.ndarray:
+    """``elem * 2^(e - 127)`` as fp32 [N, K] (exact: a power-of-two scale of a 2-bit significand): the
+    weight a ``linear_mx4`` node means."""
+    c = np.asarray(codes, dtype=np.uint8)
+    s = np.asarray(scales, dtype=np.uint8)
+    if c.ndim != 2 or s.ndim != 2 or c.shape[0] != s.shape[0] or c.shape[1] * 2 != s.shape[1] * MX4_BLOCK:
+        raise ValueError(f"dequantize_rows_mx4 takes codes [N, K / 2] and scales [N, K / {MX4_BLOCK}], got {c.shape} "
+                         f"and {s.shape}")
+    el = np.empty((c.shape[0], c.shape[1] * 2), np.float32)
+    el[:, 0::2] = MX4_VALUES[c & 15]
+    el[:, 1::2] = MX4_VALUES[c >> 4]
+    return np.ldexp(el, np.repeat(s.astype(np.int32) - 127, MX4_BLOCK, axis=1)).astype(np.float32)
+
+
 class Builder:
     """Assemble a wire program with numpy only (the pod side never imports
     torch).  ``param`` appends a weight to the payload; op methods append
@@ -83,6 +132,25 @@ class Builder:
             self.chunks.append(b"\0" * pad)
             self.offset += pad
         return name + ".q8", self.param(name + ".scale", scale)
+
+    def _param_u8(self, name: str, a: np.ndarray) -> str:
+        raw = a.tobytes()
+        self.params.append({"name": name, "shape": list(a.shape), "dtype": "u8", "offset": self.offset,
+                            "nbytes": len(raw)})
+        self.chunks.append(raw)
+        self.offset += len(raw)
+        pad = -self.offset % 4   # the params after it stay 4-byte aligned in the payload
+        if pad:
+            self.chunks.append(b"\0" * pad)
+            self.offset += pad
+        return name
+
+    def param_mx4(self, name: str, w_fp32: np.ndarray) -> tuple[str, str]:
+        """An fp32 weight [N, K] stored as MXFP4 (:func:`quantize_rows_mx4`): the u8 params
+        ``name + ".mx4"`` (codes [N, K / 2]) and ``name + ".e8m0"`` (block scales [N, K / 32]) a
+        ``linear_mx4`` node takes."""
+        codes, scales = quantize_rows_mx4(w_fp32)
+        return self._param_u8(name + ".mx4", codes), self._param_u8(name + ".e8m0", scales)
 
     def state(self, name: str, shape, dtype: str = "fp32") -> str:
         """A state buffer (zero at registration, kept across requests)."""

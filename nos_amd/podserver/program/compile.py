@@ -9,7 +9,7 @@ import os
 from dataclasses import dataclass, field
 
 from .graph import Program
-from .ir import BINARY, NATIVE_KINDS, NEVER_FOLD, SPEC_KINDS, STATE_WRITERS, STOP_KINDS, UNARY, ProgramError, torch_dtype
+from .ir import BINARY, NATIVE_KINDS, NEVER_FOLD, QUANT_LINEARS, SPEC_KINDS, STATE_WRITERS, STOP_KINDS, UNARY, ProgramError, torch_dtype
 from .reference import _eager
 
 
@@ -113,6 +113,7 @@ class Lowered:
         self._derived = None
         self.stats["kernels"] = sum(1 for s in self.steps if s.kind in NATIVE_KINDS)
         self.stats["q8_linears"] = sum(1 for s in self.steps if s.kind == "linear_q8")
+        self.stats["mx4_linears"] = sum(1 for s in self.steps if s.kind == "linear_mx4")
         if "stop_steps_fused" in self.stats:   # a stopping program: the launches its stopping ops cost
             self.stats["stop_launches"] = sum(1 for s in self.steps if s.kind in STOP_KINDS
                                               or (s.kind == "pos_add" and len(s.inputs) == 2))
@@ -574,7 +575,7 @@ class Lowered:
         output dim ``d``, as (input index, input dim); None: not row-wise in d."""
         if p.kind in UNARY or p.kind == "cast":
             return [(0, d)]
-        if p.kind in ("linear", "linear_q8", "layernorm", "rmsnorm", "moe"):   # moe: each row routes for itself
+        if p.kind in ("linear", *QUANT_LINEARS, "layernorm", "rmsnorm", "moe"):   # moe: each row routes for itself
             return [(0, d)] if len(self._shape(p.inputs[0])) == r else None
         if p.kind in BINARY:
             plan = []
@@ -979,14 +980,14 @@ class Lowered:
         """rmsnorm -> linear (its only consumer, constant weights) becomes one
         ``linear_rms``: gamma folded into the weight, the row statistics in
         the h3 split pre-pass (ops.tenant.linear_rms).  rmsnorm -> ``linear_q8``
-        keeps its int8 weight as it is (per-row scales leave no room for a
-        per-column gamma, and no fp32 copy is made): the step takes ``eps`` and
+        or ``linear_mx4`` keeps its quantized weight as it is (per-row or per-block
+        scales leave no room for a per-column gamma, and no fp32 copy is made): the step takes ``eps`` and
         the gamma tensor as one more input, applied in the GEMV's x staging."""
         uses = self._consumers(steps, self.outputs)
         by_out = {s.output: s for s in steps}
-        drop, n, nq = set(), 0, 0
+        drop, n, nq = set(), 0, {k: 0 for k in QUANT_LINEARS}
         for s in steps:
-            if s.kind not in ("linear", "linear_q8") or s.inputs[0] not in by_out:
+            if s.kind not in ("linear", *QUANT_LINEARS) or s.inputs[0] not in by_out:
                 continue
             rn = by_out[s.inputs[0]]
             sh = self._shrink_of(s, by_out)   # an adapted linear's shrink reads the norm too, and folds with it
@@ -996,11 +997,11 @@ class Lowered:
             if sh is not None:   # the same statistic and gamma in the shrink's x (gamma as a pointer)
                 sh.inputs = [rn.inputs[0]] + sh.inputs[1:] + [rn.inputs[1]]
                 sh.attrs = {**sh.attrs, "eps": rn.attrs.get("eps", 1e-5), "gamma": True}
-            if s.kind == "linear_q8":
+            if s.kind in QUANT_LINEARS:
                 s.inputs = [rn.inputs[0]] + s.inputs[1:] + [rn.inputs[1]]
                 s.attrs = {**s.attrs, "eps": rn.attrs.get("eps", 1e-5), "gamma": True}
                 drop.add(rn.output)
-                nq += 1
+                nq[s.kind] += 1
                 continue
             w, g = self.consts[s.inputs[1]], self.consts[rn.inputs[1]]
             base = f"{s.output}::rms"
@@ -1012,7 +1013,8 @@ class Lowered:
                        **{k: v for k, v in s.attrs.items() if k.startswith("lora")}}
             drop.add(rn.output)
             n += 1
-        self.stats["rmsnorm_folded"], self.stats["q8_rms_prologue"] = n, nq
+        self.stats["rmsnorm_folded"], self.stats["q8_rms_prologue"] = n, nq["linear_q8"]
+        self.stats["mx4_rms_prologue"] = nq["linear_mx4"]
         return [s for s in steps if s.output not in drop]
 
     def _fuse_epilogues(self, steps: list[_Step]) -> list[_Step]:
@@ -1026,7 +1028,7 @@ class Lowered:
             s.inputs = [rename.get(i, i) for i in s.inputs]
             src = by_out.get(s.inputs[0]) if s.inputs else None
             if (s.kind in ("gelu", "relu") and src is not None
-                    and src.kind in ("linear", "linear_ln", "linear_rms", "linear_q8")
+                    and src.kind in ("linear", "linear_ln", "linear_rms", *QUANT_LINEARS)
                     and uses.get(src.output) == 1 and not src.attrs.get("act") and "residual" not in src.attrs):
                 src.attrs["act"] = s.kind
                 rename[s.output] = src.output
@@ -1046,7 +1048,7 @@ class Lowered:
                 a, b = s.inputs
                 for prod, other in ((a, b), (b, a)):
                     p = by_out.get(prod)
-                    if (p is not None and p.kind in ("linear", "conv2d", "linear_q8") and uses.get(prod) == 1
+                    if (p is not None and p.kind in ("linear", "conv2d", *QUANT_LINEARS) and uses.get(prod) == 1
                             and "residual" not in p.attrs
                             and self._shape(prod) == self._shape(s.output) == self._shape(other)
                             and self._dtype(prod) == self._dtype(other) and other != prod):
@@ -1158,7 +1160,7 @@ class Lowered:
 
     def _fuse_gemv_glu(self, steps: list[_Step]) -> list[_Step]:
         """Decode rows (at most 8, known statically): ``glu(silu)`` of the two
-        column halves of a merged gate-up ``linear_rms`` (or ``linear_q8``)
+        column halves of a merged gate-up ``linear_rms`` (or ``linear_q8`` / ``linear_mx4``)
         becomes that GEMV's epilogue (each wave computes gate columns and their
         up columns), one launch instead of two."""
         from ...ops.tenant import GEMV_MAX_ROWS
@@ -1167,7 +1169,7 @@ class Lowered:
             return steps
         uses = self._consumers(steps, self.outputs)
         by_out = {s.output: s for s in steps}
-        drop, n, nq = set(), 0, 0
+        drop, n, nq = set(), 0, {k: 0 for k in QUANT_LINEARS}
         for s in steps:
             if s.kind != "glu" or s.attrs.get("op") != "silu":
                 continue
@@ -1176,9 +1178,9 @@ class Lowered:
                 continue
             lin = by_out.get(a.inputs[0])
             shp = tuple(self._shape(lin.output)) if lin is not None else ()
-            q8 = lin is not None and lin.kind == "linear_q8"
+            q8 = lin is not None and lin.kind in QUANT_LINEARS
             plain = 3 + bool(lin.attrs.get("gamma")) if q8 else 2      # its inputs without a bias or a residual
-            if (lin is None or lin.kind not in ("linear_rms", "linear_q8") or lin.attrs.get("act")
+            if (lin is None or lin.kind not in ("linear_rms", *QUANT_LINEARS) or lin.attrs.get("act")
                     or len(lin.inputs) > plain or uses.get(lin.output) != 2 or uses.get(a.output) != 1 or uses.get(b.output) != 1
                     or math.prod(shp[:-1]) > GEMV_MAX_ROWS or shp[-1] % 2
                     or any(t.attrs.get("dim") not in (-1, len(shp) - 1) for t in (a, b))
@@ -1192,8 +1194,11 @@ class Lowered:
             for t in steps:
                 t.inputs = [rename.get(i, i) for i in t.inputs]
             self.outputs = [rename.get(o, o) for o in self.outputs]
-            n, nq = n + (not q8), nq + q8
-        self.stats["gemv_glu_fused"], self.stats["q8_glu_fused"] = n, nq
+            n += not q8
+            if q8:
+                nq[lin.kind] += 1
+        self.stats["gemv_glu_fused"], self.stats["q8_glu_fused"] = n, nq["linear_q8"]
+        self.stats["mx4_glu_fused"] = nq["linear_mx4"]
         return [s for s in steps if id(s) not in drop]
 
     def _merge_kv_writes(self, steps: list[_Step]) -> list[_Step]:
@@ -1296,7 +1301,7 @@ class Lowered:
         for t in steps:
             for i in t.inputs:
                 by_input.setdefault(i, []).append(t)
-        drop, n, nq = set(), 0, 0
+        drop, n, nq = set(), 0, {k: 0 for k in QUANT_LINEARS}
         for s in steps:
             if s.kind != "sdpa_cache" or s.attrs.get("sync") or uses.get(s.output) != 1:
                 continue
@@ -1307,14 +1312,14 @@ class Lowered:
             if r is None or r.kind != "reshape":
                 continue
             readers = by_input.get(r.output, [])
-            lin = next((t for t in readers if t.kind in ("linear", "linear_q8")), None)
+            lin = next((t for t in readers if t.kind in ("linear", *QUANT_LINEARS)), None)
             sh = self._shrink_of(lin, {t.output: t for t in readers}) if lin is not None else None
             if uses.get(r.output) != 1 + (sh is not None):   # an adapted projection's shrink reads x too
                 continue
             rs = tuple(self._shape(r.output))
             if rs[0] != shp[0] or math.prod(rs[1:]) != shp[2] * shp[3] or rs[-1] != shp[2] * shp[3]:
                 continue
-            if (lin is None or lin.kind not in ("linear", "linear_q8") or lin.inputs[0] != r.output
+            if (lin is None or lin.kind not in ("linear", *QUANT_LINEARS) or lin.inputs[0] != r.output
                     or lin.attrs.get("gamma") or lin.attrs.get("glu") or lin.attrs.get("out_into")
                     or lin.attrs.get("row_stats") or lin.attrs.get("planes_out") or lin.attrs.get("act") == "glu"):
                 continue
@@ -1325,8 +1330,11 @@ class Lowered:
                 sh.inputs = [s.output] + sh.inputs[1:]
                 sh.attrs = {**sh.attrs, "x_partials": True}
             drop.add(id(r))
-            n, nq = n + (lin.kind == "linear"), nq + (lin.kind == "linear_q8")
-        self.stats["decode_combines_into_gemv"], self.stats["q8_combines_into_gemv"] = n, nq
+            n += lin.kind == "linear"
+            if lin.kind in QUANT_LINEARS:
+                nq[lin.kind] += 1
+        self.stats["decode_combines_into_gemv"], self.stats["q8_combines_into_gemv"] = n, nq["linear_q8"]
+        self.stats["mx4_combines_into_gemv"] = nq["linear_mx4"]
         return [t for t in steps if id(t) not in drop]
 
     def _fuse_argmax_pos(self, steps: list[_Step]) -> list[_Step]:
@@ -1524,5 +1532,6 @@ class Lowered:
         if v is not None:
             return v.dtype
         t = str(self.consts[name].dtype)  # a constant: its wire name, as program values carry
-        return {"torch.float32": "fp32", "torch.bfloat16": "bf16", "torch.int32": "i32", "torch.int8": "i8"}.get(t, t)
+        return {"torch.float32": "fp32", "torch.bfloat16": "bf16", "torch.int32": "i32", "torch.int8": "i8",
+                "torch.uint8": "u8"}.get(t, t)
 

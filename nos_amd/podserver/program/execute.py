@@ -125,6 +125,16 @@ class CompiledProgram(Lowered):
                     y = T.linear_q8(a[0], a[1], a[2], a[3] if len(a) > 3 else None, act=s.attrs.get("act"),
                                     residual=res, rms_eps=float(s.attrs.get("eps", 0.0)), gamma=g,
                                     glu=bool(s.attrs.get("glu")), lora=lora)
+            elif k == "linear_mx4":   # inputs: x, codes, block scales, [bias], [gamma], [residual]
+                res = a.pop() if s.attrs.get("residual") else None
+                g = a.pop() if s.attrs.get("gamma") else None
+                if s.attrs.get("x_partials"):   # x = the decode attention's split partials
+                    y = T.gemv_mx4_partials(a[0], a[1], a[2], a[3] if len(a) > 3 else None, act=s.attrs.get("act"),
+                                            residual=res).reshape(self._shape(s.output))
+                else:
+                    y = T.linear_mx4(a[0], a[1], a[2], a[3] if len(a) > 3 else None, act=s.attrs.get("act"),
+                                     residual=res, rms_eps=float(s.attrs.get("eps", 0.0)), gamma=g,
+                                     glu=bool(s.attrs.get("glu")))
             elif k == "matmul":
                 y = T.matmul(a[0], a[1])
             elif k == "softmax":

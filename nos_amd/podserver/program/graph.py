@@ -8,7 +8,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .ir import GEMM_OPS, NEVER_FOLD, Node, Value, torch_dtype
+from .ir import GEMM_OPS, MX4_SCALE_MAX, MX4_SCALE_MIN, NEVER_FOLD, QUANT_LINEARS, Node, Value, torch_dtype
 from .reference import _eager
 
 def _workspace(node: Node, ins: list[Value], out: Value, f32_math: str) -> int:
@@ -35,9 +35,9 @@ def _workspace(node: Node, ins: list[Value], out: Value, f32_math: str) -> int:
         p = out.numel // (n * oc)
         kp = -(-(cg * kh * kw) // 32) * 32
         return n * (c // cg) * p * (kp * 4 + 4) + ins[0].numel * 4 + out.numel * 4
-    if op == "linear_q8":
-        # decode rows run on the int8 GEMV; more dequantize the weight into a transient fp32
-        # buffer for the run-time-split h3 product (ops.tenant.linear_q8)
+    if op in QUANT_LINEARS:
+        # decode rows run on the int8 / MXFP4 GEMV; more dequantize the weight into a transient fp32
+        # buffer for the run-time-split h3 product (ops.tenant.linear_q8, linear_mx4)
         k = ins[0].shape[-1]
         m, n = ins[0].numel // k, ins[1].shape[0]
         if m <= 8:
@@ -212,9 +212,18 @@ class Program:
 
         out = {}
         buf = memoryview(self.payload)
+        # the block scales of the MXFP4 linears: one host pass over each, so that no kernel sees a scale byte
+        # outside the range it is defined (and tested) on
+        mx4_scales = {n.inputs[2] for n in self.nodes if n.op == "linear_mx4"}
         for name, v in self.params.items():
             off, nb = self.param_layout[name]
-            raw = np.frombuffer(buf[off:off + nb], dtype={"fp32": np.float32, "i8": np.int8}.get(v.dtype, np.int16))
+            raw = np.frombuffer(buf[off:off + nb],
+                                dtype={"fp32": np.float32, "i8": np.int8, "u8": np.uint8}.get(v.dtype, np.int16))
+            if name in mx4_scales and raw.size and (raw.min() < MX4_SCALE_MIN or raw.max() > MX4_SCALE_MAX):
+                bad = int(raw[(raw < MX4_SCALE_MIN) | (raw > MX4_SCALE_MAX)][0])
+                raise ValueError(f"param {name!r}: MXFP4 block scale byte {bad} is outside [{MX4_SCALE_MIN}, "
+                                 f"{MX4_SCALE_MAX}], the scales whose dequantized values are normal, finite fp32 "
+                                 f"(255 is the format's NaN)")
             t = torch.from_numpy(raw.copy()).view(v.shape)
             if v.dtype == "bf16":
                 t = t.view(torch.bfloat16)
@@ -267,7 +276,7 @@ class Program:
         import torch
 
         ps = params if params is not None else self.tensors("cpu")
-        env = {k: t.float().cpu() for k, t in ps.items()}
+        env = {k: (t if t.dtype == torch.uint8 else t.float()).cpu() for k, t in ps.items()}
         if state is None:
             state = {k: (t if t.dtype in (torch.int32, torch.int8) else t.float())
                      for k, t in self.state_tensors("cpu").items()}

@@ -7,9 +7,12 @@ from dataclasses import dataclass, field
 
 FORMAT = "nos-amd.program/v1"
 # i32: token ids (an input only; consumed by embedding); i8: quantized weights (a param; linear_q8's input 1)
-# or a quantized K / V cache (a state; the cache operand of kv_write / sdpa_cache, with an fp32 scales state)
-WIRE_DTYPES = {"fp32": 4, "bf16": 2, "i32": 4, "i8": 1}
-PARAM_DTYPES = ("fp32", "bf16", "i8")
+# or a quantized K / V cache (a state; the cache operand of kv_write / sdpa_cache, with an fp32 scales state);
+# u8: MXFP4 codes and E8M0 block scales (params; linear_mx4's inputs 1 and 2, nothing else)
+WIRE_DTYPES = {"fp32": 4, "bf16": 2, "i32": 4, "i8": 1, "u8": 1}
+PARAM_DTYPES = ("fp32", "bf16", "i8", "u8")
+MX4_BLOCK = 32               # consecutive k under one scale byte (builder.quantize_rows_mx4)
+MX4_SCALE_MIN, MX4_SCALE_MAX = 2, 252   # the scale bytes a registration accepts: dequantized values stay normal fp32
 FLOAT_DTYPES = ("fp32", "bf16")
 MAX_NODES = 8192
 MAX_PARAMS = 8192
@@ -115,7 +118,9 @@ OPS = ("linear", "layernorm", "attention", *BINARY, *UNARY, "cat", "slice", "res
        "conv2d", "batchnorm", "max_pool2d", "avg_pool2d", "mean", "sum", "matmul", "softmax", "embedding",
        "rmsnorm", "rotary", "sdpa",
        # int8 weight-only linear: act(x @ (wq.float() * wscale[:, None]).T + bias), fp32 math
-       "linear_q8")
+       "linear_q8",
+       # MXFP4 weight-only linear: act(x @ dequantize_rows_mx4(wq, wscale).T + bias), fp32 math
+       "linear_mx4")
 # stateful decoding (round 6): ops over state buffers that persist across a
 # tenant's requests (a K / V cache, a position counter).  STATE_WRITERS update
 # their first input IN PLACE and return its new version (the validator makes
@@ -151,11 +156,12 @@ MOE_MAX_EXPERTS = 64         # a lane per expert in the route kernel
 MOE_MAX_TOP_K = 8
 OPS = OPS + STATE_OPS + ("moe",)
 # linear_q8: folding it would materialise the fp32 weight the format exists to avoid
-NEVER_FOLD = ("attention", "sdpa", "linear_q8", "moe", *STATE_OPS)
+NEVER_FOLD = ("attention", "sdpa", "linear_q8", "linear_mx4", "moe", *STATE_OPS)
+QUANT_LINEARS = ("linear_q8", "linear_mx4")   # weight-only linears: (x, wq, wscale, [bias]), never folded
 # step kinds that run a gfx950 kernel of libnos_hip.so (CompiledProgram.stats["kernels"])
 NATIVE_KINDS = ("linear", "linear_ln", "linear_rms", "ln_qkv_attention", "attention", "layernorm", "conv2d", "matmul",
                 "softmax", "embedding", "rmsnorm", "rotary", "sdpa", "patches", "unary", "kv_write", "sdpa_cache",
-                "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu", "linear_q8", *STOP_OPS, "stop_step", *SPEC_OPS, "spec_step", "lora_shrink",
+                "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu", "linear_q8", "linear_mx4", *STOP_OPS, "stop_step", *SPEC_OPS, "spec_step", "lora_shrink",
                 "moe_route", "moe_glu", "moe_down")
 # the steps a speculating tenant's verify program closes with (CompiledProgram.stats["spec_launches"]);
 # spec_step: spec_accept / hist_write / pos_advance / spec_draft fused into one launch
@@ -169,4 +175,5 @@ GEMM_OPS = ("linear", "conv2d")
 def torch_dtype(dt: str):
     import torch
 
-    return {"fp32": torch.float32, "bf16": torch.bfloat16, "i32": torch.int32, "i8": torch.int8}[dt]
+    return {"fp32": torch.float32, "bf16": torch.bfloat16, "i32": torch.int32, "i8": torch.int8,
+            "u8": torch.uint8}[dt]

@@ -22,6 +22,10 @@ def _eager(op: str, args: list, attrs: dict, ref: bool = False):
         from ...ops import tenant as T
 
         return T.linear_q8(args[0], args[1], args[2], args[3] if len(args) > 3 else None, act=attrs.get("act"))
+    if op == "linear_mx4":
+        from ...ops import tenant as T
+
+        return T.linear_mx4(args[0], args[1], args[2], args[3] if len(args) > 3 else None, act=attrs.get("act"))
     if op == "layernorm":
         x = args[0]
         return F.layer_norm(x, (x.shape[-1],), args[1], args[2], attrs.get("eps", 1e-5))

@@ -7,7 +7,7 @@ import math
 
 from .graph import Program
 from .ir import (FLOAT_DTYPES, FORMAT, LORA_MAX_RANK, MOE_MAX_EXPERTS, MOE_MAX_TOP_K, MAX_NUMEL, MAX_PARAMS, MAX_NODES, MAX_RANK, MAX_STATE,
-                 MAX_VARIANTS, OPS, PARAM_DTYPES, SPEC_CTL_WORDS, SPEC_MAX_K, SPEC_MIN_K, STATE_DTYPES, STATE_WRITERS, STOP_CTL_WORDS, ACTS,
+                 MAX_VARIANTS, MX4_BLOCK, OPS, PARAM_DTYPES, SPEC_CTL_WORDS, SPEC_MAX_K, SPEC_MIN_K, STATE_DTYPES, STATE_WRITERS, STOP_CTL_WORDS, ACTS,
                  BINARY, INTERP_MODES, UNARY, WIRE_DTYPES, Node, ProgramError, Value, _broadcast, _eps, _int, _name,
                  _pair, _req, _shape)
 
@@ -63,6 +63,27 @@ def _infer(node: Node, ins: list[Value], gpu: bool) -> tuple[tuple[int, ...], st
         if gpu:
             _req(x.shape[-1] % 32 == 0, f"{what}: the int8 GEMV and its h3 fallback need K % 32 == 0, "
                  f"K = {x.shape[-1]}")
+        return x.shape[:-1] + (w.shape[0],), "fp32"
+    if op == "linear_mx4":
+        # weight-only MXFP4: codes [N, K / 2] u8 (two E2M1 elements a byte), scales [N, K / 32] u8 (E8M0)
+        only("act")
+        arity(3, 4)
+        x, w, sc = ins[0], ins[1], ins[2]
+        _req(w.dtype == "u8" and w.kind == "param" and len(w.shape) == 2,
+             f"{what}: the weight must be a u8 [N, K / 2] param of MXFP4 codes, got {w.kind} {w.dtype} {list(w.shape)}")
+        _req(x.dtype == "fp32", f"{what}: x must be fp32 (MXFP4 weights are an fp32 tenant's storage format; "
+             f"a bf16 x is not taken), got {x.dtype}")
+        K = x.shape[-1] if x.shape else 0
+        _req(K > 0 and K % MX4_BLOCK == 0, f"{what}: K % {MX4_BLOCK} == 0 required (one scale byte per {MX4_BLOCK} "
+             f"consecutive k), K = {K}")
+        _req(w.shape[1] * 2 == K, f"{what}: x [..., K] and codes [N, K / 2] required, got {x.shape} and {w.shape}")
+        _req(sc.dtype == "u8" and sc.kind == "param" and sc.shape == (w.shape[0], K // MX4_BLOCK),
+             f"{what}: wscale must be a u8 [{w.shape[0]}, {K // MX4_BLOCK}] param (K / {MX4_BLOCK} block scales per "
+             f"row), got {sc.kind} {sc.dtype} {list(sc.shape)}")
+        if len(ins) == 4:
+            _req(ins[3].dtype == "fp32" and ins[3].shape == (w.shape[0],),
+                 f"{what}: bias must be fp32 [{w.shape[0]}], got {ins[3].dtype} {list(ins[3].shape)}")
+        _req(a.get("act") in ACTS, f"{what}: act must be one of {ACTS}")
         return x.shape[:-1] + (w.shape[0],), "fp32"
     if op == "layernorm":
         only("eps")
@@ -633,7 +654,9 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     for d in ins:
         _req(isinstance(d, dict), "inputs must be objects")
         dt = d.get("dtype", "fp32")
-        _req(dt in WIRE_DTYPES and dt != "i8", f"input dtype must be one of {sorted(set(WIRE_DTYPES) - {'i8'})}")
+        _req(dt != "u8", "input dtype u8 is the MXFP4 codes' and block scales': a u8 value is a param, read only as "
+             "input 1 or 2 of linear_mx4")
+        _req(dt in WIRE_DTYPES and dt != "i8", f"input dtype must be one of {sorted(set(WIRE_DTYPES) - {'i8', 'u8'})}")
         v = Value(_name(d.get("name"), "input name"), _shape(d.get("shape"), "input shape"), dt, "input")
         define(v)
         inputs.append(v)
@@ -664,6 +687,8 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     for d in st:
         _req(isinstance(d, dict) and set(d) <= {"name", "shape", "dtype"}, "a state is {name, shape, dtype}")
         dt = d.get("dtype", "fp32")
+        _req(dt != "u8", "state dtype u8 is the MXFP4 codes' and block scales': a u8 value is a param, read only as "
+             "input 1 or 2 of linear_mx4")
         _req(dt in STATE_DTYPES, f"state dtype must be one of {STATE_DTYPES}")
         v = Value(_name(d.get("name"), "state name"), _shape(d.get("shape"), "state shape"), dt, "state")
         define(v)
@@ -711,6 +736,11 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
             else:
                 _req(op == "linear_q8" and k == 1, f"node {n.output!r} ({op}): input {r!r} is an i8 param; only "
                      f"linear_q8 takes one, as its weight")
+        # a u8 value is an MXFP4 weight's codes or block scales: only linear_mx4 reads it, as input 1 or 2
+        for k, r in enumerate(refs):
+            _req(values[r].dtype != "u8" or (op == "linear_mx4" and k in (1, 2)),
+                 f"node {n.output!r} ({op}): input {k} {r!r} is a u8 param; only linear_mx4 takes one, as its codes "
+                 f"(input 1) or its block scales (input 2)")
         shape, dt = _infer(n, [values[r] for r in refs], gpu)
         _req(math.prod(shape) <= MAX_NUMEL, f"node {n.output!r}: output too large")
         # a scales state is not versioned: it is named only beside versions of its ONE cache, so the
@@ -791,6 +821,8 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
     _req(adapter not in outs, f"the adapter state {adapter!r} cannot be an output: it is a control state")
     _req(not any(o in root_of for o in outs), "a state (or a version of one) cannot be an output: it is mutable")
     _req(not any(values[o].dtype == "i8" for o in outs), "an i8 param cannot be an output")
+    _req(not any(values[o].dtype == "u8" for o in outs), "a u8 param cannot be an output: MXFP4 codes and block scales "
+         "are read only by linear_mx4")
     return Program(name, inputs, params, layout, nodes, list(outs), values, payload, state=state,
                    state_root={k: v for k, v in root_of.items() if k != v}, sampling_state=sampling,
                    stopping_state=stop["stopping"], done_state=stop["done"], seen_state=stop["seen"],
