@@ -2339,6 +2339,337 @@ __global__ __launch_bounds__(256) void moe_down_kernel(const float* __restrict__
   }
 }
 
+// ------------------------------------------------------------------ quantized experts (rows <= 8)
+// The glu and down launches over expert tensors stored as int8 rows (W13q [E, 2I, H] i8 with scales
+// [E, 2I] fp32, W2q [E, H, I] i8 with scales [E, H]) or as MXFP4 (codes [E, 2I, H / 2] u8 with scale
+// bytes [E, 2I, H / 32], codes [E, H, I / 2] with [E, H, I / 32]): storage formats, the products are
+// those of the dequantized fp32 experts.  The route launch is moe_route_kernel, unchanged; idx is
+// checked against [0, E) before it forms an address, as above, and an invalid slot reads neither a
+// weight nor a scale.  A lane's load is KL consecutive k of one row -- 16 int8; one MX block (32 k, 16
+// bytes) or, where the row is at most NOS_MX4_NARROW_K long, half of one (16 k, 8 bytes) -- and a
+// wave load covers BLK = 64 KL k, as in gemv_q8_kernel / gemv_mx4_kernel.
+//
+// The vector the rows multiply (x' in glu, act[m][s] in down; K floats) sits in LDS PERMUTED, by the
+// GEMVs' rule with KL in place of 16:
+//   k = BLK b + KL l + 4 j + e  ->  BLK b + 4 nl j + 4 l + e,  j < KL / 4,  nl = min(64, (K - BLK b) / KL)
+// (nl: the lanes wave load b has work for; K % KL == 0).  Why: lane l needs the KL / 4 float4
+// k = BLK b + KL l + 4 j.  In the natural layout the j-th float4 of neighbouring lanes lie 4 KL bytes
+// apart (64 or 128), so the 64 banks x 4 bytes serve only every 4th (8th) lane of a ds_read_b128
+// group at once: a 4-way (8-way) conflict.  Permuted, the j-th float4 of lanes 0 .. nl - 1 are the
+// one contiguous run [BLK b + 4 nl j, BLK b + 4 nl (j + 1)): a 16-byte lane stride, each group of
+// lanes the hardware serves together covers every bank exactly once, and the run starts 16-byte
+// aligned (BLK b, 4 nl j and, in down, the slot's offset s I are multiples of 4 floats).  The map is a
+// bijection of [0, K): block b keeps its nl KL positions, and (j, l) -> 4 nl j + 4 l is onto them.
+template <int KL>
+__device__ __forceinline__ int moe_perm_k(int p, int K) {   // the k of LDS position p (p % 4 == 0)
+  constexpr int BLK = 64 * KL;
+  const int b = p / BLK, o = p % BLK;
+  const int nl = min(64, (K - b * BLK) / KL);
+  return b * BLK + KL * ((o % (4 * nl)) >> 2) + 4 * (o / (4 * nl));
+}
+
+// int8 rows: the FMAs run on (float)q, the row's scale multiplies the wave's sum afterwards
+struct MoeQ8 {
+  static constexpr int KL = 16, KD = 2;   // KD: wave loads per batch of the down kernel (I = 1408: one batch)
+  using Ld = uint4;
+  // expert e's row n: its bytes, and the pointer its scale is read through
+  struct Row {
+    const unsigned char* w;
+    const float* s;
+  };
+  static __device__ __forceinline__ Row row(const unsigned char* W, long long bsw, int ldw, const void* S,
+                                            long long bss, int, int e, int n) {
+    return Row{W + (long long)e * bsw + (long long)n * ldw, static_cast<const float*>(S) + (long long)e * bss + n};
+  }
+  static __device__ __forceinline__ void load(const Row& r, int k, int K, Ld& a, unsigned& sc) {
+    a = k < K ? *reinterpret_cast<const uint4*>(r.w + k) : uint4{0u, 0u, 0u, 0u};
+    sc = 0u;
+  }
+  static __device__ __forceinline__ float scale(const Row& r) { return *r.s; }
+  // acc[c] += row c's KL weights . the lane's KL values of the staged vector (xb: its first float4)
+  template <int R>
+  static __device__ __forceinline__ void dot(const Ld (&a)[R], const unsigned (&)[R], const float* xb, int nl,
+                                             float (&acc)[R]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float4 xv = *reinterpret_cast<const float4*>(xb + 4 * nl * j);
+#pragma unroll
+      for (int c = 0; c < R; ++c) {
+        const unsigned wd = j == 0 ? a[c].x : j == 1 ? a[c].y : j == 2 ? a[c].z : a[c].w;
+        acc[c] = dot4(q8_cvt4(wd), xv, acc[c]);
+      }
+    }
+  }
+};
+
+// MXFP4 rows: the FMAs run on elem x 2^(e - 127) (mx4_cvt4: the hardware conversion, or the plain
+// one under NOS_MX4_CVT_PLAIN); nothing is left for the epilogue
+template <int LB>
+struct MoeMx4 {
+  static_assert(LB == 16 || LB == 8, "a lane loads one MX block or half of one");
+  static constexpr int KL = 2 * LB, NW = LB / 4, KD = LB == 16 ? 1 : 2;
+  using Ld = typename Mx4Words<LB>::T;
+  struct Row {
+    const unsigned char* w;
+    const unsigned char* s;
+  };
+  static __device__ __forceinline__ Row row(const unsigned char* W, long long bsw, int ldw, const void* S,
+                                            long long bss, int lds, int e, int n) {
+    return Row{W + (long long)e * bsw + (long long)n * ldw,
+               static_cast<const unsigned char*>(S) + (long long)e * bss + (long long)n * lds};
+  }
+  // codes and the block's scale byte; past K: zeros under the scale 1
+  static __device__ __forceinline__ void load(const Row& r, int k, int K, Ld& a, unsigned& sc) {
+    a = k < K ? *reinterpret_cast<const Ld*>(r.w + (k >> 1)) : Ld{};
+    sc = k < K ? (unsigned)r.s[k >> 5] : 127u;
+  }
+  static __device__ __forceinline__ float scale(const Row&) { return 1.f; }
+  template <int R>
+  static __device__ __forceinline__ void dot(const Ld (&a)[R], const unsigned (&sc)[R], const float* xb, int nl,
+                                             float (&acc)[R]) {
+    unsigned wd[R][NW];
+    float s[R];
+#pragma unroll
+    for (int c = 0; c < R; ++c) {
+      Mx4Words<LB>::get(a[c], wd[c]);
+      s[c] = mx4_scale(sc[c]);
+    }
+#pragma unroll
+    for (int j2 = 0; j2 < NW; ++j2) {   // a word: 8 k, two float4 of the staged vector
+      const float4 x0 = *reinterpret_cast<const float4*>(xb + 4 * nl * (2 * j2));
+      const float4 x1 = *reinterpret_cast<const float4*>(xb + 4 * nl * (2 * j2 + 1));
+#pragma unroll
+      for (int c = 0; c < R; ++c) {
+        acc[c] = dot4(mx4_cvt4<0>(wd[c][j2], s[c]), x0, acc[c]);
+        acc[c] = dot4(mx4_cvt4<1>(wd[c][j2], s[c]), x1, acc[c]);
+      }
+    }
+  }
+};
+
+// moe_stage_x into the permuted layout of lane runs of KL: xs complete on return, the factor returned
+template <int KL>
+__device__ __forceinline__ float moe_stage_xp(const float* __restrict__ xr, const float* __restrict__ gamma,
+                                              float rms_eps, int H, float* __restrict__ xs, float (&red)[4]) {
+  const int tid = threadIdx.x;
+  float q = 0.f;
+  for (int p = tid * 4; p < H; p += 1024) {
+    const int k = moe_perm_k<KL>(p, H);
+    float4 xv = *reinterpret_cast<const float4*>(xr + k);
+    if (rms_eps > 0.f) {
+      q = fmaf(xv.x, xv.x, fmaf(xv.y, xv.y, fmaf(xv.z, xv.z, fmaf(xv.w, xv.w, q))));
+      if (gamma != nullptr) {
+        const float4 g = *reinterpret_cast<const float4*>(gamma + k);
+        xv = float4{xv.x * g.x, xv.y * g.y, xv.z * g.z, xv.w * g.w};
+      }
+    }
+    *reinterpret_cast<float4*>(xs + p) = xv;
+  }
+  q = nos::wave_sum(q);
+  if ((tid & 63) == 0) red[tid >> 6] = q;
+  __syncthreads();
+  return rms_eps > 0.f ? rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)H + rms_eps) : 1.f;
+}
+
+// moe_glu_kernel over quantized rows.  Grid (column tiles of I) x (rows x k); a wave streams FOUR rows
+// of its pair's expert -- the gates n0, n0 + 1 and their ups I + n0, I + n0 + 1, as the GEMVs' GLU form
+// pairs them -- so a workgroup pass is 8 columns; the first group's first wave load goes out before x
+// is staged, every later group's while the one before is computed.
+template <class F>
+__global__ __launch_bounds__(256) void moe_glu_quant_kernel(const float* __restrict__ x, int ldx,
+                                                            const int* __restrict__ idx,
+                                                            const unsigned char* __restrict__ W, long long bsw,
+                                                            int ldw, const void* __restrict__ S, long long bss,
+                                                            int lds, const float* __restrict__ gamma, float rms_eps,
+                                                            float* __restrict__ act, int E, int H, int I, int k) {
+  constexpr int KL = F::KL, BLK = 64 * KL, R = 4;
+  using Ld = typename F::Ld;
+  extern __shared__ __attribute__((aligned(16))) float xs[];   // [H], permuted as above
+  __shared__ float red[4];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int pair = blockIdx.y, m = pair / k;
+  const int e = __builtin_amdgcn_readfirstlane(idx[pair]);
+  float* out = act + (long long)pair * I;
+  const int ngrp = (I + 7) / 8;
+  if (e < 0 || e >= E) {   // the whole workgroup: no barrier is left behind, no weight or scale is read
+    for (int n = blockIdx.x * 256 + tid; n < I; n += gridDim.x * 256) out[n] = 0.f;
+    return;
+  }
+  auto rows_of = [&](int grp, int& n0, typename F::Row (&rw)[R]) {
+    n0 = grp * 8 + wid * 2;
+#pragma unroll
+    for (int c = 0; c < R; ++c) rw[c] = F::row(W, bsw, ldw, S, bss, lds, e, min(n0 + (c & 1), I - 1) + (c >> 1) * I);
+  };
+  auto load_chunk = [&](const typename F::Row (&rw)[R], int kb, Ld (&a)[R], unsigned (&sc)[R]) {
+#pragma unroll
+    for (int c = 0; c < R; ++c) F::load(rw[c], kb + lane * KL, H, a[c], sc[c]);
+  };
+  Ld pa[R];
+  unsigned pe[R];
+  if ((int)blockIdx.x < ngrp) {
+    int n0;
+    typename F::Row rw[R];
+    rows_of(blockIdx.x, n0, rw);
+    load_chunk(rw, 0, pa, pe);
+  }
+  const float rsc = moe_stage_xp<KL>(x + (long long)m * ldx, gamma, rms_eps, H, xs, red);
+  for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    int n0;
+    typename F::Row rw[R];
+    rows_of(grp, n0, rw);
+    float acc[R] = {0.f, 0.f, 0.f, 0.f};
+    for (int kb = 0; kb < H; kb += BLK) {
+      Ld ra[R];
+      unsigned re[R];
+      if (kb == 0) {   // prefetched; the workgroup's next group's first load goes out before this one's math
+#pragma unroll
+        for (int c = 0; c < R; ++c) {
+          ra[c] = pa[c];
+          re[c] = pe[c];
+        }
+        if (grp + (int)gridDim.x < ngrp) {
+          int nn;
+          typename F::Row rn[R];
+          rows_of(grp + gridDim.x, nn, rn);
+          load_chunk(rn, 0, pa, pe);
+        }
+      } else {
+        load_chunk(rw, kb, ra, re);
+      }
+      if (kb + lane * KL < H) F::template dot<R>(ra, re, xs + kb + 4 * lane, min(64, (H - kb) / KL), acc);
+    }
+#pragma unroll
+    for (int c = 0; c < R; ++c) acc[c] = nos::wave_sum(acc[c]);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {   // lane c finishes column n0 + c from gate row c and up row c + 2
+      const int n = n0 + c;
+      if (lane == c && n < I) {
+        const float ag = acc[c] * F::scale(rw[c]) * rsc, au = acc[c + 2] * F::scale(rw[c + 2]) * rsc;
+        out[n] = ag / (1.f + __expf(-ag)) * au;
+      }
+    }
+  }
+}
+
+// moe_down_kernel over quantized rows.  Grid (column tiles of H) x rows; a wave takes R columns (R = 2
+// where that still fills the CUs, else 1; R = 4 with two slots in flight takes all 256 VGPRs) and walks its row's slots two at a time in the order
+// 0 .. k - 1, KD wave loads of both slots and all R rows in flight; a lane folds w[m][s] (int8: times
+// the row's scale s2[e_s][n]) into its running term per slot, and the wave sum closes the column: no
+// atomics, a fixed order.  act[m] (k x I floats) sits in LDS, every slot permuted as above; the first
+// group's first batch goes out before it is staged.
+template <class F, int R>
+__global__ __launch_bounds__(256) void moe_down_quant_kernel(const float* __restrict__ act,
+                                                             const int* __restrict__ idx, const float* __restrict__ w,
+                                                             const unsigned char* __restrict__ W, long long bsw,
+                                                             int ldw, const void* __restrict__ S, long long bss,
+                                                             int lds, const float* __restrict__ res, int ldr,
+                                                             float* __restrict__ y, int ldy, int E, int H, int I,
+                                                             int k) {
+  constexpr int KL = F::KL, BLK = 64 * KL, KD = F::KD;
+  using Ld = typename F::Ld;
+  extern __shared__ __attribute__((aligned(16))) float as[];   // [k][I], each slot permuted as above
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, m = blockIdx.y;
+  const int ngrp = (H + 4 * R - 1) / (4 * R);
+  // slots s, s + 1 of row m: the experts (-1: none, or outside [0, E): wave-uniform, checked before any address)
+  auto slots_of = [&](int s, int& e0, int& e1) {
+    e0 = __builtin_amdgcn_readfirstlane(idx[(long long)m * k + s]);
+    e1 = s + 1 < k ? __builtin_amdgcn_readfirstlane(idx[(long long)m * k + s + 1]) : -1;
+    if (e0 < 0 || e0 >= E) e0 = -1;
+    if (e1 < 0 || e1 >= E) e1 = -1;
+  };
+  // a batch: KD wave loads from kb of the R rows of expert e (e < 0: no lane loads)
+  auto load_batch = [&](int e, int n0, int kb, Ld (&a)[R][KD], unsigned (&sc)[R][KD]) {
+    const int I0 = e >= 0 ? I : 0;   // a bound, not a branch per load
+#pragma unroll
+    for (int c = 0; c < R; ++c) {
+      const typename F::Row rw = F::row(W, bsw, ldw, S, bss, lds, e >= 0 ? e : 0, min(n0 + c, H - 1));
+#pragma unroll
+      for (int u = 0; u < KD; ++u) F::load(rw, kb + BLK * u + lane * KL, I0, a[c][u], sc[c][u]);
+    }
+  };
+  Ld pa0[R][KD], pa1[R][KD];
+  unsigned pe0[R][KD], pe1[R][KD];
+  if ((int)blockIdx.x < ngrp) {
+    int e0, e1;
+    slots_of(0, e0, e1);
+    const int n0 = blockIdx.x * 4 * R + wid * R;
+    load_batch(e0, n0, 0, pa0, pe0);
+    load_batch(e1, n0, 0, pa1, pe1);
+  }
+  const float* am = act + (long long)m * k * I;
+  for (int p = tid * 4; p < k * I; p += 1024) {
+    const int s = p / I;   // I % 4 == 0: a float4 stays inside its slot
+    *reinterpret_cast<float4*>(as + p) = *reinterpret_cast<const float4*>(am + s * I + moe_perm_k<KL>(p - s * I, I));
+  }
+  __syncthreads();
+  for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    const int n0 = grp * 4 * R + wid * R;
+    float acc[R];
+#pragma unroll
+    for (int c = 0; c < R; ++c) acc[c] = 0.f;
+    for (int s = 0; s < k; s += 2) {
+      int e0, e1;
+      slots_of(s, e0, e1);
+      if (e0 < 0 && e1 < 0) continue;
+      float d0[R], d1[R];
+#pragma unroll
+      for (int c = 0; c < R; ++c) d0[c] = d1[c] = 0.f;
+      for (int kb = 0; kb < I; kb += BLK * KD) {
+        Ld ra[R][KD], rc[R][KD];
+        unsigned re[R][KD], rf[R][KD];
+        if (grp == (int)blockIdx.x && s == 0 && kb == 0) {
+#pragma unroll
+          for (int c = 0; c < R; ++c)
+#pragma unroll
+            for (int u = 0; u < KD; ++u) {
+              ra[c][u] = pa0[c][u], re[c][u] = pe0[c][u];
+              rc[c][u] = pa1[c][u], rf[c][u] = pe1[c][u];
+            }
+        } else {
+          load_batch(e0, n0, kb, ra, re);
+          load_batch(e1, n0, kb, rc, rf);
+        }
+#pragma unroll
+        for (int u = 0; u < KD; ++u) {
+          const int k0 = kb + BLK * u;
+          if (k0 + lane * KL < I) {
+            const int nl = min(64, (I - k0) / KL);
+            Ld ta[R], tc[R];
+            unsigned te[R], tf[R];
+#pragma unroll
+            for (int c = 0; c < R; ++c) {
+              ta[c] = ra[c][u], te[c] = re[c][u];
+              tc[c] = rc[c][u], tf[c] = rf[c][u];
+            }
+            if (e0 >= 0) F::template dot<R>(ta, te, as + s * I + k0 + 4 * lane, nl, d0);
+            if (e1 >= 0) F::template dot<R>(tc, tf, as + (s + 1) * I + k0 + 4 * lane, nl, d1);
+          }
+        }
+      }
+      // slot order: s, then s + 1; the weights and scales of a valid slot only
+#pragma unroll
+      for (int c = 0; c < R; ++c) {
+        const int n = min(n0 + c, H - 1);
+        if (e0 >= 0)
+          acc[c] = fmaf(w[(long long)m * k + s] * F::scale(F::row(W, bsw, ldw, S, bss, lds, e0, n)), d0[c], acc[c]);
+        if (e1 >= 0)
+          acc[c] = fmaf(w[(long long)m * k + s + 1] * F::scale(F::row(W, bsw, ldw, S, bss, lds, e1, n)), d1[c], acc[c]);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < R; ++c) acc[c] = nos::wave_sum(acc[c]);
+#pragma unroll
+    for (int c = 0; c < R; ++c) {
+      const int n = n0 + c;
+      if (lane == c && n < H) {
+        float v = acc[c];
+        if (res != nullptr) v += res[(long long)m * ldr + n];
+        y[(long long)m * ldy + n] = v;
+      }
+    }
+  }
+}
+
 // out [N, K] fp32 = (float)q * wscale[n], one rounding: 4 weights per thread (a 4-byte load, a 16-byte store)
 __global__ __launch_bounds__(256) void dequant_q8_kernel(const signed char* __restrict__ w, int ldw,
                                                          const float* __restrict__ wscale, float* __restrict__ out,
@@ -3212,4 +3543,110 @@ NOS_API int nos_moe_down(const float* act, const int* idx, const float* w, const
   hipLaunchKernelGGL(moe_down_kernel, dim3((unsigned)gx, (unsigned)M), dim3(256), (size_t)k * I * 4, stream, act, idx,
                      w, W2, bs2, ld2, res, ldr, y, ldy, E, H, I, k);
   return (int)hipGetLastError();
+}
+
+// nos_moe_glu / nos_moe_down over quantized experts (moe_glu_quant_kernel / moe_down_quant_kernel; the
+// route launch is nos_moe_route).  The fp32 entry points' contract, and: H and I multiples of KM (16 for
+// int8, 32 for MXFP4); codes 16-byte aligned with row and expert strides (bytes) that are multiples of 16;
+// int8 scales fp32 [E, rows] with an expert stride bss (floats); MXFP4 scale bytes [E, rows, K / 32] with
+// strides bss >= rows x lds and lds >= K / 32 (bytes), every byte in [2, 252] (the registration checks it).
+static bool moe_quant_ok(int M, int E, int H, int I, int k, int KM, const void* Wq, long long bsw, int ldw,
+                         int rows, int kbytes, const void* S) {
+  return moe_dims_ok(M, E, H, I, k) && (H % KM) == 0 && (I % KM) == 0 && Wq && !((uintptr_t)Wq & 15) &&
+         ldw >= kbytes && (ldw % 16) == 0 && bsw >= (long long)(rows - 1) * ldw + kbytes && (bsw % 16) == 0 && S;
+}
+
+static int moe_glu_quant_grid(int I, int pairs) {
+  const int ngrp = (I + 7) / 8;
+  const int gx = 16 * nos_effective_cus() / pairs;   // up to 16 workgroups per CU over all pairs, as nos_moe_glu
+  return gx < 1 ? 1 : (gx > ngrp ? ngrp : gx);
+}
+
+template <class F>
+static int moe_glu_quant_launch(const float* x, int ldx, const int* idx, const void* Wq, long long bsw, int ldw,
+                                const void* S, long long bss, int lds, const float* gamma, float rms_eps, float* act,
+                                int M, int E, int H, int I, int k, hipStream_t stream) {
+  hipLaunchKernelGGL((moe_glu_quant_kernel<F>), dim3((unsigned)moe_glu_quant_grid(I, M * k), (unsigned)(M * k)),
+                     dim3(256), (size_t)H * 4, stream, x, ldx, idx, static_cast<const unsigned char*>(Wq), bsw, ldw, S,
+                     bss, lds, gamma, rms_eps, act, E, H, I, k);
+  return (int)hipGetLastError();
+}
+
+// R = 2 columns per wave where the grid still covers the CUs, else a column per wave (a single row of
+// H = 1024: 256 workgroups, as nos_moe_down)
+template <class F>
+static int moe_down_quant_launch(const float* act, const int* idx, const float* w, const void* Wq, long long bsw,
+                                 int ldw, const void* S, long long bss, int lds, const float* res, int ldr, float* y,
+                                 int ldy, int M, int E, int H, int I, int k, hipStream_t stream) {
+  const int cus = nos_effective_cus();
+  const bool wide = (long long)M * ((H + 7) / 8) >= cus;
+  const int ngrp = wide ? (H + 7) / 8 : (H + 3) / 4;
+  int gx = 16 * cus / M;
+  gx = gx < 1 ? 1 : (gx > ngrp ? ngrp : gx);
+#define NOS_MOE_DOWN_Q(r)                                                                                          \
+  hipLaunchKernelGGL((moe_down_quant_kernel<F, r>), dim3((unsigned)gx, (unsigned)M), dim3(256), (size_t)k * I * 4, \
+                     stream, act, idx, w, static_cast<const unsigned char*>(Wq), bsw, ldw, S, bss, lds, res, ldr, \
+                     y, ldy, E, H, I, k)
+  if (wide) {
+    NOS_MOE_DOWN_Q(2);
+  } else {
+    NOS_MOE_DOWN_Q(1);
+  }
+#undef NOS_MOE_DOWN_Q
+  return (int)hipGetLastError();
+}
+
+static bool moe_down_args_ok(const float* act, const int* idx, const float* w, const float* res, int ldr,
+                             const float* y, int ldy, int H, int I, int k) {
+  return (long long)k * I * 4 <= 65536 && act && !((uintptr_t)act & 15) && idx && !((uintptr_t)idx & 3) && w &&
+         !((uintptr_t)w & 3) && y && !((uintptr_t)y & 3) && ldy >= H && (!res || (ldr >= H && !((uintptr_t)res & 3)));
+}
+
+NOS_API int nos_moe_glu_q8(const float* x, int ldx, const int* idx, const void* W13q, long long bs13, int ld13,
+                           const float* s13, long long bss13, const float* gamma, float rms_eps, float* act, int M,
+                           int E, int H, int I, int k, hipStream_t stream) {
+  if (!moe_quant_ok(M, E, H, I, k, 16, W13q, bs13, ld13, 2 * I, H, s13) || !moe_x_ok(x, ldx, gamma, rms_eps, H) ||
+      !idx || ((uintptr_t)idx & 3) || bss13 < 2 * I || ((uintptr_t)s13 & 3) || !act || ((uintptr_t)act & 15))
+    return (int)hipErrorInvalidValue;
+  return moe_glu_quant_launch<MoeQ8>(x, ldx, idx, W13q, bs13, ld13, s13, bss13, 0, gamma, rms_eps, act, M, E, H, I, k,
+                                     stream);
+}
+
+NOS_API int nos_moe_down_q8(const float* act, const int* idx, const float* w, const void* W2q, long long bs2, int ld2,
+                            const float* s2, long long bss2, const float* res, int ldr, float* y, int ldy, int M,
+                            int E, int H, int I, int k, hipStream_t stream) {
+  if (!moe_quant_ok(M, E, H, I, k, 16, W2q, bs2, ld2, H, I, s2) || !moe_down_args_ok(act, idx, w, res, ldr, y, ldy, H, I, k) ||
+      bss2 < H || ((uintptr_t)s2 & 3))
+    return (int)hipErrorInvalidValue;
+  return moe_down_quant_launch<MoeQ8>(act, idx, w, W2q, bs2, ld2, s2, bss2, 0, res, ldr, y, ldy, M, E, H, I, k,
+                                      stream);
+}
+
+// rows up to NOS_MX4_NARROW_K long take the 8-byte-load form, as the MXFP4 GEMV (docs/kernels.md)
+NOS_API int nos_moe_glu_mx4(const float* x, int ldx, const int* idx, const void* W13c, long long bs13, int ld13,
+                            const void* e13, long long bse13, int lde13, const float* gamma, float rms_eps,
+                            float* act, int M, int E, int H, int I, int k, hipStream_t stream) {
+  if (!moe_quant_ok(M, E, H, I, k, 32, W13c, bs13, ld13, 2 * I, H / 2, e13) ||
+      !moe_x_ok(x, ldx, gamma, rms_eps, H) || !idx || ((uintptr_t)idx & 3) || lde13 < H / 32 ||
+      bse13 < (long long)(2 * I - 1) * lde13 + H / 32 || !act || ((uintptr_t)act & 15))
+    return (int)hipErrorInvalidValue;
+  if (H <= NOS_MX4_NARROW_K)
+    return moe_glu_quant_launch<MoeMx4<8>>(x, ldx, idx, W13c, bs13, ld13, e13, bse13, lde13, gamma, rms_eps, act, M, E,
+                                           H, I, k, stream);
+  return moe_glu_quant_launch<MoeMx4<16>>(x, ldx, idx, W13c, bs13, ld13, e13, bse13, lde13, gamma, rms_eps, act, M, E,
+                                          H, I, k, stream);
+}
+
+NOS_API int nos_moe_down_mx4(const float* act, const int* idx, const float* w, const void* W2c, long long bs2, int ld2,
+                             const void* e2, long long bse2, int lde2, const float* res, int ldr, float* y, int ldy,
+                             int M, int E, int H, int I, int k, hipStream_t stream) {
+  if (!moe_quant_ok(M, E, H, I, k, 32, W2c, bs2, ld2, H, I / 2, e2) ||
+      !moe_down_args_ok(act, idx, w, res, ldr, y, ldy, H, I, k) || lde2 < I / 32 ||
+      bse2 < (long long)(H - 1) * lde2 + I / 32)
+    return (int)hipErrorInvalidValue;
+  if (I <= NOS_MX4_NARROW_K)
+    return moe_down_quant_launch<MoeMx4<8>>(act, idx, w, W2c, bs2, ld2, e2, bse2, lde2, res, ldr, y, ldy, M, E, H, I,
+                                            k, stream);
+  return moe_down_quant_launch<MoeMx4<16>>(act, idx, w, W2c, bs2, ld2, e2, bse2, lde2, res, ldr, y, ldy, M, E, H, I, k,
+                                           stream);
 }

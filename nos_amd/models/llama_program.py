@@ -256,7 +256,8 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
                           extend: tuple[int, ...] = (), sampling: bool = False,
                           weights: str = "fp32", kv: str | None = None,
                           stopping: bool = False, speculate: int | None = None,
-                          adapters: list | None = None, window: int | None = None) -> tuple[list[dict], bytes]:
+                          adapters: list | None = None, window: int | None = None,
+                          experts: str = "fp32") -> tuple[list[dict], bytes]:
     """A STATEFUL generation tenant: ``[prefill, decode, *extends]`` programs
     over one weight payload and one state -- per layer a K and a V cache
     ``[batch, max_len, kv_heads, head_dim]`` plus the position counter
@@ -376,9 +377,21 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     mlp.experts.down_proj, top_k=num_experts_per_tok), h)`` over the fused expert
     tensors as the state dict holds them.  ``batch``, ``extend``, ``sampling``,
     ``stopping``, ``kv="int8"``, ``speculate`` and ``adapters`` on q / k / v / o work
-    as above; refused, each with its rule: ``weights="int8"``, ``dtype="bf16"``,
+    as above; refused, each with its rule: ``weights="int8"`` / ``"mxfp4"`` (quantized
+    experts are ``experts=``, below), ``dtype="bf16"``,
     adapter targets in the MLP, a ``sliding_window`` smaller than ``max_len`` and a
     ``speculate`` with ``batch * K * max(H, I) * 4 > GEMV_X_BYTES``.
+
+    ``experts="int8"`` / ``"mxfp4"`` (a Mixtral only; default ``"fp32"``): the two expert tensors of every
+    layer are stored quantized -- ``Builder.param_q8`` / ``param_mx4`` of the 3-D tensors, row by row over
+    the last axis (block by block for MXFP4) -- and read by ``moe_q8`` / ``moe_mx4`` nodes; the programs are
+    named ``...-fp32-eq8-...`` / ``...-fp32-emx4-...``.  The attention linears, the LM head, the embedding
+    and the router stay fp32 (routing is discontinuous, and the router is E x H floats).  A storage format,
+    as ``weights=`` is for a dense model: the server computes, in fp32, exactly
+    ``dequantized_llama(model, experts=...)``.  It combines with everything a Mixtral takes (``batch``,
+    ``extend``, ``sampling``, ``stopping``, ``kv="int8"``, ``speculate``, ``adapters`` on q / k / v / o);
+    refused: ``dtype="bf16"``, and a hidden or intermediate size that is no multiple of 16 (int8) or 32
+    (MXFP4).  ``experts="fp32"`` programs are byte for byte those built without the keyword.
 
     ``window`` (default: ``config.sliding_window`` of a ``MistralForCausalLM``, else none; with every
     option above): sliding-window attention, the query at position p attending the W positions
@@ -394,10 +407,22 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     from ..ops.tenant import GEMV_MAX_ROWS, GEMV_X_BYTES
 
     moe = getattr(model.config, "model_type", None) == "mixtral"
+    if experts not in ("fp32", "int8", "mxfp4"):
+        raise ValueError(f"experts must be 'fp32', 'int8' or 'mxfp4', got {experts!r}")
+    if experts != "fp32" and not moe:
+        raise ValueError(f"experts={experts!r} is a Mixtral tenant's option (the storage format of its expert tensors): "
+                         f"this model has no experts; a dense model's linears are quantized with weights=")
     if moe:
         _refuse_mixtral(model.config, max_len, batch, dtype, weights, speculate, adapters, GEMV_X_BYTES)
         if window is not None:
             raise ValueError("a Mixtral tenant takes no window (no sliding-window attention beside the moe op yet)")
+        if experts != "fp32":
+            mult, what = (16, "16 int8 weights are one 16-byte load") if experts == "int8" else \
+                (32, "an MXFP4 block is 32 consecutive inputs of an expert row under one scale byte")
+            for name, size in (("hidden_size", model.config.hidden_size),
+                               ("intermediate_size", model.config.intermediate_size)):
+                if size % mult:
+                    raise ValueError(f"experts={experts!r}: {name} = {size} is not a multiple of {mult} ({what})")
     if window is None and getattr(model.config, "model_type", None) == "mistral":
         window = getattr(model.config, "sliding_window", None)
     if window is not None and (not isinstance(window, int) or isinstance(window, bool) or window < 1):
@@ -470,7 +495,7 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
     ring = {"window": window, "limit": max_len} if ring_slots else {}
     payload = b""
     for seq, reset, verify in chunks:
-        b = Builder(f"{'mixtral' if moe else 'llama'}-h{d}-l{cfg.num_hidden_layers}-{dtype}{'-q8' if q8 else '-mx4' if mx4 else ''}{'-kvq8' if kvq8 else ''}-"
+        b = Builder(f"{'mixtral' if moe else 'llama'}-h{d}-l{cfg.num_hidden_layers}-{dtype}{'-q8' if q8 else '-mx4' if mx4 else ''}{'-eq8' if experts == 'int8' else '-emx4' if experts == 'mxfp4' else ''}{'-kvq8' if kvq8 else ''}-"
                     f"{'stop-' if stopping else ''}{'spec-' if speculate else ''}{'lora-' if stacked else ''}"
                     f"{'prefill' if reset else 'verify' if verify else 'step'}{seq}")
         ids = b.input("input_ids", [batch, seq], "i32")
@@ -540,8 +565,15 @@ def llama_decode_programs(model, prompt_len: int, max_len: int, batch: int = 1, 
             h = b.op("add", adapted(lin(o, pf + "self_attn.o_proj.weight"), o, pf + "self_attn.o_proj"), h)
             y = b.op("rmsnorm", h, P(pf + "post_attention_layernorm.weight"), eps=eps)
             if moe:   # the sparse MLP: the router, the fused expert tensors as the state dict holds them
-                h = b.op("add", b.moe(y, P(pf + "mlp.gate.weight"), P(pf + "mlp.experts.gate_up_proj"),
-                                      P(pf + "mlp.experts.down_proj"), cfg.num_experts_per_tok), h)
+                egu, edn = pf + "mlp.experts.gate_up_proj", pf + "mlp.experts.down_proj"
+                if experts == "fp32":
+                    h = b.op("add", b.moe(y, P(pf + "mlp.gate.weight"), P(egu), P(edn), cfg.num_experts_per_tok), h)
+                    continue
+                # quantized experts: codes and scales of the two tensors; the router stays fp32
+                quantized = b.param_q8 if experts == "int8" else b.param_mx4
+                node = b.moe_q8 if experts == "int8" else b.moe_mx4
+                h = b.op("add", node(y, P(pf + "mlp.gate.weight"), *quantized(egu, sd[egu]), *quantized(edn, sd[edn]),
+                                     cfg.num_experts_per_tok), h)
                 continue
             if quant or pf + "mlp.gate_up_proj" in stacked:
                 if pf + "mlp.gate_up_proj" in stacked:
@@ -621,13 +653,35 @@ def _refuse_mixtral(cfg, max_len, batch, dtype, weights, speculate, adapters, x_
                              f"kernels")
 
 
-def dequantized_llama(model, weights: str = "int8"):
+def dequantized_llama(model, weights: str = "int8", experts: str | None = None):
     """A deep copy of the HF model whose linear weights (attention and MLP
     projections, the LM head -- untied from the embedding table, which stays
     fp32) are ``dequantize(quantize(w))`` row by row (``weights="mxfp4"``: block
     by block, ``quantize_rows_mx4``): the model an int8 (MXFP4) tenant of
     ``model`` computes (``llama_decode_programs(weights=...)``), for tests and
-    users to compare against."""
+    users to compare against.
+
+    ``experts="int8"`` / ``"mxfp4"`` (a Mixtral): instead, ONLY the expert tensors
+    ``mlp.experts.gate_up_proj`` and ``mlp.experts.down_proj`` are round-tripped, row by row over the
+    last axis (``quantize_rows_q8`` / ``quantize_rows_mx4`` on the tensor flattened to [E * N, K]);
+    everything else keeps its fp32 values: the model a tenant built with
+    ``llama_decode_programs(experts=...)`` computes."""
+    if experts is not None:
+        if experts not in ("int8", "mxfp4"):
+            raise ValueError(f"dequantized_llama: experts must be 'int8' or 'mxfp4', got {experts!r}")
+        import copy
+
+        import torch
+
+        rt = ((lambda w: dequantize_rows_mx4(*quantize_rows_mx4(w))) if experts == "mxfp4"
+              else (lambda w: dequantize_rows_q8(*quantize_rows_q8(w))))
+        m = copy.deepcopy(model)
+        with torch.no_grad():
+            for name, p in m.named_parameters():
+                if name.endswith(("mlp.experts.gate_up_proj", "mlp.experts.down_proj")):
+                    w = p.detach().float().cpu().numpy()
+                    p.copy_(torch.from_numpy(rt(w.reshape(-1, w.shape[-1])).reshape(w.shape)).to(p.dtype))
+        return m
     if weights not in ("int8", "mxfp4"):
         raise ValueError(f"dequantized_llama: weights must be 'int8' or 'mxfp4', got {weights!r}")
     roundtrip = ((lambda w: dequantize_rows_mx4(*quantize_rows_mx4(w))) if weights == "mxfp4"

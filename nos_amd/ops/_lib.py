@@ -181,6 +181,15 @@ _SIGS = {
                     c_int, c_int, c_void_p],
     "nos_moe_down": [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                      c_int, c_int, c_int, c_int, c_void_p],
+    # decode.hip: the glu and down launches over int8 and MXFP4 experts
+    "nos_moe_glu_q8": [c_void_p, c_int, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_ll, c_void_p, c_float, c_void_p,
+                       c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "nos_moe_down_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_ll, c_void_p, c_int, c_void_p,
+                        c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "nos_moe_glu_mx4": [c_void_p, c_int, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_ll, c_int, c_void_p, c_float,
+                        c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "nos_moe_down_mx4": [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_ll, c_int, c_void_p, c_int,
+                         c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "nos_attn_h3g_workspace": [c_int, c_int, c_int, c_int, c_int, c_int],
     # LayerNorm hand-off (gemm_f32h.hip): producer row statistics, LN in the consumer's A load
     "nos_gemm_f32h3_stats": [c_void_p, c_int, c_ll, c_void_p, c_float, c_void_p, c_int, c_ll, c_void_p, c_void_p,

@@ -2245,6 +2245,227 @@ def moe(x: torch.Tensor, Wr: torch.Tensor, W13: torch.Tensor, W2: torch.Tensor, 
     return y.view(x.shape)
 
 
+# ------------------------------------------------------------------ quantized experts (int8, MXFP4)
+def _dequant_experts_q8(Wq: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """fp32 [E, N, K] = ``Wq.float() * s[..., None]``, one rounding (``dequantize_rows_q8`` expert by expert)."""
+    if Wq.dim() != 3 or tuple(s.shape) != tuple(Wq.shape[:2]):
+        raise ValueError(f"int8 experts are codes [E, N, K] and scales [E, N], got {tuple(Wq.shape)} and {tuple(s.shape)}")
+    return Wq.to(torch.float32) * s.to(torch.float32).unsqueeze(-1)
+
+
+def _dequant_experts_mx4(Wc: torch.Tensor, We: torch.Tensor) -> torch.Tensor:
+    """fp32 [E, N, K] of MXFP4 experts: codes u8 [E, N, K / 2], scale bytes u8 [E, N, K / 32] (exact)."""
+    if Wc.dim() != 3 or We.dim() != 3 or tuple(Wc.shape[:2]) != tuple(We.shape[:2]):
+        raise ValueError(f"MXFP4 experts are codes u8 [E, N, K / 2] and scales u8 [E, N, K / {MX4_BLOCK}], got "
+                         f"{tuple(Wc.shape)} and {tuple(We.shape)}")
+    E, N = Wc.shape[:2]
+    return _dequant_mx4_ref(Wc.reshape(E * N, -1), We.reshape(E * N, -1)).view(E, N, -1)
+
+
+def moe_glu_q8_ref(x2, idx, W13q, s13, rms_eps: float = 0.0, gamma=None, dtype: torch.dtype = torch.float32):
+    """:func:`moe_glu_q8` in ``dtype`` arithmetic: :func:`moe_glu_ref` on the experts dequantized in fp32."""
+    return moe_glu_ref(x2, idx, _dequant_experts_q8(W13q, s13), rms_eps, gamma, dtype)
+
+
+def moe_down_q8_ref(act, idx, w, W2q, s2, res=None, dtype: torch.dtype = torch.float32):
+    """:func:`moe_down_q8` in ``dtype`` arithmetic: :func:`moe_down_ref` on the experts dequantized in fp32."""
+    return moe_down_ref(act, idx, w, _dequant_experts_q8(W2q, s2), res, dtype)
+
+
+def moe_glu_mx4_ref(x2, idx, W13c, W13e, rms_eps: float = 0.0, gamma=None, dtype: torch.dtype = torch.float32):
+    """:func:`moe_glu_mx4` in ``dtype`` arithmetic: :func:`moe_glu_ref` on the dequantized experts."""
+    return moe_glu_ref(x2, idx, _dequant_experts_mx4(W13c, W13e), rms_eps, gamma, dtype)
+
+
+def moe_down_mx4_ref(act, idx, w, W2c, W2e, res=None, dtype: torch.dtype = torch.float32):
+    """:func:`moe_down_mx4` in ``dtype`` arithmetic: :func:`moe_down_ref` on the dequantized experts."""
+    return moe_down_ref(act, idx, w, _dequant_experts_mx4(W2c, W2e), res, dtype)
+
+
+def moe_q8_ref(x, Wr, W13q, s13, W2q, s2, k: int, dtype: torch.dtype | None = None):
+    """What ``moe_q8(x, Wr, W13q, s13, W2q, s2; top_k=k)`` means: :func:`moe_ref` with the experts
+    ``q.float() * scale`` (formed in fp32, the storage format's definition)."""
+    return moe_ref(x, Wr, _dequant_experts_q8(W13q, s13), _dequant_experts_q8(W2q, s2), k, dtype)
+
+
+def moe_mx4_ref(x, Wr, W13c, W13e, W2c, W2e, k: int, dtype: torch.dtype | None = None):
+    """What ``moe_mx4(x, Wr, W13c, W13e, W2c, W2e; top_k=k)`` means: :func:`moe_ref` with the experts
+    ``elem x 2^(e - 127)`` (exact in fp32)."""
+    return moe_ref(x, Wr, _dequant_experts_mx4(W13c, W13e), _dequant_experts_mx4(W2c, W2e), k, dtype)
+
+
+_MOE_QUANT = {"q8": (16, torch.int8, 1, "int8"), "mx4": (MX4_BLOCK, torch.uint8, 2, "MXFP4")}   # K multiple, codes, k per byte
+
+
+def _moe_quant_weights(what: str, fmt: str, Wq, S, E: int, N: int, K: int, x) -> None:
+    """The codes [E, N, K / per] and scales of one quantized expert tensor as the kernels load them."""
+    mult, cdt, per, name = _MOE_QUANT[fmt]
+    if K % mult:
+        raise ValueError(f"{what}: {name} expert rows of {K} inputs; a multiple of {mult} required (H and I both)")
+    if Wq.dtype != cdt or tuple(Wq.shape) != (E, N, K // per):
+        raise ValueError(f"{what}: {name} codes must be {cdt} [{E}, {N}, {K // per}], got {Wq.dtype} {tuple(Wq.shape)}")
+    sshape, sdt = ((E, N), torch.float32) if fmt == "q8" else ((E, N, K // MX4_BLOCK), torch.uint8)
+    if S.dtype != sdt or tuple(S.shape) != sshape:
+        raise ValueError(f"{what}: {name} scales must be {sdt} {list(sshape)}, got {S.dtype} {tuple(S.shape)}")
+    for nm, t in (("codes", Wq), ("scales", S)):
+        if not t.is_cuda or t.device != x.device:
+            raise ValueError(f"{what}: the {name} {nm} must be on the GPU with x, they are on {t.device}")
+    if Wq.stride(-1) != 1 or Wq.stride(0) % 16 or Wq.stride(1) % 16 or Wq.data_ptr() % 16:
+        raise ValueError(f"{what}: {name} codes {tuple(Wq.shape)} with strides {Wq.stride()} at offset "
+                         f"{Wq.data_ptr() % 16} of a 16-byte line: unit inner stride, row and expert strides that are "
+                         f"multiples of 16 bytes and a 16-byte aligned base required")
+    if S.stride(-1) != 1 or (fmt == "q8" and S.data_ptr() % 4):
+        raise ValueError(f"{what}: {name} scales {tuple(S.shape)} with strides {S.stride()}: unit inner stride required")
+
+
+def _moe_act_out(what: str, out, rows: int, k: int, I: int, device):
+    act = out if out is not None else torch.empty((rows, k, I), dtype=torch.float32, device=device)
+    if (act.dtype != torch.float32 or tuple(act.shape) != (rows, k, I) or not act.is_contiguous() or not act.is_cuda
+            or act.data_ptr() % 16):
+        raise ValueError(f"{what}: out must be a contiguous, 16-byte aligned fp32 [{rows}, {k}, {I}] on the GPU, got "
+                         f"{act.dtype} {tuple(act.shape)} on {act.device}")
+    return act
+
+
+def _moe_glu_quant(fmt: str, x, idx, Wq, S, rms_eps, gamma, out):
+    what = "moe_glu_" + fmt
+    if x.dim() != 2 or Wq.dim() != 3 or Wq.shape[1] % 2 or idx.dim() != 2:
+        raise ValueError(f"{what}: x [rows, H], idx [rows, k] and codes [E, 2I, .] required, got {tuple(x.shape)}, "
+                         f"{tuple(idx.shape)} and {tuple(Wq.shape)}")
+    rows, H = x.shape
+    _moe_gamma(what, gamma, rms_eps, H)
+    if not x.is_cuda:
+        ref = moe_glu_q8_ref if fmt == "q8" else moe_glu_mx4_ref
+        return ref(x, idx, Wq, S, rms_eps, gamma)
+    E, I, k = Wq.shape[0], Wq.shape[1] // 2, idx.shape[1]
+    _moe_dims(what, rows, E, H, I, k)
+    if I % _MOE_QUANT[fmt][0]:
+        raise ValueError(f"{what}: I = {I}; a multiple of {_MOE_QUANT[fmt][0]} required (H and I both)")
+    _moe_idx(what, idx, rows)
+    _moe_refuse(what, x=x, gamma=gamma)
+    _moe_quant_weights(what, fmt, Wq, S, E, 2 * I, H, x)
+    act = _moe_act_out(what, out, rows, k, I, x.device)
+    L = _lib.lib()
+    if fmt == "q8":
+        _lib.check(L.nos_moe_glu_q8(x.data_ptr(), x.stride(0), idx.data_ptr(), Wq.data_ptr(), Wq.stride(0), Wq.stride(1),
+                                    S.data_ptr(), S.stride(0), _ptr(gamma), float(rms_eps), act.data_ptr(), rows, E, H, I,
+                                    k, _stream()), "nos_moe_glu_q8")
+    else:
+        _lib.check(L.nos_moe_glu_mx4(x.data_ptr(), x.stride(0), idx.data_ptr(), Wq.data_ptr(), Wq.stride(0), Wq.stride(1),
+                                     S.data_ptr(), S.stride(0), S.stride(1), _ptr(gamma), float(rms_eps), act.data_ptr(),
+                                     rows, E, H, I, k, _stream()), "nos_moe_glu_mx4")
+    return act
+
+
+def _moe_down_quant(fmt: str, act, idx, w, Wq, S, res, out):
+    what = "moe_down_" + fmt
+    if (act.dim() != 3 or Wq.dim() != 3 or tuple(w.shape) != tuple(act.shape[:2])
+            or tuple(idx.shape) != tuple(act.shape[:2])):
+        raise ValueError(f"{what}: act [rows, k, I], idx and w [rows, k] and codes [E, H, .] required, got "
+                         f"{tuple(act.shape)}, {tuple(idx.shape)}, {tuple(w.shape)} and {tuple(Wq.shape)}")
+    rows, k, I = act.shape
+    E, H = Wq.shape[:2]
+    if res is not None and tuple(res.shape) != (rows, H):
+        raise ValueError(f"{what}: res must be [{rows}, {H}], got {tuple(res.shape)}")
+    if not act.is_cuda:
+        ref = moe_down_q8_ref if fmt == "q8" else moe_down_mx4_ref
+        y = ref(act, idx, w, Wq, S, res)
+        return y if out is None else out.copy_(y)
+    _moe_dims(what, rows, E, H, I, k)
+    if H % _MOE_QUANT[fmt][0]:
+        raise ValueError(f"{what}: H = {H}; a multiple of {_MOE_QUANT[fmt][0]} required (H and I both)")
+    _moe_idx(what, idx, rows, k)
+    if not act.is_contiguous() or not w.is_contiguous() or w.dtype != torch.float32 or not w.is_cuda:
+        raise ValueError(f"{what}: act and w must be contiguous and w fp32 on the GPU, got w {w.dtype} on {w.device}")
+    _moe_refuse(what, act=act)
+    _moe_quant_weights(what, fmt, Wq, S, E, H, I, act)
+    y = out if out is not None else torch.empty((rows, H), dtype=torch.float32, device=act.device)
+    for name, t in (("res", res), ("out", y)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_cuda or t.stride(-1) != 1 or tuple(t.shape) != (rows, H)
+                              or t.stride(0) < H):
+            raise ValueError(f"{what}: {name} must be an fp32 [{rows}, {H}] on the GPU with unit inner stride, got "
+                             f"{t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
+    L = _lib.lib()
+    tail = (_ptr(res), res.stride(0) if res is not None else 0, y.data_ptr(), y.stride(0), rows, E, H, I, k, _stream())
+    if fmt == "q8":
+        _lib.check(L.nos_moe_down_q8(act.data_ptr(), idx.data_ptr(), w.data_ptr(), Wq.data_ptr(), Wq.stride(0),
+                                     Wq.stride(1), S.data_ptr(), S.stride(0), *tail), "nos_moe_down_q8")
+    else:
+        _lib.check(L.nos_moe_down_mx4(act.data_ptr(), idx.data_ptr(), w.data_ptr(), Wq.data_ptr(), Wq.stride(0),
+                                      Wq.stride(1), S.data_ptr(), S.stride(0), S.stride(1), *tail), "nos_moe_down_mx4")
+    return y
+
+
+def moe_glu_q8(x: torch.Tensor, idx: torch.Tensor, W13q: torch.Tensor, s13: torch.Tensor, rms_eps: float = 0.0,
+               gamma: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`moe_glu` over int8 experts: W13q [E, 2I, H] i8 with one fp32 scale per row, s13 [E, 2I]
+    (decode.hip ``nos_moe_glu_q8``; H % 16 == 0 and I % 16 == 0, codes with 16-byte rows).  One byte of
+    HBM per weight of the chosen experts; fp32 FMAs on the int8 values, the row scale after the sum.  A
+    slot outside [0, E) reads no weight or scale and is zeros.  CPU tensors: :func:`moe_glu_q8_ref`."""
+    return _moe_glu_quant("q8", x, idx, W13q, s13, rms_eps, gamma, out)
+
+
+def moe_down_q8(act: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, W2q: torch.Tensor, s2: torch.Tensor,
+                res: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`moe_down` over int8 experts: W2q [E, H, I] i8, s2 [E, H] fp32 (decode.hip
+    ``nos_moe_down_q8``); the slots summed in the order 0 .. k - 1 without atomics.  CPU tensors:
+    :func:`moe_down_q8_ref`."""
+    return _moe_down_quant("q8", act, idx, w, W2q, s2, res, out)
+
+
+def moe_glu_mx4(x: torch.Tensor, idx: torch.Tensor, W13c: torch.Tensor, W13e: torch.Tensor, rms_eps: float = 0.0,
+                gamma: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`moe_glu` over MXFP4 experts: codes W13c [E, 2I, H / 2] u8 and block scales W13e [E, 2I, H / 32]
+    u8 (decode.hip ``nos_moe_glu_mx4``; H % 32 == 0 and I % 32 == 0).  4.25 bits of HBM per weight of the
+    chosen experts, fp32 FMAs on the dequantized values.  Every scale byte must lie in [2, 252] (a
+    registration checks it; this call does not read them).  CPU tensors: :func:`moe_glu_mx4_ref`."""
+    return _moe_glu_quant("mx4", x, idx, W13c, W13e, rms_eps, gamma, out)
+
+
+def moe_down_mx4(act: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, W2c: torch.Tensor, W2e: torch.Tensor,
+                 res: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`moe_down` over MXFP4 experts: codes W2c [E, H, I / 2] u8, block scales W2e [E, H, I / 32] u8
+    (decode.hip ``nos_moe_down_mx4``).  CPU tensors: :func:`moe_down_mx4_ref`."""
+    return _moe_down_quant("mx4", act, idx, w, W2c, W2e, res, out)
+
+
+def _moe_dense_quant(x, Wr, k: int, E: int, expert):
+    """:func:`moe`'s dense path with ``expert(e)`` -> (W13 [2I, H], W2 [H, I]) fp32, made per expert and
+    dropped after its product: one expert's fp32 weights alive at a time, never all of them."""
+    x2 = x.reshape(-1, x.shape[-1])
+    idx, w = moe_route_ref(x2, Wr, k)
+    gates = torch.zeros((x2.shape[0], E), dtype=x2.dtype, device=x.device).scatter_(1, idx.long(), w)
+    y = torch.zeros_like(x2)
+    for e in range(E):
+        W13, W2 = expert(e)
+        I = W13.shape[0] // 2
+        gu = x2 @ W13.T
+        y = y + gates[:, e:e + 1] * ((F.silu(gu[:, :I]) * gu[:, I:]) @ W2.T)
+        del W13, W2
+    return y.view(x.shape)
+
+
+def moe_q8(x: torch.Tensor, Wr: torch.Tensor, W13q: torch.Tensor, s13: torch.Tensor, W2q: torch.Tensor,
+           s2: torch.Tensor, k: int) -> torch.Tensor:
+    """``moe_q8`` (:func:`moe_q8_ref`) of fp32 x [..., H] on the device for steps of more rows than the
+    kernels take (a prefill): :func:`moe`'s dense PyTorch path, one expert at a time dequantized into a
+    transient fp32 buffer by the ``dequant_q8`` kernel (never all experts at once), no host read of a
+    routing value.  CPU tensors: the reference."""
+    if not x.is_cuda:
+        return moe_q8_ref(x, Wr, W13q, s13, W2q, s2, k)
+    return _moe_dense_quant(x, Wr, k, W13q.shape[0], lambda e: (dequant_q8(W13q[e], s13[e]), dequant_q8(W2q[e], s2[e])))
+
+
+def moe_mx4(x: torch.Tensor, Wr: torch.Tensor, W13c: torch.Tensor, W13e: torch.Tensor, W2c: torch.Tensor,
+            W2e: torch.Tensor, k: int) -> torch.Tensor:
+    """``moe_mx4`` (:func:`moe_mx4_ref`) of fp32 x [..., H] for steps of more rows than the kernels take:
+    as :func:`moe_q8`, with the ``dequant_mx4`` kernel.  CPU tensors: the reference."""
+    if not x.is_cuda:
+        return moe_mx4_ref(x, Wr, W13c, W13e, W2c, W2e, k)
+    return _moe_dense_quant(x, Wr, k, W13c.shape[0],
+                            lambda e: (dequant_mx4(W13c[e], W13e[e]), dequant_mx4(W2c[e], W2e[e])))
+
+
 def set_attention_h3g_kvsplit(n: int) -> None:
     """Key splits of :func:`sdpa` (0 = auto: fill the CU slots)."""
     _lib.check(_lib.lib().nos_attn_h3g_set_kvsplit(int(n)), "nos_attn_h3g_set_kvsplit")
@@ -2256,6 +2477,8 @@ __all__ = ["glu", "kv_write", "rotary_at", "sdpa_cache", "pos_update", "argmax",
            "linear_mx4", "linear_mx4_ref","lora", "lora_ref", "lora_shrink", "lora_shrink_ref", "lora_expand_ref", "linear_lora",
            "LORA_MAX_RANK", "moe", "moe_ref", "moe_route", "moe_glu", "moe_down", "moe_route_ref", "moe_glu_ref",
            "moe_down_ref", "MOE_MAX_EXPERTS", "MOE_MAX_TOP_K",
+           "moe_q8", "moe_mx4", "moe_q8_ref", "moe_mx4_ref", "moe_glu_q8", "moe_down_q8", "moe_glu_mx4", "moe_down_mx4",
+           "moe_glu_q8_ref", "moe_down_q8_ref", "moe_glu_mx4_ref", "moe_down_mx4_ref",
            "DecodePartials", "conv2d", "matmul", "sdpa", "linear_rms", "embedding", "rmsnorm", "softmax", "rotary", "conv2d_ref",
            "sdpa_ref", "rope_ref", "rmsnorm_ref", "linear_rms_ref", "set_attention_h3g_kvsplit", "EPI_BIAS_ROW",
            "sdpa_lse", "sdpa_bwd", "sdpa_lse_ref", "sdpa_bwd_ref", "sdpa_bwd_workspace_bytes"]

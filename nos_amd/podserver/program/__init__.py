@@ -20,11 +20,12 @@ Wire form (JSON object; the weights travel as the message payload)::
 Values are SSA names; nodes are listed in execution order.  Wire dtypes are
 ``fp32`` (IEEE float32, little endian), ``bf16`` (the upper 16 bits of a
 float32, little-endian uint16) and, for the weight of a ``linear_q8`` node
-only, ``i8`` (two's-complement int8 rows with one fp32 scale per row:
-weight-only quantization, a storage format -- the math stays fp32) and,
-for inputs 1 and 2 of a ``linear_mx4`` node only, ``u8`` (OCP MXFP4: two
-4-bit E2M1 codes a byte, and one E8M0 scale byte per 32 consecutive inputs
-of a row, each in [2, 252]).
+and the expert codes of a ``moe_q8`` node (inputs 2 and 4) only, ``i8``
+(two's-complement int8 rows with one fp32 scale per row: weight-only
+quantization, a storage format -- the math stays fp32) and, for inputs 1
+and 2 of a ``linear_mx4`` node and inputs 2 to 5 of a ``moe_mx4`` node only,
+``u8`` (OCP MXFP4: two 4-bit E2M1 codes a byte, and one E8M0 scale byte per
+32 consecutive inputs of a row, each in [2, 252]).
 
 :func:`parse` validates a program completely before anything is allocated:
 the op whitelist, every attribute, the topological order and the exact shape
@@ -69,7 +70,8 @@ adapter tenants ``add(linear | linear_q8, lora)`` at decode rows as the GEMV
 with the adapter epilogue plus one ``lora_shrink`` step (``_fuse_lora``), and
 a ``moe`` at decode rows as ``moe_route`` / ``moe_glu`` / ``moe_down`` with the
 ``rmsnorm`` in front as their prologue and the ``add`` behind as the residual
-(``_fuse_moe``).
+(``_fuse_moe``; ``moe_q8`` / ``moe_mx4`` alike, onto ``moe_glu_q8`` /
+``moe_down_q8`` or ``moe_glu_mx4`` / ``moe_down_mx4``).
 
 The compiled program is a callable ``(x) -> tuple(outputs)``, captured into a
 HIP graph by the server exactly like a built-in model.  :meth:`Program.reference`

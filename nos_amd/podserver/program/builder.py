@@ -89,6 +89,17 @@ def dequantize_rows_mx4(codes: np.ndarray, scales: np.ndarray) -> np.ndarray:
     return np.ldexp(el, np.repeat(s.astype(np.int32) - 127, MX4_BLOCK, axis=1)).astype(np.float32)
 
 
+def _rows_of_experts(quantize, w: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """``quantize`` (a rows quantizer of [N, K]) on a 2-D weight as it is, on a 3-D [E, N, K] on the rows
+    flattened to [E * N, K] with both outputs shaped back to [E, N, ...]."""
+    a = np.asarray(w)
+    if a.ndim != 3:
+        return quantize(w)
+    E, N, K = a.shape
+    q, s = quantize(a.reshape(E * N, K))
+    return q.reshape(E, N, *q.shape[1:]), s.reshape(E, N, *s.shape[1:])
+
+
 class Builder:
     """Assemble a wire program with numpy only (the pod side never imports
     torch).  ``param`` appends a weight to the payload; op methods append
@@ -120,8 +131,10 @@ class Builder:
     def param_q8(self, name: str, w_fp32: np.ndarray) -> tuple[str, str]:
         """An fp32 weight [N, K] stored as int8 rows + fp32 row scales
         (:func:`quantize_rows_q8`): the params ``name + ".q8"`` (i8) and
-        ``name + ".scale"`` a ``linear_q8`` node takes."""
-        q, scale = quantize_rows_q8(w_fp32)
+        ``name + ".scale"`` a ``linear_q8`` node takes.  A 3-D weight [E, N, K] (an expert tensor of a
+        ``moe_q8`` node) is quantized by the same rule on its rows flattened to [E * N, K]: q8 [E, N, K] and
+        scale [E, N]."""
+        q, scale = _rows_of_experts(quantize_rows_q8, w_fp32)
         raw = q.tobytes()
         self.params.append({"name": name + ".q8", "shape": list(q.shape), "dtype": "i8", "offset": self.offset,
                             "nbytes": len(raw)})
@@ -148,8 +161,9 @@ class Builder:
     def param_mx4(self, name: str, w_fp32: np.ndarray) -> tuple[str, str]:
         """An fp32 weight [N, K] stored as MXFP4 (:func:`quantize_rows_mx4`): the u8 params
         ``name + ".mx4"`` (codes [N, K / 2]) and ``name + ".e8m0"`` (block scales [N, K / 32]) a
-        ``linear_mx4`` node takes."""
-        codes, scales = quantize_rows_mx4(w_fp32)
+        ``linear_mx4`` node takes.  A 3-D weight [E, N, K] (an expert tensor of a ``moe_mx4`` node) is
+        quantized by the same rule on its rows flattened to [E * N, K]: mx4 [E, N, K / 2] and e8m0 [E, N, K / 32]."""
+        codes, scales = _rows_of_experts(quantize_rows_mx4, w_fp32)
         return self._param_u8(name + ".mx4", codes), self._param_u8(name + ".e8m0", scales)
 
     def state(self, name: str, shape, dtype: str = "fp32") -> str:
@@ -192,6 +206,20 @@ class Builder:
         then up rows) and ``down`` [E, H, I] are fp32 params; each row takes its ``top_k`` experts
         (``ops.tenant.moe_ref``)."""
         return self.op("moe", x, router, gate_up, down, out=out, top_k=int(top_k))
+
+    def moe_q8(self, x: str, router: str, gate_up_q8: str, gate_up_scale: str, down_q8: str, down_scale: str,
+               top_k: int, out: str | None = None) -> str:
+        """:meth:`moe` over int8 experts: ``gate_up_q8`` [E, 2I, H] / ``down_q8`` [E, H, I] i8 and their fp32 row
+        scales [E, 2I] / [E, H] (:meth:`param_q8` of the 3-D tensors); the router stays fp32
+        (``ops.tenant.moe_q8_ref``)."""
+        return self.op("moe_q8", x, router, gate_up_q8, gate_up_scale, down_q8, down_scale, out=out, top_k=int(top_k))
+
+    def moe_mx4(self, x: str, router: str, gate_up_mx4: str, gate_up_e8m0: str, down_mx4: str, down_e8m0: str,
+                top_k: int, out: str | None = None) -> str:
+        """:meth:`moe` over MXFP4 experts: codes ``gate_up_mx4`` [E, 2I, H / 2] / ``down_mx4`` [E, H, I / 2] u8 and
+        their block scales [E, 2I, H / 32] / [E, H, I / 32] u8 (:meth:`param_mx4` of the 3-D tensors); the router
+        stays fp32 (``ops.tenant.moe_mx4_ref``)."""
+        return self.op("moe_mx4", x, router, gate_up_mx4, gate_up_e8m0, down_mx4, down_e8m0, out=out, top_k=int(top_k))
 
     def op(self, op: str, *inputs: str, out: str | None = None, **attrs) -> str:
         self._n += 1

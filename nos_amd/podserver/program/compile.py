@@ -9,7 +9,7 @@ import os
 from dataclasses import dataclass, field
 
 from .graph import Program
-from .ir import BINARY, NATIVE_KINDS, NEVER_FOLD, QUANT_LINEARS, SPEC_KINDS, STATE_WRITERS, STOP_KINDS, UNARY, ProgramError, torch_dtype
+from .ir import BINARY, MOE_OPS, NATIVE_KINDS, NEVER_FOLD, QUANT_LINEARS, SPEC_KINDS, STATE_WRITERS, STOP_KINDS, UNARY, ProgramError, torch_dtype
 from .reference import _eager
 
 
@@ -575,7 +575,7 @@ class Lowered:
         output dim ``d``, as (input index, input dim); None: not row-wise in d."""
         if p.kind in UNARY or p.kind == "cast":
             return [(0, d)]
-        if p.kind in ("linear", *QUANT_LINEARS, "layernorm", "rmsnorm", "moe"):   # moe: each row routes for itself
+        if p.kind in ("linear", *QUANT_LINEARS, "layernorm", "rmsnorm", *MOE_OPS):   # moe: each row routes for itself
             return [(0, d)] if len(self._shape(p.inputs[0])) == r else None
         if p.kind in BINARY:
             plan = []
@@ -909,11 +909,13 @@ class Lowered:
         ``moe_down`` (y).  An ``rmsnorm`` in front whose only reader is the moe becomes the prologue of
         route and glu (the statistic in the kernels, gamma as a pointer: no expert weight is copied or
         folded), an ``add(moe, h)`` after it ``moe_down``'s residual.  More rows (a prefill), or the CPU:
-        the ``moe`` step stays and runs as PyTorch ops on the device."""
+        the ``moe`` step stays and runs as PyTorch ops on the device.  ``moe_q8`` / ``moe_mx4`` (quantized experts)
+        lower exactly alike, onto ``moe_glu_q8`` / ``moe_down_q8`` or ``moe_glu_mx4`` / ``moe_down_mx4`` with the
+        codes and their scales as operands; the route launch is the same."""
         from ...ops.tenant import GEMV_MAX_ROWS, GEMV_X_BYTES
 
         st = self.stats
-        st["moe_blocks"] = sum(1 for s in steps if s.kind == "moe")
+        st["moe_blocks"] = sum(1 for s in steps if s.kind in MOE_OPS)
         st["moe_launches"] = st["moe_rms_prologue"] = st["moe_residual_fused"] = 0
         if not self.gpu or not st["moe_blocks"]:
             return steps
@@ -927,14 +929,17 @@ class Lowered:
         rename: dict[str, str] = {}
         out: list[_Step] = []
         for s in steps:
-            if s.kind != "moe":
+            if s.kind not in MOE_OPS:
                 out.append(s)
                 continue
-            x, wr, w13, w2 = s.inputs
+            # the expert operands: W13 and W2, each followed by its scales when quantized
+            x, wr, *experts = s.inputs
+            n13 = len(experts) // 2
+            sfx = s.kind[3:]   # "", "_q8" or "_mx4"
             xs, k = tuple(self._shape(x)), int(s.attrs["top_k"])
-            rows, H, I = math.prod(xs[:-1]), xs[-1], self._shape(w13)[1] // 2
+            rows, H, I = math.prod(xs[:-1]), xs[-1], self._shape(experts[0])[1] // 2
             if (rows > GEMV_MAX_ROWS or H * 4 > GEMV_X_BYTES or k * I * 4 > GEMV_X_BYTES
-                    or not all(i in self.consts for i in (wr, w13, w2))):
+                    or not all(i in self.consts for i in (wr, *experts))):
                 out.append(s)
                 continue
             pro: dict = {}
@@ -960,8 +965,8 @@ class Lowered:
             self._new_shapes[rt], self._new_dtypes[rt] = (rows, 2 * k), "i32"
             self._new_shapes[act], self._new_dtypes[act] = (rows, k, I), "fp32"
             out.append(_Step("moe_route", [x, wr] + gam, rt, {"top_k": k, **pro}))
-            out.append(_Step("moe_glu", [x, rt, w13] + gam, act, dict(pro)))
-            out.append(_Step("moe_down", [act, rt, w2] + res, s.output, down))
+            out.append(_Step("moe_glu" + sfx, [x, rt, *experts[:n13]] + gam, act, dict(pro)))
+            out.append(_Step("moe_down" + sfx, [act, rt, *experts[n13:]] + res, s.output, down))
             st["moe_launches"] += 3
         kept = []
         for s in out:

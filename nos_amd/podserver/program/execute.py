@@ -43,6 +43,17 @@ class CompiledProgram(Lowered):
                 shp = self._shape(s.output)
                 res = _rows(a[3]).view(-1, shp[-1]) if s.attrs.get("residual") else None
                 y = T.moe_down(a[0], a[1][0], a[1][1], a[2], res=res).view(shp)
+            elif k in ("moe_glu_q8", "moe_glu_mx4"):   # inputs: x, (idx, w), codes, scales, [gamma]
+                y = (T.moe_glu_q8 if k == "moe_glu_q8" else T.moe_glu_mx4)(
+                    _rows(a[0]).view(-1, a[0].shape[-1]), a[1][0], a[2], a[3], rms_eps=float(s.attrs.get("eps", 0.0)),
+                    gamma=a[4] if s.attrs.get("gamma") else None)
+            elif k in ("moe_down_q8", "moe_down_mx4"):   # inputs: act, (idx, w), codes, scales, [residual]
+                shp = self._shape(s.output)
+                res = _rows(a[4]).view(-1, shp[-1]) if s.attrs.get("residual") else None
+                y = (T.moe_down_q8 if k == "moe_down_q8" else T.moe_down_mx4)(a[0], a[1][0], a[1][1], a[2], a[3],
+                                                                             res=res).view(shp)
+            elif k in ("moe_q8", "moe_mx4"):   # a prefill: the dense path, one expert dequantized at a time
+                y = (T.moe_q8 if k == "moe_q8" else T.moe_mx4)(*a[:6], int(s.attrs["top_k"]))
             elif k == "moe":   # more rows than the kernels take (a prefill): PyTorch ops, no host read of the routing
                 y = T.moe(a[0], a[1], a[2], a[3], int(s.attrs["top_k"]))
             elif k == "linear" and s.attrs.get("x_partials"):   # x = the decode attention's split partials

@@ -8,7 +8,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .ir import GEMM_OPS, MX4_SCALE_MAX, MX4_SCALE_MIN, NEVER_FOLD, QUANT_LINEARS, Node, Value, torch_dtype
+from .ir import GEMM_OPS, MOE_OPS, MX4_SCALE_MAX, MX4_SCALE_MIN, NEVER_FOLD, QUANT_LINEARS, Node, Value, torch_dtype
 from .reference import _eager
 
 def _workspace(node: Node, ins: list[Value], out: Value, f32_math: str) -> int:
@@ -52,16 +52,19 @@ def _workspace(node: Node, ins: list[Value], out: Value, f32_math: str) -> int:
         if b * s <= 8:
             return b * s * r * 4
         return b * (r * k + n * r) * 4 + b * s * r * 4 + 2 * out.numel * 4
-    if op == "moe":
+    if op in MOE_OPS:
         # decode rows: idx and w [rows, k] and act [rows, k, I] between the three launches; more rows (a
         # prefill) run dense over the experts: the gates [rows, E] and, per expert, the merged product
         # [rows, 2I], its activation [rows, I] and the down product and running sum [rows, H] (the expert
         # weights themselves are params: charged once, never copied)
+        # quantized experts (moe_q8, moe_mx4): decode rows as moe; a prefill also holds ONE expert's two tensors
+        # dequantized into fp32 at a time ((2I H + H I) x 4 bytes), never all of them
         h = ins[0].shape[-1]
         rows, (e, i2, _), k = ins[0].numel // h, ins[2].shape, node.attrs["top_k"]
         if rows <= 8:
             return rows * k * (8 + i2 // 2 * 4)
-        return rows * (3 * e + 2 * k) * 4 + rows * (i2 + i2 // 2 + 3 * h) * 4
+        one = (i2 * h + h * (i2 // 2)) * 4 if op != "moe" else 0
+        return rows * (3 * e + 2 * k) * 4 + rows * (i2 + i2 // 2 + 3 * h) * 4 + one
     if op == "matmul":
         k = ins[0].shape[-1]
         kp = -(-k // 32) * 32
@@ -215,6 +218,7 @@ class Program:
         # the block scales of the MXFP4 linears: one host pass over each, so that no kernel sees a scale byte
         # outside the range it is defined (and tested) on
         mx4_scales = {n.inputs[2] for n in self.nodes if n.op == "linear_mx4"}
+        mx4_scales |= {i for n in self.nodes if n.op == "moe_mx4" for i in (n.inputs[3], n.inputs[5])}
         for name, v in self.params.items():
             off, nb = self.param_layout[name]
             raw = np.frombuffer(buf[off:off + nb],

@@ -154,15 +154,19 @@ MAX_STATE = 1024
 # weights are chosen per row by a value computed on the device (ops.tenant.moe_ref)
 MOE_MAX_EXPERTS = 64         # a lane per expert in the route kernel
 MOE_MAX_TOP_K = 8
-OPS = OPS + STATE_OPS + ("moe",)
+# quantized experts: moe_q8(x, Wr, W13q, s13, W2q, s2; top_k) holds the expert tensors as int8 rows with an fp32
+# scale per row, moe_mx4(x, Wr, W13c, W13e, W2c, W2e; top_k) as MXFP4 codes and E8M0 block scales (storage
+# formats: moe over the dequantized experts, ops.tenant.moe_q8_ref / moe_mx4_ref); the router stays fp32
+MOE_OPS = ("moe", "moe_q8", "moe_mx4")
+OPS = OPS + STATE_OPS + MOE_OPS
 # linear_q8: folding it would materialise the fp32 weight the format exists to avoid
-NEVER_FOLD = ("attention", "sdpa", "linear_q8", "linear_mx4", "moe", *STATE_OPS)
+NEVER_FOLD = ("attention", "sdpa", "linear_q8", "linear_mx4", *MOE_OPS, *STATE_OPS)
 QUANT_LINEARS = ("linear_q8", "linear_mx4")   # weight-only linears: (x, wq, wscale, [bias]), never folded
 # step kinds that run a gfx950 kernel of libnos_hip.so (CompiledProgram.stats["kernels"])
 NATIVE_KINDS = ("linear", "linear_ln", "linear_rms", "ln_qkv_attention", "attention", "layernorm", "conv2d", "matmul",
                 "softmax", "embedding", "rmsnorm", "rotary", "sdpa", "patches", "unary", "kv_write", "sdpa_cache",
                 "rotary_at", "pos_add", "pos_set", "argmax", "sample", "glu", "linear_q8", "linear_mx4", *STOP_OPS, "stop_step", *SPEC_OPS, "spec_step", "lora_shrink",
-                "moe_route", "moe_glu", "moe_down")
+                "moe_route", "moe_glu", "moe_down", "moe_glu_q8", "moe_down_q8", "moe_glu_mx4", "moe_down_mx4")
 # the steps a speculating tenant's verify program closes with (CompiledProgram.stats["spec_launches"]);
 # spec_step: spec_accept / hist_write / pos_advance / spec_draft fused into one launch
 SPEC_KINDS = (*SPEC_OPS, "spec_step")

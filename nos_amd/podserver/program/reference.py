@@ -149,6 +149,8 @@ def _eager(op: str, args: list, attrs: dict, ref: bool = False):
         return T.spec_draft(args[0], args[1], int(attrs["k"]))
     if op == "lora":
         return T.lora_ref(args[0], args[1], args[2], args[3])
+    if op in ("moe_q8", "moe_mx4"):   # moe over the experts dequantized in fp32, in x's arithmetic
+        return (T.moe_q8_ref if op == "moe_q8" else T.moe_mx4_ref)(*args[:6], int(attrs["top_k"]))
     if op == "moe":   # in x's arithmetic: fp32 for a program, fp64 when a test passes fp64 tensors
         return T.moe_ref(args[0], args[1], args[2], args[3], int(attrs["top_k"]))
     if op == "pos_set":

@@ -542,6 +542,49 @@ def _infer(node: Node, ins: list[Value], gpu: bool) -> tuple[tuple[int, ...], st
         _req(H % 4 == 0 and I % 4 == 0, f"{what}: H % 4 == 0 and I % 4 == 0 required (16-byte loads), got H = {H}, "
              f"I = {I}")
         return x.shape, "fp32"
+    if op in ("moe_q8", "moe_mx4"):
+        # moe over quantized experts (ops.tenant.moe_q8_ref / moe_mx4_ref): what moe checks, and the storage format's
+        # params -- int8 codes [E, N, K] with fp32 scales [E, N], or MXFP4 codes u8 [E, N, K / 2] with E8M0 scale
+        # bytes u8 [E, N, K / 32]; the router stays an fp32 param
+        only("top_k")
+        arity(6, 6)
+        x, Wr, W13, S13, W2, S2 = ins
+        q8 = op == "moe_q8"
+        fmt, cdt, sdt, mult, per = ("int8", "i8", "fp32", 16, 1) if q8 else ("MXFP4", "u8", "u8", MX4_BLOCK, 2)
+        _req(x.dtype == "fp32" and len(x.shape) >= 2,
+             f"{what}: x must be fp32 [..., H] (a bf16 x is not taken), got {x.dtype} {list(x.shape)}")
+        _req(Wr.kind == "param" and Wr.dtype == "fp32",
+             f"{what}: the router Wr must be an fp32 param (routing is not quantized), got {Wr.kind} {Wr.dtype} "
+             f"{Wr.name!r}")
+        _req(all(w.kind == "param" and w.dtype == cdt for w in (W13, W2)),
+             f"{what}: the expert codes W13 and W2 must be {cdt} params ({fmt} is a storage format: the weights are "
+             f"chosen on the device, never computed), got "
+             + ", ".join(f"{w.kind} {w.dtype} {w.name!r}" for w in (W13, W2)))
+        _req(all(w.kind == "param" and w.dtype == sdt for w in (S13, S2)),
+             f"{what}: the expert scales must be {sdt} params, got "
+             + ", ".join(f"{w.kind} {w.dtype} {w.name!r}" for w in (S13, S2)))
+        H = x.shape[-1]
+        _req(len(Wr.shape) == 2 and len(W13.shape) == 3 and len(W2.shape) == 3 and W13.shape[1] % 2 == 0
+             and H % per == 0 and Wr.shape == (W13.shape[0], H) and W13.shape[2] * per == H
+             and W2.shape[:2] == (W13.shape[0], H) and W2.shape[2] * per == W13.shape[1] // 2,
+             f"{what}: the weights' shapes must match: Wr [E, H], codes [E, 2I, H{' / 2' if per == 2 else ''}] and "
+             f"[E, H, I{' / 2' if per == 2 else ''}] with H = {H}, got {list(Wr.shape)}, {list(W13.shape)} and "
+             f"{list(W2.shape)}")
+        E, I = Wr.shape[0], W13.shape[1] // 2
+        _req(H % mult == 0 and I % mult == 0,
+             f"{what}: H % {mult} == 0 and I % {mult} == 0 required ("
+             + ("16 int8 weights a 16-byte load" if q8 else f"an MXFP4 block is {MX4_BLOCK} consecutive inputs under one "
+                "scale byte") + f"), got H = {H}, I = {I}")
+        want13, want2 = ((E, 2 * I), (E, H)) if q8 else ((E, 2 * I, H // MX4_BLOCK), (E, H, I // MX4_BLOCK))
+        _req(S13.shape == want13 and S2.shape == want2,
+             f"{what}: the scales' shapes must match the codes: {list(want13)} and {list(want2)} ("
+             + ("one per row" if q8 else f"one byte per {MX4_BLOCK} inputs of a row")
+             + f"), got {list(S13.shape)} and {list(S2.shape)}")
+        _req(E <= MOE_MAX_EXPERTS, f"{what}: E = {E} experts; E <= {MOE_MAX_EXPERTS} required")
+        k = _int(a.get("top_k"), f"{what}: top_k", 1)
+        _req(k <= min(E, MOE_MAX_TOP_K), f"{what}: 1 <= top_k <= min(E, {MOE_MAX_TOP_K}) = {min(E, MOE_MAX_TOP_K)} "
+             f"required, got {k}")
+        return x.shape, "fp32"
     raise ProgramError(f"{what}: op {op!r} is not one the pod server runs (whitelist: {' '.join(OPS)})")
 
 
@@ -734,11 +777,11 @@ def parse(obj: dict, payload: bytes | memoryview = b"", gpu: bool = False) -> Pr
                 _req(k in slots, f"node {n.output!r} ({op}): input {r!r} is an i8 state; only kv_write and "
                      f"sdpa_cache take one, as their cache")
             else:
-                _req(op == "linear_q8" and k == 1, f"node {n.output!r} ({op}): input {r!r} is an i8 param; only "
+                _req((op == "linear_q8" and k == 1) or (op == "moe_q8" and k in (2, 4)), f"node {n.output!r} ({op}): input {r!r} is an i8 param; only "
                      f"linear_q8 takes one, as its weight")
         # a u8 value is an MXFP4 weight's codes or block scales: only linear_mx4 reads it, as input 1 or 2
         for k, r in enumerate(refs):
-            _req(values[r].dtype != "u8" or (op == "linear_mx4" and k in (1, 2)),
+            _req(values[r].dtype != "u8" or (op == "linear_mx4" and k in (1, 2)) or (op == "moe_mx4" and 2 <= k <= 5),
                  f"node {n.output!r} ({op}): input {k} {r!r} is a u8 param; only linear_mx4 takes one, as its codes "
                  f"(input 1) or its block scales (input 2)")
         shape, dt = _infer(n, [values[r] for r in refs], gpu)

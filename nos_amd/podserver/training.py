@@ -38,6 +38,7 @@ import math
 import os
 
 from .program import Program, ProgramError, _eager, _qkv_views, _req
+from .program.ir import MOE_OPS
 
 LOSSES = ("mse", "cross_entropy")
 _STEP_SPLIT = 1 << 24   # a checkpointed step count = hi * 2^24 + lo, both exact in float32
@@ -54,8 +55,9 @@ def parse_train_spec(spec, prog: Program) -> dict:
     """Validate a register request's ``train`` spec against the program;
     returns it normalised, with the target's shape and dtype."""
     _req(isinstance(spec, dict), "train must be an object")
-    _req(not any(n.op == "moe" for n in prog.nodes),
-         "a program holding a moe node cannot be a training tenant: its routing (top-k, arg-max) has no trained "
+    moe = next((n.op for n in prog.nodes if n.op in MOE_OPS), "moe")
+    _req(not any(n.op in MOE_OPS for n in prog.nodes),
+         f"a program holding a {moe} node cannot be a training tenant: its routing (top-k, arg-max) has no trained "
          "form here (no auxiliary load-balancing loss, no gradient through the selection); serve it for inference")
     extra = set(spec) - SPEC_KEYS
     _req(not extra, f"unknown train keys {sorted(extra)}")
