@@ -35,6 +35,12 @@
 // nos_attn_h3g_lse also stores every query row's log-sum-exp (natural log of
 // sum_j exp(scale q_i . k_j) over the keys the row sees) for the backward
 // (attention_h3g_bwd.hip); O is the same bits with or without it.
+//
+// nos_attn_h3g_cache / nos_attn_h3g_cache_ring run the same kernel over the
+// K / V caches of a decoder tenant for a step of several tokens (an extend
+// chunk, a long windowed prefill): the query positions come from device-side
+// counters, the pre-pass and the tile loop are bounded by them (template
+// parameter CACHE; attn_kv_planes.h 1', 3').
 #include <float.h>
 #include <limits.h>
 #include <math.h>
@@ -60,12 +66,19 @@ using nos::glds16;  // the asm form: in-flight tiles are not drained before ever
 using nos::glds16_s;
 
 // ---------------------------------------------------------------- 4. attention
-template <int D, bool CAUSAL, bool ROPE, bool PERSIST>
+// CACHE: the keys are a K / V cache of Skv rows (slots) per sequence, attended by a step of Sq tokens at
+// the device-side counters cs.pos (nos_attn_h3g_cache*): every item derives its sequence's key count,
+// mask offset and tile range from pos[b], so one launch shape serves every step.  PLAIN: query i sees the
+// keys 0 .. min(pos[b] + i, Skv - 1) -- the causal mask with a per-sequence off (CAUSAL is set).  RING:
+// the slots of a sliding window's ring in slot order, masked per element (kv_ring.h; CAUSAL is clear).
+enum { NO_CACHE = 0, PLAIN_CACHE = 1, RING_CACHE = 2 };
+
+template <int D, bool CAUSAL, bool ROPE, bool PERSIST, int CACHE = NO_CACHE>
 __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
     const float* __restrict__ q, int ldq, long long bsq, const _Float16* __restrict__ kvs,
     const float* __restrict__ kvsc, float* __restrict__ o, int ldo, long long bso, int B, int H, int Hkv, int Sq,
     int Skv, float c, int nqb, int nsplit, float* __restrict__ part, const float* __restrict__ rc,
-    const float* __restrict__ rs, float* __restrict__ lse) {
+    const float* __restrict__ rs, float* __restrict__ lse, CacheStep cs) {
   constexpr int NH = D / 64;                 // 64-dim halves
   constexpr int NKS = D / 16;                // 16-deep MFMA steps over D
   constexpr int STAGE = 4 * NH * IMG;
@@ -99,8 +112,9 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
   for (int db = 0; db < 2; ++db)
     voff[db] = (4 * hh + tq) * 128 + (((4 * (db ^ vlb)) + 2 * g16 + (tp >> 1)) << 4) + 8 * (tp & 1);
 
-  const int skvp = padded_keys(Skv), ntiles = skvp / KVB;
-  const int off = Skv - Sq;  // query i sees keys <= i + off (causal; 0 for self-attention)
+  const int skvp = padded_keys(Skv);
+  int skv = Skv, ntiles = skvp / KVB;  // the keys an item attends (CACHE: its sequence's, set per item)
+  int off = Skv - Sq;  // query i sees keys <= i + off (causal; 0 for self-attention; CACHE: pos[b])
   int soff[PPW];
 #pragma unroll
   for (int i = 0; i < PPW; ++i) {
@@ -121,7 +135,26 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
     const int qb = CAUSAL ? nqb - 1 - (rem - h * nqb) : rem - h * nqb;  // causal: the longest rows first
     const int hk = h / (H / Hkv);
     const int q0 = qb * QB;
-    const int nt_item = CAUSAL ? min(ntiles, (min(q0 + QB, Sq) - 1 + off) / KVB + 1) : ntiles;
+    int pmax = 0, pmod = 0, plo = 0, phi = -1;  // RING: the step's last position and its slot; the positions this block sees
+    bool counted = true;                        // RING: the counter lies in [0, limit) (else: zero rows)
+    int rpos = 0;                               // CACHE: the counter as the rotary tables are read at (any value)
+    if constexpr (CACHE != NO_CACHE) rpos = max(-(1 << 30), min(cs.pos[b], 1 << 30));
+    if constexpr (CACHE == PLAIN_CACHE) {
+      off = max(min(rpos, Skv), -Sq);  // a counter past the cache sees all of it, one before it nothing
+      skv = min(off + Sq, Skv);
+      ntiles = padded_keys(skv) / KVB;
+    }
+    if constexpr (CACHE == RING_CACHE) {
+      off = rpos;
+      counted = off >= 0 && off < cs.limit;
+      if (!counted) off = 0;
+      pmax = off + Sq - 1;
+      pmod = nos::ring_mod(pmax, Skv);
+      plo = nos::ring_oldest(off + q0, pmax, Skv, cs.W);
+      phi = off + min(q0 + QB, Sq) - 1;
+    }
+    int nt_item = CAUSAL ? min(ntiles, (min(q0 + QB, Sq) - 1 + off) / KVB + 1) : ntiles;
+    if constexpr (CACHE != NO_CACHE) nt_item = counted ? max(nt_item, 0) : 0;  // rows before position 0 see no tile
     const int tps = (nt_item + nsplit - 1) / nsplit;
     const int t0 = sp * tps, t1 = min(nt_item, t0 + tps);
     const float ksc = kvsc[(b * Hkv + hk) * 2], vinv = 1.f / kvsc[(b * Hkv + hk) * 2 + 1];
@@ -143,8 +176,10 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
         x[ks][4] = x1.x; x[ks][5] = x1.y; x[ks][6] = x1.z; x[ks][7] = x1.w;
       }
       if constexpr (ROPE) {  // partner dims d +- D/2 are ks +- NKS/2 of this same lane
-        const float* cr = rc + (long long)(qr + off) * D + 8 * hh;
-        const float* sr = rs + (long long)(qr + off) * D + 8 * hh;
+        // the table row of the query's position (CACHE: clamped to the tables, as rotary_at does)
+        const int rr = CACHE != NO_CACHE ? max(0, min(qr + rpos, cs.R - 1)) : qr + off;
+        const float* cr = rc + (long long)rr * D + 8 * hh;
+        const float* sr = rs + (long long)rr * D + 8 * hh;
         float y[NKS][8];
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks)
@@ -178,8 +213,8 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
     auto stage_piece = [&](int t, int buf, int i) {
       const int p = wid * PPW + i;
       long long o2 = (long long)t * (KVB * 4) * D + soff[i];
-      if ((t + 1) * KVB > Skv) {  // tail tile: rows past Skv re-read the last key (masked)
-        const int over = t * KVB + (p & 3) * 8 + (lane >> 3) - (Skv - 1);
+      if ((t + 1) * KVB > skv) {  // tail tile: rows past skv re-read the last key (masked)
+        const int over = t * KVB + (p & 3) * 8 + (lane >> 3) - (skv - 1);
         if (over > 0) o2 -= (long long)over * 4 * D;
       }
       glds16(pb + o2, smem + buf * STAGE + (p >> 2) * IMG + (p & 3) * 8 * 128);
@@ -197,21 +232,30 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
       for (int i = 0; i < 16; ++i) oacc[db][i] = 0.f;
     float m = 0.f, l = 0.f;
 
-    if (t0 < t1) {
+    // RING: the next tile from t on with a slot some row of this block sees (block-uniform); else t
+    auto next_tile = [&](int t) {
+      if constexpr (CACHE == RING_CACHE)
+        while (t < t1 && nos::ring_split_rows(t * KVB, min(KVB, skv - t * KVB), plo, phi, skv) == 0) ++t;
+      return t;
+    };
+    const int tf = next_tile(t0);  // the first tile of this item
+    if (tf < t1) {
 #pragma unroll
-      for (int i = 0; i < PPW; ++i) stage_piece(t0, 0, i);
+      for (int i = 0; i < PPW; ++i) stage_piece(tf, 0, i);
       dma_wait_publish();
     }
     const int qw0 = q0 + wid * 32;  // this wave's first query row (wave-uniform mask test)
-    for (int t = t0; t < t1; ++t) {
-      const int buf = (t - t0) & 1;
-      if (t + 1 < t1) {
-        if ((t + 2) * KVB <= Skv) {
+    int nth = 0;                    // RING: tiles done (the stage ring's phase when tiles are skipped)
+    for (int t = tf, tn; t < t1; t = tn) {
+      const int buf = CACHE == RING_CACHE ? (nth++ & 1) : (t - t0) & 1;
+      tn = next_tile(t + 1);
+      if (tn < t1) {
+        if ((tn + 1) * KVB <= skv) {
 #pragma unroll
-          for (int i = 0; i < PPW; ++i) stage_full(t + 1, buf ^ 1, i);
+          for (int i = 0; i < PPW; ++i) stage_full(tn, buf ^ 1, i);
         } else {
 #pragma unroll
-          for (int i = 0; i < PPW; ++i) stage_piece(t + 1, buf ^ 1, i);
+          for (int i = 0; i < PPW; ++i) stage_piece(tn, buf ^ 1, i);
         }
       }
       const unsigned char* st = smem + buf * STAGE;
@@ -229,10 +273,16 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
             a[pc] = *reinterpret_cast<const f16x8_t*>(st + (pc * NH + hf) * IMG + koff[ks]);
           s = nos::mma3h(a, qf[hf * 4 + ks], s);
         }
-      if ((t + 1) * KVB > Skv) {
+      if ((t + 1) * KVB > skv) {
 #pragma unroll
         for (int i = 0; i < 16; ++i)
-          if (t * KVB + (i & 3) + 8 * (i >> 2) + 4 * hh >= Skv) s[i] = -INFINITY;
+          if (t * KVB + (i & 3) + 8 * (i >> 2) + 4 * hh >= skv) s[i] = -INFINITY;
+      }
+      if constexpr (CACHE == RING_CACHE) {  // the window, per element: the slots hold positions in no order
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          if (!nos::ring_visible_m(t * KVB + (i & 3) + 8 * (i >> 2) + 4 * hh, qrow + off, pmax, pmod, skv, cs.W))
+            s[i] = -INFINITY;
       }
       if (CAUSAL && t * KVB + KVB - 1 > qw0 + off) {  // a diagonal tile of this wave
 #pragma unroll
@@ -246,7 +296,7 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
       // reference -1e30; the new reference is set directly (m + delta would
       // lose a real maximum against 1e30 and break P <= 2^8)
       const float mnew = fmaxf(xor32_max(mt) * fs, -1e30f);
-      if (t == t0) {
+      if (t == tf) {
         m = mnew;
       } else if (!__all(mnew - m <= RESCALE_THR)) {
         const float mref = fmaxf(mnew, m);
@@ -300,13 +350,14 @@ __global__ __launch_bounds__(64 * HW, D == 64 ? 2 : 1) void attn_h3g_kernel(
         for (int db = 0; db < 2 * NH; ++db) nos::store_acc32(op + 32 * db, oacc[db], vinv, hh);
         if (hh == 0) {
           float* ml = part_ml(part, nsplit, B, Sq, H, ldh, row, h);
-          ml[0] = t0 < t1 ? m : -1e30f;
+          ml[0] = tf < t1 ? m : -1e30f;
           ml[1] = lt;
         }
       }
       continue;
     }
-    const float inv = vinv / lt;
+    // CACHE: a row that sees no key (a bad counter, a position before 0) ends as zeros
+    const float inv = CACHE != NO_CACHE && !(lt > 0.f) ? 0.f : vinv / lt;
     if (qrow < Sq) {
       float* op = o + b * bso + (long long)qrow * ldo + h * D;
 #pragma unroll
@@ -354,6 +405,30 @@ NOS_API int nos_attn_h3g_set_kvsplit(int n) {
 
 namespace {
 
+// the attention launch of every entry point: the kernel's instantiation for (D, causal, rope, CACHE),
+// persistent under a CU budget; a plain cache is causal, a ring is masked per element instead
+template <int D, bool CZ, int CACHE, class... A>
+int launch_h3g_d(bool rope, long long items, hipStream_t stream, A... args) {
+  constexpr size_t lds = 2 * 4 * (D / 64) * IMG;
+  if (rope)
+    return nos::launch_items(attn_h3g_kernel<D, CZ, true, true, CACHE>, attn_h3g_kernel<D, CZ, true, false, CACHE>,
+                             64 * HW, lds, items, stream, args...);
+  return nos::launch_items(attn_h3g_kernel<D, CZ, false, true, CACHE>, attn_h3g_kernel<D, CZ, false, false, CACHE>,
+                           64 * HW, lds, items, stream, args...);
+}
+template <int CACHE, class... A>
+int launch_h3g(int D, bool causal, bool rope, long long items, hipStream_t stream, A... args) {
+  if constexpr (CACHE != RING_CACHE) {
+    if (causal || CACHE == PLAIN_CACHE)
+      return D == 64 ? launch_h3g_d<64, true, CACHE>(rope, items, stream, args...)
+                     : launch_h3g_d<128, true, CACHE>(rope, items, stream, args...);
+  }
+  if constexpr (CACHE != PLAIN_CACHE)
+    return D == 64 ? launch_h3g_d<64, false, CACHE>(rope, items, stream, args...)
+                   : launch_h3g_d<128, false, CACHE>(rope, items, stream, args...);
+  return (int)hipErrorInvalidValue;
+}
+
 // the one host path of nos_attn_h3g (lse == nullptr) and nos_attn_h3g_lse
 int attn_h3g_run(const float* q, int ldq, long long bsq, const Rows& k, const Rows& v, float* o, int ldo, long long bso,
                  int B, int H, int Hkv, int Sq, int Skv, int D, int causal, float scale, const float* rope_cos,
@@ -380,26 +455,9 @@ int attn_h3g_run(const float* q, int ldq, long long bsq, const Rows& k, const Ro
   const int nqb = (Sq + QB - 1) / QB;
   const long long nwg1 = (long long)B * H * nqb;
   const int nsplit = pick_split(g_kvsplit, nwg1, L.skvp / KVB, D == 64 ? 2 : 1);
-  int rc;
-  const bool rope = rope_cos != nullptr;
-#define NOS_H3G(d, cz, rp)                                                                                         \
-  rc = nos::launch_items(attn_h3g_kernel<d, cz, rp, true>, attn_h3g_kernel<d, cz, rp, false>, 64 * HW,             \
-                         2 * 4 * (d / 64) * IMG, nwg1 * nsplit, stream, q, ldq, bsq, kvs, kvsc, o, ldo, bso, B, H, \
-                         Hkv, Sq, Skv, c, nqb, nsplit, part, rope_cos, rope_sin, lse)
-  if (D == 64) {
-    if (causal) {
-      if (rope) NOS_H3G(64, true, true); else NOS_H3G(64, true, false);
-    } else {
-      if (rope) NOS_H3G(64, false, true); else NOS_H3G(64, false, false);
-    }
-  } else {
-    if (causal) {
-      if (rope) NOS_H3G(128, true, true); else NOS_H3G(128, true, false);
-    } else {
-      if (rope) NOS_H3G(128, false, true); else NOS_H3G(128, false, false);
-    }
-  }
-#undef NOS_H3G
+  const int rc = launch_h3g<NO_CACHE>(D, causal != 0, rope_cos != nullptr, nwg1 * nsplit, stream, q, ldq, bsq, kvs, kvsc,
+                                      o, ldo, bso, B, H, Hkv, Sq, Skv, c, nqb, nsplit, part, rope_cos, rope_sin, lse,
+                                      CacheStep{});
   if (rc != 0 || nsplit == 1) return rc;
   if (lse != nullptr) return run_merge<0, false, true>(part, o, B, H, D, Sq, nsplit, ldo, bso, stream, lse);
   return run_merge<0, false, false>(part, o, B, H, D, Sq, nsplit, ldo, bso, stream);
@@ -433,4 +491,84 @@ NOS_API int nos_attn_h3g_lse(const float* q, int ldq, long long bsq, const float
   if (lse == nullptr || ((uintptr_t)lse & 3)) return (int)hipErrorInvalidValue;
   return attn_h3g_run(q, ldq, bsq, {k, ldk, bsk}, {v, ldv, bsv}, o, ldo, bso, B, H, Hkv, Sq, Skv, D, causal, scale,
                       rope_cos, rope_sin, rope_bound, ws, ws_bytes, lse, stream);
+}
+
+// ---------------------------------------------------------------- over K / V caches
+// Workspace bytes of nos_attn_h3g_cache / nos_attn_h3g_cache_ring over caches of L rows (slots): sized
+// from L alone, whatever the counters hold.
+NOS_API long long nos_attn_h3g_cache_workspace(int B, int H, int Hkv, int Sq, int L, int D) {
+  return nos_attn_h3g_workspace(B, H, Hkv, Sq, L, D);
+}
+
+namespace {
+
+// the one host path of nos_attn_h3g_cache (window == 0) and nos_attn_h3g_cache_ring: nothing here reads
+// pos -- the grid, the split count and the workspace layout follow L, so a captured graph serves every step
+int attn_h3g_cache_run(const float* q, int ldq, long long bsq, const float* kc, const float* vc, const int* pos,
+                       const float* rope_cos, const float* rope_sin, int R, float* o, int ldo, long long bso, int B,
+                       int H, int Hkv, int Sq, int L, int D, float scale, void* ws, long long ws_bytes, int window,
+                       int limit, hipStream_t stream) {
+  if (!attn_call_ok(B, H, Hkv, Sq, L, D, 0, scale, ws, ws_bytes, nos_attn_h3g_cache_workspace) ||
+      !Rows{q, ldq, bsq}.ok(H, D) || !Rows{o, ldo, bso}.ok(H, D) || !Rows{kc, Hkv * D, 0}.ok(Hkv, D) ||
+      !Rows{vc, Hkv * D, 0}.ok(Hkv, D) || pos == nullptr || ((uintptr_t)pos & 3))
+    return (int)hipErrorInvalidValue;
+  if ((rope_cos == nullptr) != (rope_sin == nullptr) || (rope_cos && R <= 0)) return (int)hipErrorInvalidValue;
+  if (window != 0 && !nos::ring_args_ok(L, Sq, window, limit, rope_cos != nullptr, R)) return (int)hipErrorInvalidValue;
+  const Layout lay = layout(B, H, Hkv, Sq, L, D);
+  if ((long long)B * H * ((Sq + QB - 1) / QB) * MAX_SPLIT > (1LL << 30) || (long long)B * Hkv * lay.skvp * 4 * D > INT_MAX * 8LL ||
+      L > (1 << 30) - Sq)
+    return (int)hipErrorInvalidValue;
+  auto* base = static_cast<unsigned char*>(ws);
+  auto* kvs = reinterpret_cast<_Float16*>(base + lay.planes);
+  auto* absmax = reinterpret_cast<float*>(base + lay.absmax);
+  auto* kvsc = reinterpret_cast<float*>(base + lay.scales);
+  auto* part = reinterpret_cast<float*>(base + lay.part);
+  const CacheStep cs{pos, Sq, window, limit, R};
+  launch_kv_cache_prepass(kc, vc, absmax, kvsc, kvs, B, Hkv, L, D, cs, stream);
+  if (int rc = (int)hipGetLastError()) return rc;
+  const float c = scale * nos::LOG2E;
+  const int nqb = (Sq + QB - 1) / QB;
+  const long long nwg1 = (long long)B * H * nqb;
+  const int nsplit = pick_split(g_kvsplit, nwg1, lay.skvp / KVB, D == 64 ? 2 : 1);
+  const bool rope = rope_cos != nullptr;
+  float* no_lse = nullptr;
+  const int rc = window == 0
+                     ? launch_h3g<PLAIN_CACHE>(D, true, rope, nwg1 * nsplit, stream, q, ldq, bsq, kvs, kvsc, o, ldo, bso,
+                                               B, H, Hkv, Sq, L, c, nqb, nsplit, part, rope_cos, rope_sin, no_lse, cs)
+                     : launch_h3g<RING_CACHE>(D, false, rope, nwg1 * nsplit, stream, q, ldq, bsq, kvs, kvsc, o, ldo, bso,
+                                              B, H, Hkv, Sq, L, c, nqb, nsplit, part, rope_cos, rope_sin, no_lse, cs);
+  if (rc != 0 || nsplit == 1) return rc;
+  return run_merge<0, false, false>(part, o, B, H, D, Sq, nsplit, ldo, bso, stream);
+}
+}  // namespace
+
+// The h3 flash attention of a step of Sq tokens over K / V caches: q fp32 [B, Sq, H, D] (ldq, bsq as in
+// nos_attn_h3g), kc / vc fp32 [B, L, Hkv, D] contiguous and 16-byte aligned (the keys as stored: already
+// rotated), pos i32 [B] on the device.  Query i of sequence b, at position pos[b] + i, attends the keys
+// 0 .. min(pos[b] + i, L - 1); rows at and past pos[b] + Sq are never read (the pre-pass and the kernel are
+// bounded by the counter), so a step's work follows pos, not L.  rope_cos / rope_sin (fp32 [R][D], or
+// null): Q alone is rotated, at table row pos[b] + i clamped to the tables.  A row that sees no key is
+// zeros.  ws: at least nos_attn_h3g_cache_workspace() bytes, 256-byte aligned.  Nothing on the host reads
+// pos: one captured graph serves every step.
+NOS_API int nos_attn_h3g_cache(const float* q, int ldq, long long bsq, const float* kc, const float* vc, const int* pos,
+                               const float* rope_cos, const float* rope_sin, int R, float* o, int ldo, long long bso,
+                               int B, int H, int Hkv, int Sq, int L, int D, float scale, void* ws, long long ws_bytes,
+                               hipStream_t stream) {
+  return attn_h3g_cache_run(q, ldq, bsq, kc, vc, pos, rope_cos, rope_sin, R, o, ldo, bso, B, H, Hkv, Sq, L, D, scale,
+                            ws, ws_bytes, 0, 0, stream);
+}
+
+// nos_attn_h3g_cache over ring caches [B, C, Hkv, D] (kv_ring.h) with a sliding window: the query at
+// position p attends the positions max(0, p - window + 1) .. p, position j in slot j % C, after the
+// step's rows were written.  Only the slots some row of the step sees are read (the others, stale or
+// never written, get zero planes); a counter outside [0, limit) gives zero rows.  window < Sq is legal (a
+// long windowed prefill).  Arguments checked as nos_attn_decode_ring's: min(limit, window + Sq - 1) <= C <=
+// limit, Sq <= C, limit <= R with rotary tables.
+NOS_API int nos_attn_h3g_cache_ring(const float* q, int ldq, long long bsq, const float* kc, const float* vc,
+                                    const int* pos, const float* rope_cos, const float* rope_sin, int R, float* o,
+                                    int ldo, long long bso, int B, int H, int Hkv, int Sq, int C, int D, float scale,
+                                    void* ws, long long ws_bytes, int window, int limit, hipStream_t stream) {
+  if (window < 1) return (int)hipErrorInvalidValue;
+  return attn_h3g_cache_run(q, ldq, bsq, kc, vc, pos, rope_cos, rope_sin, R, o, ldo, bso, B, H, Hkv, Sq, C, D, scale,
+                            ws, ws_bytes, window, limit, stream);
 }

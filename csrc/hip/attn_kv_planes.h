@@ -10,10 +10,15 @@
 //  3. split_kv: K (rotated on the fly) and V as four fp16 planes per token,
 //     [b][kv head][token][K hi, K lo, V hi, V lo][D], 16-byte stores.
 //
+// 1' and 3' are their forms over a K / V cache at device-side counters (the
+// forward over caches, attention_h3g.hip nos_attn_h3g_cache*): only the rows
+// the step attends are read.
+//
 // Below the kernels: what the two host paths share -- the padded sizes, the
 // launches of the pre-pass and the argument checks of the entry points.
 #pragma once
 #include "common.h"
+#include "kv_ring.h"
 #include "split_f16.h"
 
 namespace {
@@ -124,6 +129,94 @@ __global__ __launch_bounds__(256) void split_kv_kernel(const float* __restrict__
   *reinterpret_cast<f16x8_t*>(dst + D) = lo;
 }
 
+// ---------------------------------------------------------------- 1', 3': over a K / V cache
+// The pre-pass of the flash attention over K / V caches [B, L, Hkv, D] (contiguous fp32, keys stored
+// rotated) at the device-side counters pos [B]: only the rows the step of Sq tokens at pos[b] attends
+// are read -- stale rows (a rejected draft's, a sequence's from before a reset, a ring's never written
+// slots) neither set the scales nor reach the planes.
+struct CacheStep {
+  const int* pos;    // i32 [B]
+  int Sq, W, limit;  // W == 0: a plain cache; else a ring of L slots (kv_ring.h)
+  int R;             // rows of the attention's rotary tables for Q (row pos[b] + i, clamped)
+};
+
+// row (slot) s of sequence b's caches is read: plain, s < min(pos[b], L) + Sq (the keys 0 .. the last
+// query's); a ring, slot s holds a position some query row sees (>= the first row's oldest) -- none at a
+// counter outside [0, limit)
+__device__ __forceinline__ bool cache_row_live(int s, int p0, int L, const CacheStep& cs) {
+  if (cs.W == 0) return s < min(p0, L) + cs.Sq;
+  if (p0 < 0 || p0 >= cs.limit) return false;
+  const int pmax = p0 + cs.Sq - 1;
+  return nos::ring_position(s, pmax, L) >= nos::ring_oldest(p0, pmax, L, cs.W);
+}
+
+// kv_absmax_kernel over the live rows of the caches
+__global__ __launch_bounds__(256) void kv_absmax_cache_kernel(const float* __restrict__ k, const float* __restrict__ v,
+                                                              float* __restrict__ part, int L, int Hkv, int D,
+                                                              int nchunk, CacheStep cs) {
+  __shared__ float red[2][4];
+  const int bh = blockIdx.y, chunk = blockIdx.x;
+  const int b = bh / Hkv, h = bh - b * Hkv;
+  const int p0 = cs.pos[b];
+  const int r0 = chunk * ABS_ROWS, r1 = min(L, r0 + ABS_ROWS);
+  const int d4 = D / 4;
+  const int n = (r1 - r0) * d4;
+  float mk = 0.f, mv = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int r = r0 + i / d4, c = (i % d4) * 4;
+    if (!cache_row_live(r, p0, L, cs)) continue;
+    const long long at = (((long long)b * L + r) * Hkv + h) * D + c;
+    const float4 a = *reinterpret_cast<const float4*>(k + at);
+    const float4 e = *reinterpret_cast<const float4*>(v + at);
+    mk = fmaxf(mk, fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))));
+    mv = fmaxf(mv, fmaxf(fmaxf(fabsf(e.x), fabsf(e.y)), fmaxf(fabsf(e.z), fabsf(e.w))));
+  }
+  mk = nos::wave_max(mk);
+  mv = nos::wave_max(mv);
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = mk;
+    red[1][threadIdx.x >> 6] = mv;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const float* r = red[threadIdx.x];
+    part[((long long)bh * nchunk + chunk) * 2 + threadIdx.x] = fmaxf(fmaxf(r[0], r[1]), fmaxf(r[2], r[3]));
+  }
+}
+
+// split_kv_kernel over the caches (no rotation: the keys are stored rotated): the planes of the live
+// rows; a ring's other slots get zero planes (the attention walks every slot), a plain cache's rows past
+// the step are not written (the attention never loads them)
+__global__ __launch_bounds__(256) void split_kv_cache_kernel(const float* __restrict__ k, const float* __restrict__ v,
+                                                             const float* __restrict__ kvsc,
+                                                             _Float16* __restrict__ kvs, int L, int skvp, int Hkv,
+                                                             int D, long long n8, CacheStep cs) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  const int c8 = D / 8;
+  const int ch = (int)(i % c8);
+  long long rest = i / c8;
+  const int t = (int)(rest & 1);
+  rest >>= 1;
+  const int s = (int)(rest % L);
+  const int bh = (int)(rest / L);
+  const int b = bh / Hkv, h = bh - b * Hkv;
+  const bool live = cache_row_live(s, cs.pos[b], L, cs);
+  if (!live && cs.W == 0) return;
+  float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (live) {
+    const float* src = (t == 0 ? k : v) + (((long long)b * L + s) * Hkv + h) * D + ch * 8;
+    const float4 a = *reinterpret_cast<const float4*>(src);
+    const float4 e = *reinterpret_cast<const float4*>(src + 4);
+    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = e.x; x[5] = e.y; x[6] = e.z; x[7] = e.w;
+  }
+  f16x8_t hi, lo;
+  nos::split8h(x, kvsc[bh * 2 + t], hi, lo);
+  _Float16* dst = kvs + (((long long)bh * skvp + s) * 4 + 2 * t) * D + ch * 8;
+  *reinterpret_cast<f16x8_t*>(dst) = hi;
+  *reinterpret_cast<f16x8_t*>(dst + D) = lo;
+}
+
 // ---------------------------------------------------------------- host
 // a [B, S, heads, D] fp32 operand: token row stride ld, batch stride bs (floats)
 struct Rows {
@@ -155,6 +248,20 @@ inline void launch_kv_prepass(const Rows& k, const Rows& v, float* absmax, float
   const long long n8 = (long long)nbh * Skv * 2 * (D / 8);
   hipLaunchKernelGGL(split_kv_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, k.p, v.p, kvsc, kvs, Skv,
                      padded_keys(Skv), Hkv, D, k.ld, k.bs, v.ld, v.bs, rc, rs, n8);
+}
+
+// the three launches over caches kc / vc [B, L, Hkv, D]: grids sized from L alone, the rows read
+// bounded by the device-side counters (cs)
+inline void launch_kv_cache_prepass(const float* kc, const float* vc, float* absmax, float* kvsc, _Float16* kvs, int B,
+                                    int Hkv, int L, int D, const CacheStep& cs, hipStream_t stream) {
+  const int nbh = B * Hkv, nchunk = abs_chunks(L);
+  hipLaunchKernelGGL(kv_absmax_cache_kernel, dim3((unsigned)nchunk, (unsigned)nbh), dim3(256), 0, stream, kc, vc,
+                     absmax, L, Hkv, D, nchunk, cs);
+  hipLaunchKernelGGL(kv_scale_kernel, dim3((unsigned)((2 * nbh + 255) / 256)), dim3(256), 0, stream, absmax, kvsc,
+                     2 * nbh, nchunk, 1.f);
+  const long long n8 = (long long)nbh * L * 2 * (D / 8);
+  hipLaunchKernelGGL(split_kv_cache_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, kc, vc, kvsc, kvs,
+                     L, padded_keys(L), Hkv, D, n8, cs);
 }
 
 // the checks every entry point makes; need: its workspace function (-1 for bad dims)

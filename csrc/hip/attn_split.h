@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void merge_splits_kernel(float* __restrict__ p
     acc.z = fmaf(v.z, a, acc.z);
     acc.w = fmaf(v.w, a, acc.w);
   }
-  const float inv = 1.f / L;
+  const float inv = L > 0.f ? 1.f / L : 0.f;  // every split empty (a cache row that sees no key): zeros
   const float4 y = float4{acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv};
   if constexpr (PLANES) {
     f16x2_t h01, l01, h23, l23;

@@ -2720,10 +2720,7 @@ NOS_API int nos_kv_write(const void* x, int xbf, int ldx, long long bsx, void* c
 // the arguments of a ring cache of C slots at a step of S rows: window W >= 1, min(limit, W + S - 1) <= C
 // <= limit (the step's rows and the first row's window fit), and the rotary tables cover every stored position
 static bool ring_ok(int C, int S, int W, int limit, bool rope, int R) {
-  if (W < 1 || limit < 1 || limit > (1 << 30) || C > limit || S > C) return false;
-  const long long need = (long long)W + S - 1;
-  if (C < (need < limit ? need : limit)) return false;
-  return !rope || limit <= R;
+  return nos::ring_args_ok(C, S, W, limit, rope, R);   // kv_ring.h: shared with attention_h3g.hip
 }
 
 // nos_kv_write into ring caches [B, C, H, D] (kv_ring.h): the row of position p = pos[b] + s goes to slot

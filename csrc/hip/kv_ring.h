@@ -38,6 +38,21 @@ __host__ __device__ inline bool ring_visible(int s, int qpos, int pmax, int C, i
   return a >= 0 && a <= qpos && a > qpos - W;
 }
 
+// ring_visible with m = ring_mod(pmax, C) computed once by the caller (a kernel's inner loop)
+__host__ __device__ inline bool ring_visible_m(int s, int qpos, int pmax, int m, int C, int W) {
+  const int a = s <= m ? pmax - m + s : pmax - m + s - C;
+  return a >= 0 && a <= qpos && a > qpos - W;
+}
+
+// the checks of every entry point that takes a ring cache of C slots at a step of S rows: window W,
+// positions below limit (<= the R rows of the rotary tables, when there are any)
+inline bool ring_args_ok(int C, int S, int W, int limit, bool rope, int R) {
+  if (W < 1 || limit < 1 || limit > (1 << 30) || C > limit || S > C) return false;
+  const long long need = (long long)W + S - 1;
+  if (C < (need < limit ? need : limit)) return false;
+  return !rope || limit <= R;
+}
+
 // the positions some query row of a launch sees: rows at qlo .. qhi (<= pmax) see lo .. qhi, lo the
 // oldest position the first row's window and the ring still hold; lo > qhi: none
 __host__ __device__ inline int ring_oldest(int qlo, int pmax, int C, int W) {

@@ -210,6 +210,13 @@ _SIGS = {
     "nos_attn_h3g_lse": [c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p, c_int, c_ll,
                          c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_float,
                          c_void_p, c_ll, c_void_p, c_void_p],
+    # the flash attention of a multi-token step over K / V caches at device-side positions (attention_h3g.hip)
+    "nos_attn_h3g_cache_workspace": [c_int, c_int, c_int, c_int, c_int, c_int],
+    "nos_attn_h3g_cache": [c_void_p, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                           c_int, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_ll, c_void_p],
+    "nos_attn_h3g_cache_ring": [c_void_p, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                c_void_p, c_int, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                c_ll, c_int, c_int, c_void_p],
     "nos_attn_h3g_bwd_workspace": [c_int, c_int, c_int, c_int, c_int, c_int],
     "nos_attn_h3g_bwd": [c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p, c_int, c_ll,
                          c_void_p, c_int, c_ll, c_void_p, c_void_p, c_int, c_ll, c_void_p, c_int, c_ll, c_void_p, c_int,
@@ -218,7 +225,7 @@ _SIGS = {
 
 
 _RESTYPES = {"nos_attn_f32x6_workspace": c_ll, "nos_attn_h3g_workspace": c_ll, "nos_attn_decode_workspace": c_ll,
-             "nos_attn_h3g_bwd_workspace": c_ll}
+             "nos_attn_h3g_bwd_workspace": c_ll, "nos_attn_h3g_cache_workspace": c_ll}
 
 
 class NativeUnavailable(RuntimeError):

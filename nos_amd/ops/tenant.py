@@ -868,10 +868,66 @@ class DecodePartials:
         self.ws, self.NS, self.G, self.Hkv, self.D, self.shape, self.dtype = ws, NS, G, Hkv, D, tuple(shape), dtype
 
 
+DECODE_MAX_ROWS = 32   # decode.hip MAXR: the G x Sq rows one pass of the decode kernel holds
+
+
+def cache_flash_rule(G: int, Sq: int, D: int, fp32: bool, env=None) -> bool:
+    """Whether a ``sdpa_cache`` step of ``Sq`` tokens with ``G`` query heads per K / V head runs on the flash
+    kernel over the caches: an fp32 tenant with fp32 caches (``fp32``), head_dim 64 or 128, and more rows than
+    one pass of the decode kernel holds (``G x Sq > 32``).  ``NOS_AMD_CACHE_FLASH=0`` (``env``: the environment
+    to read, ``os.environ`` by default) keeps the decode kernel everywhere."""
+    import os
+
+    if (os.environ if env is None else env).get("NOS_AMD_CACHE_FLASH", "1") == "0":
+        return False
+    return bool(fp32) and D in (64, 128) and G * Sq > DECODE_MAX_ROWS
+
+
+def sdpa_cache_flash_workspace_bytes(B: int, H: int, Hkv: int, Sq: int, L: int, D: int) -> int:
+    """Workspace bytes of ``sdpa_cache(flash=True)`` from the shapes alone (the memory estimate needs no
+    library): equals ``nos_attn_h3g_cache_workspace`` (attention_h3g.hip ``layout``)."""
+    def al(x: int) -> int:
+        return -(-x // 256) * 256
+
+    skvp = -(-L // 32) * 32
+    return (al(B * Hkv * skvp * 4 * D * 2) + al(B * Hkv * -(-L // BWD_ABS_ROWS) * 2 * 4) + al(B * Hkv * 2 * 4)
+            + 4 * B * Sq * H * (D + 2) * 4)     # planes, absmax partials, scales, MAX_SPLIT key-split partials
+
+
+def _sdpa_cache_flash(q, kc, vc, pos, scale, rope, fresh, window, limit):
+    """:func:`sdpa_cache` on the flash kernel over fp32 caches (``window`` None: plain caches)."""
+    B, Sq, H, D = q.shape
+    L, Hkv = kc.shape[1], kc.shape[2]
+    if fresh is not None:   # the step's rows first, by kv_write's launch: the same bits in the caches
+        kv_write(kc, fresh[0], pos, rope=rope, second=(vc, fresh[1]), window=window, limit=limit)
+    q, ldq, bsq = _rows(q, aligned=True)
+    c = s_ = None
+    R = 0
+    if rope is not None:
+        c, s_ = rope[0].float().contiguous(), rope[1].float().contiguous()
+        R = c.shape[0]
+        if c.shape[1] != D or s_.shape != c.shape:
+            raise ValueError(f"rotary tables must be [positions, {D}]")
+    lib = _lib.lib()
+    nbytes = int(lib.nos_attn_h3g_cache_workspace(B, H, Hkv, Sq, L, D))
+    if nbytes < 0:
+        raise ValueError(f"sdpa_cache: no flash kernel for q {tuple(q.shape)} over caches {tuple(kc.shape)}")
+    ws, wptr = _workspace(nbytes, q.device)
+    out = torch.empty((B, Sq, H, D), dtype=torch.float32, device=q.device)
+    sc = scale if scale is not None else 1.0 / math.sqrt(D)
+    args = (q.data_ptr(), ldq, bsq, kc.data_ptr(), vc.data_ptr(), _i32_pos(pos, B).data_ptr(), _ptr(c), _ptr(s_), R,
+            out.data_ptr(), out.stride(1), out.stride(0), B, H, Hkv, Sq, L, D, float(sc), wptr, nbytes)
+    if window is not None:
+        _lib.check(lib.nos_attn_h3g_cache_ring(*args, int(window), int(limit), _stream()), "nos_attn_h3g_cache_ring")
+    else:
+        _lib.check(lib.nos_attn_h3g_cache(*args, _stream()), "nos_attn_h3g_cache")
+    return out
+
+
 def sdpa_cache(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: torch.Tensor, scale: float | None = None,
                rope: tuple | None = None, fresh: tuple | None = None, sync: torch.Tensor | None = None,
                partials: bool = False, scales: tuple | None = None, window: int | None = None,
-               limit: int | None = None):
+               limit: int | None = None, flash: bool | None = None):
     """Query i of sequence b, at position pos[b] + i, attends the cached keys
     0 .. pos[b] + i: q [B, Sq, H, D], caches [B, L, Hkv, D] (fp32 / bf16).
     ``rope`` = (cos, sin): q rotated at its positions inside the kernel.
@@ -896,7 +952,20 @@ def sdpa_cache(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: torch.T
     there by :func:`kv_write` with the same pair, or as ``fresh`` rows; rows
     at positions >= limit dropped).  min(limit, window + Sq - 1) <= C <=
     limit; a counter outside [0, limit) gives zero rows.  The partials carry
-    the ring's split count."""
+    the ring's split count.
+
+    ``flash``: the h3 flash kernel over the caches (attention_h3g.hip
+    ``nos_attn_h3g_cache`` / ``nos_attn_h3g_cache_ring``: the matrix pipes,
+    work bounded by the counters) instead of the one-token decode kernel --
+    fp32 q and caches, no ``sync`` or ``partials`` (``ValueError``
+    otherwise); ``fresh`` rows are written first by :func:`kv_write`'s
+    launch (the same bits in the caches).  ``False``: the decode kernel.
+    ``None``: the compiler's rule (:func:`cache_flash_rule`: ``G x Sq > 32``,
+    where the decode kernel needs more than one pass), which the compiler
+    applies to a program's steps and passes on as ``True`` / ``False``; a
+    direct call has no step to mark and keeps the decode kernel, whose bits
+    its callers compare across ``sync``, ``partials``, rings and dtypes.
+    The CPU path is ``sdpa_cache_ref`` either way."""
     from ..podserver.program.reference import kv_write_ref, rotary_at_ref, sdpa_cache_ref
 
     q8 = kc.dtype == torch.int8
@@ -921,6 +990,10 @@ def sdpa_cache(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: torch.T
     if (kc.shape != vc.shape or kc.dtype != vc.dtype or kc.shape[0] != B or kc.shape[3] != D or H % Hkv
             or D not in (64, 128) or not kc.is_contiguous() or not vc.is_contiguous()):
         raise ValueError(f"sdpa_cache: q {tuple(q.shape)} vs caches {tuple(kc.shape)}")
+    if flash:
+        if q.dtype != torch.float32 or kc.dtype != torch.float32 or sync is not None or partials:
+            raise ValueError("sdpa_cache: flash needs fp32 q and caches (no bf16 / int8) and takes no sync or partials")
+        return _sdpa_cache_flash(q, kc, vc, pos, scale, rope, fresh, window if ring else None, limit)
     q, ldq, bsq = _rows(q)
     c = s_ = None
     R = 0
@@ -2467,11 +2540,12 @@ def moe_mx4(x: torch.Tensor, Wr: torch.Tensor, W13c: torch.Tensor, W13e: torch.T
 
 
 def set_attention_h3g_kvsplit(n: int) -> None:
-    """Key splits of :func:`sdpa` (0 = auto: fill the CU slots)."""
+    """Key splits of :func:`sdpa` and ``sdpa_cache(flash=True)`` (0 = auto: fill the CU slots)."""
     _lib.check(_lib.lib().nos_attn_h3g_set_kvsplit(int(n)), "nos_attn_h3g_set_kvsplit")
 
 
-__all__ = ["glu", "kv_write", "rotary_at", "sdpa_cache", "pos_update", "argmax", "sample", "sample_row_ref",
+__all__ = ["glu", "kv_write", "rotary_at", "sdpa_cache", "cache_flash_rule", "sdpa_cache_flash_workspace_bytes",
+           "pos_update", "argmax", "sample", "sample_row_ref",
            "sampling_ctl", "philox4x32", "gemv", "gemv_ok", "gemv_partials", "gemv_q8", "gemv_q8_ok", "gemv_q8_partials",
            "dequant_q8", "linear_q8", "linear_q8_ref", "gemv_mx4", "gemv_mx4_ok", "gemv_mx4_partials", "dequant_mx4",
            "linear_mx4", "linear_mx4_ref","lora", "lora_ref", "lora_shrink", "lora_shrink_ref", "lora_expand_ref", "linear_lora",

@@ -86,6 +86,7 @@ class Lowered:
             steps = self._fuse_rotary_sdpa(steps)
             steps = self._fuse_rotary_at(steps)
             steps = self._merge_kv_writes(steps)
+            self._mark_cache_flash(steps)
             if "kv_into_attention" not in skip:
                 steps = self._fuse_kv_write_attention(steps)
             if os.environ.get("NOS_AMD_FOLD_DECODE_COMBINE", "0") == "1":   # opt-in (A/B: slower alone)
@@ -1234,6 +1235,27 @@ class Lowered:
         self.stats["kv_writes_paired"] = n
         return [s for s in steps if id(s) not in drop]
 
+    def _mark_cache_flash(self, steps: list[_Step]) -> None:
+        """A multi-token ``sdpa_cache`` of an fp32 tenant over fp32 caches (plain or ring; an ``extend``
+        chunk, a windowed prefill longer than its window) whose ``G x Sq`` rows the decode kernel would take
+        in more than one pass runs on the h3 flash kernel over the caches instead (``attrs["flash"]``;
+        ``ops.tenant.cache_flash_rule``, ``NOS_AMD_CACHE_FLASH=0``: never).  Its layer's paired ``kv_write``
+        stays a launch of its own and the step gets no ``sync`` and no ``partials``: the O-projection reads
+        a finished o.  Steps at or under the rule keep their decode fusions."""
+        from ...ops.tenant import cache_flash_rule
+
+        n = 0
+        for s in steps:
+            if s.kind != "sdpa_cache":
+                continue
+            (_, sq, h, d), hkv = tuple(self._shape(s.inputs[0])), tuple(self._shape(s.inputs[1]))[2]
+            fp32 = (not s.attrs.get("scales")
+                    and all(self._dtype(i) == "fp32" for i in (s.inputs[0], s.inputs[1], s.inputs[2], s.output)))
+            if hkv and h % hkv == 0 and cache_flash_rule(h // hkv, sq, d, fp32):
+                s.attrs = {**s.attrs, "flash": True}
+                n += 1
+        self.stats["flash_cache"] = n
+
     def _fuse_kv_write_attention(self, steps: list[_Step]) -> list[_Step]:
         """GPU: a layer's paired K / V cache write whose new cache versions only
         its ``sdpa_cache`` reads, at the same positions and (K and q) with the
@@ -1248,7 +1270,7 @@ class Lowered:
         by_out = {s.output: s for s in steps}
         drop, n = set(), 0
         for s in steps:
-            if s.kind != "sdpa_cache" or s.attrs.get("fresh"):
+            if s.kind != "sdpa_cache" or s.attrs.get("fresh") or s.attrs.get("flash"):
                 continue
             w = by_out.get(s.inputs[2])
             if w is None or w.kind != "kv_write" or not w.attrs.get("pair") or s.inputs[1] != w.attrs.get("k_out"):
@@ -1284,7 +1306,7 @@ class Lowered:
             return
         n = 0
         for s in steps:
-            if s.kind != "sdpa_cache":
+            if s.kind != "sdpa_cache" or s.attrs.get("flash"):
                 continue
             B, Hkv = tuple(self._shape(s.inputs[1]))[0], tuple(self._shape(s.inputs[1]))[2]
             name = s.output + "::sync"
@@ -1308,7 +1330,7 @@ class Lowered:
                 by_input.setdefault(i, []).append(t)
         drop, n, nq = set(), 0, {k: 0 for k in QUANT_LINEARS}
         for s in steps:
-            if s.kind != "sdpa_cache" or s.attrs.get("sync") or uses.get(s.output) != 1:
+            if s.kind != "sdpa_cache" or s.attrs.get("sync") or s.attrs.get("flash") or uses.get(s.output) != 1:
                 continue
             shp = tuple(self._shape(s.output))
             if len(shp) != 4 or shp[1] != 1 or shp[0] > 8 or shp[3] not in (64, 128) or self._dtype(s.output) != "fp32":

@@ -197,7 +197,8 @@ class CompiledProgram(Lowered):
                                  rope=(a[4], a[5]) if s.attrs.get("rope") else None,
                                  fresh=(a[-2], a[-1]) if s.attrs.get("fresh") else None,
                                  sync=self.aux.get(s.attrs.get("sync")), partials=bool(s.attrs.get("partials")),
-                                 scales=sc or None, window=s.attrs.get("window"), limit=s.attrs.get("limit"))
+                                 scales=sc or None, window=s.attrs.get("window"), limit=s.attrs.get("limit"),
+                                 flash=bool(s.attrs.get("flash")))
             elif k == "rotary_at":
                 y = T.rotary_at(a[0], a[1], a[2], a[3])
             elif k == "stop_step":   # pos_add(pos, done) / stop_ids / done_mark: next ids, pos, done, ctl

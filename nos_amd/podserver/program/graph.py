@@ -206,7 +206,24 @@ class Program:
         # the state (K / V caches, positions) is allocated once, at registration,
         # and never grows at replay: it counts in full against the slice
         return (self.param_bytes + planes + persistent + self.state_bytes + sum(v.nbytes for v in self.inputs)
-                + 2 * peak)
+                + 2 * peak + self.cache_flash_workspace())
+
+    def cache_flash_workspace(self) -> int:
+        """The workspace of the flash attention over the K / V caches (``nos_attn_h3g_cache_workspace``: the
+        planes of a whole cache, re-split on every call and dropped after it), for the ``sdpa_cache`` nodes
+        the compiler's rule moves there (``ops.tenant.cache_flash_rule``) -- once per program (its layers run
+        one after the other), 0 without such a node."""
+        from ...ops.tenant import cache_flash_rule, sdpa_cache_flash_workspace_bytes
+
+        need = 0
+        for n in self.nodes:
+            if n.op != "sdpa_cache":
+                continue
+            q, kc = self.values[n.inputs[0]], self.values[n.inputs[1]]
+            (b, sq, h, d), (_, l, hkv, _) = q.shape, kc.shape
+            if hkv and h % hkv == 0 and cache_flash_rule(h // hkv, sq, d, q.dtype == "fp32" and kc.dtype == "fp32"):
+                need = max(need, sdpa_cache_flash_workspace_bytes(b, h, hkv, sq, l, d))
+        return need
 
     # ------------------------------------------------------------ tensors
     def tensors(self, device) -> dict:
